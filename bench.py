@@ -2,7 +2,7 @@
 """bench.py -- tiles/s of the MI355X tile-encoder hot path (BASELINE.json configs[1]: ViT-L/14 tile extraction
 on synthetic 224x224x3 u8 tiles, random-init weights of that architecture).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,8 +10,10 @@ A "step" is one pass of the hot path over one virtual slide of `--tiles` u8 tile
 im2col -> patch-embed GEMM -> 24 x {LN, QKV GEMM, attention, proj GEMM(+residual), LN, fc1 GEMM(+GELU),
 fc2 GEMM(+residual)} -> final LN on CLS -> fp16 features in HBM.  Slides shard across ranks (weak scaling: every
 rank encodes its own slide per step); for N>1 every step ends with the path's one collective, an RCCL all-gather
-of the slide-level embeddings.  Rank 0 prints ONE JSON line.  Beside `value` (HBM-resident, the contract's metric) the
-single-GPU line carries:
+of the slide-level embeddings.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes
+the last step's output under --dump-outputs DIR (features.npy; slide_embeddings.npy for N>1) and prints the line:
+`value` (HBM-resident, the contract's metric), `ms_per_step`, and the roofline of the GEMMs from that same timed region.
+With --full, the single-GPU line also carries:
   end_to_end   SURVEY.md 8d's M1: a pinned host pool of --e2e-tiles DISTINCT tiles -> double-buffered H2D -> encode -> fp16
                features D2H, wall clock from the first H2D enqueue to the last feature row on the host (PCIe-inclusive)
   drop_in_b64  what an unmodified `extract_` gets: `model(tiles.to(device)).detach().half().cpu()` on batches of 64
@@ -52,13 +54,37 @@ def parse() -> argparse.Namespace:
     ap.add_argument("--fp8", action="store_true", help="headline run with HipViT(fp8=True): the blocks' Linears on the fp8 MFMA (opt-in, ~6 %% feature error)")
     ap.add_argument("--check", default="fallback", choices=("fallback", "raise", "off"), help="HipViT's guard in front of the features (default: the product's default; 'off' for A/B)")
     ap.add_argument("--exact", action="store_true", help="headline run with HipViT(exact=True): the class-token rows also on an exact-fp32 stream")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="headline workload only (for a ViT-only rocprofv3 kernel trace)")
+    ap.add_argument("--full", action="store_true", help="after the headline, run every other leg too: end-to-end, opt-in modes, slide pipeline, "
+                    "drop-in loop, MIL / CTransPath secondaries, re-timed blocks and the CPU baselines (default: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32; a fixed seeded sample of rows past 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip every GPU leg beyond the headline")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--e2e-tiles", type=int, default=100_000, help="distinct tiles of the end-to-end (M1) leg; 0 = skip")
     ap.add_argument("--slide-tiles", type=int, default=20_736, help="tiles of the synthetic-slide leg (decode threads -> GPU resize / Canny -> encoder -> .h5); 0 = skip")
     ap.add_argument("--e2e-warmup", type=int, default=2, help="batches of the end-to-end leg run before its clock starts")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: each array as <out_dir>/<name>.npy in float32, so that two builds can be compared output for output on the same
+    seeded inputs.  An array past its share of the 64 MB budget is written as a sample of its rows (seeded: the same rows every run)."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        x = t.detach().float().cpu().numpy()
+        if x.nbytes > share:
+            keep = max(share // (x.nbytes // x.shape[0]), 1)
+            x = x[np.sort(np.random.default_rng(0).choice(x.shape[0], size=keep, replace=False))]
+        np.save(d / f"{name}.npy", np.ascontiguousarray(x, dtype=np.float32))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -723,6 +749,8 @@ def dry_run(a, ctx, D) -> None:
         out = step()
     D.barrier(ctx)
     elapsed = D.max_over_ranks(ctx, time.perf_counter() - t0)
+    if a.dump_outputs and ctx.is_main:
+        dump_outputs(a.dump_outputs, {"slide_embeddings" if ctx.world > 1 else "features": out})
     if ctx.world > 1:
         mine = (tiles.reshape(tiles.shape[0], -1).float() @ proj).half().float().mean(dim=0)
         assert out.shape == (ctx.world, 32) and torch.equal(out[ctx.rank], mine), "this rank's slide embedding is not in the gathered table"
@@ -797,6 +825,8 @@ def main() -> None:
     lib.amds_profile_enable(actx, 0)
     elapsed = D.max_over_ranks(ctx, elapsed)
     assert torch.isfinite(out.float()).all()
+    if a.dump_outputs and ctx.is_main:
+        dump_outputs(a.dump_outputs, {"slide_embeddings" if ctx.world > 1 else "features": out})
     clock0 = sampler.summary()
 
     def headline_block() -> dict:
@@ -868,7 +898,7 @@ def main() -> None:
                    "gflop_per_tile_executed": round(flops_exec / 1e9, 3),
                    "whole_path_mfma_frac": round(value / ctx.world * flops_exec / 1e12 / MFMA_PEAK_TFLOPS, 4),
                    # shader clock / socket power of rank 0's GPU during the timed region (hwmon freq1_input / power1_input every 20 ms): `value` above is
-                   # block 0; the single-GPU line re-times the same K steps after the end-to-end leg and at the very end (blocks_tiles_per_s, median_block)
+                   # block 0; the single-GPU --full line re-times the same K steps after the end-to-end leg and at the very end (blocks_tiles_per_s, median_block)
                    "sclk_mhz": clock0["sclk_mhz"], "sclk_mhz_min": clock0["sclk_mhz_min"], "socket_w": clock0["socket_w"], "socket_w_max": clock0["socket_w_max"],
                    "clock_power_samples": clock0["samples"], "blocks_tiles_per_s": [round(value / ctx.world, 1)], "blocks": [{"tiles_per_s": round(value / ctx.world, 1), **clock0}]},
         "roofline": {"kernel": "MFMA GEMMs (gemm_tn_kernel 128x96 / 128x128 tiles where N is not a multiple of 256, gemm_4w16_kernel in stage 4 and the stage-3 MLP)" if is_swin else
@@ -885,9 +915,9 @@ def main() -> None:
                      "avg_gflop_per_launch": round(gflop / max(gn, 1) / 1e9, 2),
                      "time_share": {k: round(v[0] / (elapsed * 1e3), 4) for k, v in kinds.items()}},
     }
-    # Everything below is single-GPU-line only: these blocks are wrapped in try/except, and a rank that raised while the others
+    # Everything below is --full and single-GPU-line only: these blocks are wrapped in try/except, and a rank that raised while the others
     # wait in a collective would hang the N-GPU scaling run, whose purpose is the headline value.
-    single = ctx.world == 1 and not a.no_secondary
+    single = a.full and ctx.world == 1 and not a.no_secondary
     if single and a.e2e_tiles > 0:
         try:
             line["end_to_end"] = end_to_end_leg(model, cfg, ctx.device, a.e2e_tiles, a.swin_chunk if is_swin else a.chunk, a.e2e_warmup)
@@ -1012,7 +1042,7 @@ def main() -> None:
         add_block()          # block 2: the last GPU work of the run
         bl = sorted(line["config"]["blocks_tiles_per_s"])
         line["config"]["median_block_tiles_per_s"] = bl[len(bl) // 2] if bl else None
-    if ctx.is_main and ctx.world == 1 and not a.no_cpu_baseline:
+    if ctx.is_main and a.full and ctx.world == 1 and not a.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(cfg, sd, a.cpu_seconds, swin=is_swin)
         if not a.no_secondary:
             try:

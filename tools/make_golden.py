@@ -249,7 +249,10 @@ def golden_ticon() -> None:
         emb = torch.randn(9, d_in).half().float()
         with torch.no_grad():
             y = model(x=emb.unsqueeze(1), relative_coords=torch.zeros(9, 1, 2), tile_encoder_key=key).squeeze(1)
-        out[f"emb_{key}"], out[f"out_{key}"] = emb.numpy(), y.numpy()
+            # the same call in float64: what the fp32 result rounds depends on the host's BLAS kernels, the float64 one is the same on every host
+            y64 = model.double()(x=emb.double().unsqueeze(1), relative_coords=torch.zeros(9, 1, 2, dtype=torch.float64), tile_encoder_key=key).squeeze(1)
+            model.float()
+        out[f"emb_{key}"], out[f"out_{key}"], out[f"out64_{key}"] = emb.numpy(), y.numpy(), y64.numpy()
     out.update({k: v for k, v in sd_np(model).items() if ".decoder_" not in k and "output_proj" not in k and "mask_dict" not in k})
     save("ticon.npz", **out)
 
@@ -1016,6 +1019,39 @@ def golden_slide_mpp() -> None:
     print("wrote slide_mpp.json", {k: v.get("mpp", v.get("error")) for k, v in out.items()})
 
 
+CODE_HASH_BODIES = (b"print(1)\n", b"x = 2\n" * 1000, b"")          # tests/test_cpu_host.py writes the same three files
+EXTRACTOR_NAMES = ["chief-ctranspath-0a1b2c3d", "chief-ctranspath", "virchow2", "virchow2-deadbeef", "uni2-12345", "h-optimus-0", "h-optimus-0-abcdef12",
+                   " ctranspath-ABCDEF ", "mstar-xyz123", "conch1_5-00000000", "a-b-c-123456"]
+
+
+def golden_reference_facts() -> None:
+    """What tests/test_cpu_host.py checks the project's docs and host helpers against: the line count of every .py file of the reference
+    tree (so that a `file.py:line` citation can be checked to point inside its file), and the answers of the reference's own
+    `get_processing_code_hash` (utils/cache.py) and `_resolve_extractor_name` (encoding/encoder/__init__.py) on the test's inputs."""
+    import json
+    import re
+    import tempfile
+    from functools import cache
+
+    root = REF.parent.parent
+    lines = {p.relative_to(root).as_posix(): len(p.read_text().splitlines()) for p in sorted(root.rglob("*.py"))}
+    glb = {"hashlib": hashlib, "Path": Path, "cache": cache, "re": re}
+    for path, wanted in ((REF / "utils" / "cache.py", {"get_processing_code_hash"}), (REF / "encoding" / "encoder" / "__init__.py", {"_resolve_extractor_name"})):
+        tree = ast.parse(path.read_text())
+        body = [n for n in tree.body if (isinstance(n, ast.FunctionDef) and n.name in wanted) or
+                (isinstance(n, ast.Assign) and any(getattr(t, "id", "") == "_HASH_RE" for t in n.targets))]
+        exec(compile(ast.Module(body=body, type_ignores=[]), str(path), "exec"), glb)
+    with tempfile.TemporaryDirectory() as td:
+        for i, b in enumerate(CODE_HASH_BODIES):
+            (Path(td) / f"m{i}.py").write_bytes(b)
+        (Path(td) / "notes.txt").write_text("ignored")
+        code_hash = glb["get_processing_code_hash"](Path(td) / "m0.py")
+    out = {"py_line_counts": lines, "code_hash_of_three_files": code_hash,
+           "resolve_extractor_name": {n: glb["_resolve_extractor_name"](n) for n in EXTRACTOR_NAMES}}
+    (OUT / "reference_facts.json").write_text(json.dumps(out, indent=1) + "\n")
+    print("wrote reference_facts.json:", len(lines), "files")
+
+
 def main() -> None:
     install_shims()
     golden_chief()
@@ -1038,6 +1074,7 @@ def main() -> None:
     golden_tiling()
     golden_tile_cache()
     golden_slide_mpp()
+    golden_reference_facts()
 
 
 if __name__ == "__main__":

@@ -7,7 +7,7 @@ O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 # 1. the default bench line (all legs)
-timeout 900 python $R/bench.py 2> $O/${TAG}_bench_err.log | tail -1 > $O/${TAG}_bench_default.json
+timeout 900 python $R/bench.py --full 2> $O/${TAG}_bench_err.log | tail -1 > $O/${TAG}_bench_default.json
 # 2. ViT-only kernel trace: totals and per GEMM shape
 timeout 400 rocprofv3 --kernel-trace -d /tmp/ks -o ks -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --e2e-tiles 0 > /tmp/ks.log 2>&1 < /dev/null
 DB=$(find /tmp/ks -name "*.db" | head -1)
@@ -29,7 +29,7 @@ timeout 400 rocprofv3 --kernel-trace -d /tmp/k8 -o k8 -- python $R/bench.py --st
 DB=$(find /tmp/k8 -name "*.db" | head -1); [ -n "$DB" ] && timeout 60 python $R/tools/rocprof_summary.py "$DB" > $O/${TAG}_rocprofv3_vitonly_kernel_stats_fp8.txt
 timeout 300 python $R/tools/gemm_fp8_bench.py > $O/${TAG}_gemm_fp8_bench.txt 2>&1
 for m in uni2_h virchow2; do
-  timeout 500 python $R/bench.py --model $m --no-secondary --e2e-tiles 0 --cpu-seconds 8 2>> $O/${TAG}_bench_err.log | tail -1 > $O/${TAG}_bench_$m.json
+  timeout 500 python $R/bench.py --full --model $m --no-secondary --e2e-tiles 0 --cpu-seconds 8 2>> $O/${TAG}_bench_err.log | tail -1 > $O/${TAG}_bench_$m.json
 done
 # 5. MIL training step, slide pipeline
 timeout 300 rocprofv3 --kernel-trace -d /tmp/kt -o kt -- python $R/tools/train_only.py 8 > /tmp/kt.log 2>&1 < /dev/null
