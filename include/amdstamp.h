@@ -1166,6 +1166,43 @@ int amds_convert_f16_bf16(const void* src, void* dst, long n, void* stream);
 int amds_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
                float weight_decay, int step, void* stream);
 
+/* Dynamic loss scaling of fp16 training (torch.amp.GradScaler semantics, without a host synchronisation inside a step).
+ * The state lives in device memory (48 bytes, 4-byte aligned); the host reads it only when it wants a read-out.
+ * A step:  dlogits * scale (the 0-d device float at offset 0)  ->  backward  ->  [data-parallel average]  ->
+ *          amds_grad_unscale_check  ->  amds_adamw_guarded  ->  amds_loss_scale_update(apply = 1).
+ * Back-off: scale * backoff, floored at min_scale, on a step with a non-finite gradient value (the step is skipped).  Growth:
+ * scale * growth, capped at max_scale, after growth_interval consecutive clean steps.  With max_scale = the initial scale a run that
+ * never overflows keeps that scale and amds_adamw's bits exactly. */
+typedef struct amds_loss_scale_state {
+    float scale;              /* current loss scale */
+    float inv_scale;          /* 1 / scale */
+    int32_t nonfinite;        /* non-finite gradient values counted in the current step (reset by the update) */
+    int32_t last_nonfinite;   /* the count of the last step the update closed */
+    int32_t clean_steps;      /* consecutive clean steps since the last change of scale */
+    int32_t skipped;          /* total skipped steps */
+    int32_t growth_interval;
+    float backoff;            /* e.g. 0.5 */
+    float growth;             /* e.g. 2 */
+    float min_scale;
+    float max_scale;          /* the cap of growth: the initial scale */
+    int32_t reserved;
+} amds_loss_scale_state;
+/* Writes a fresh state (one lane; no host-to-device copy).  min_scale <= init_scale <= max_scale, 0 < backoff < 1 <= growth. */
+int amds_loss_scale_init(amds_loss_scale_state* state, float init_scale, int growth_interval, float backoff, float growth,
+                         float min_scale, float max_scale, void* stream);
+/* g[0..n) *= inv_scale in place, in one pass, and the non-finite values (NaN, +-inf) among them added to state->nonfinite (one atomic add per
+ * workgroup that found any).  float4 per lane when g is 16-byte aligned, any n.  Several calls may share one state (several gradient tensors
+ * of one step).  The bits of g are those of g * inv_scale in fp32. */
+int amds_grad_unscale_check(float* g, long n, amds_loss_scale_state* state, void* stream);
+/* amds_adamw gated on the state: a non-zero state->nonfinite writes nothing to p, m, v; otherwise amds_adamw's arithmetic, with its own
+ * host-side bias corrections for `step` while state->skipped == 0 (same bits), and torch's for t = step - state->skipped (applied steps)
+ * after a skip.  `step`: the 1-based count of attempted steps. */
+int amds_adamw_guarded(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+                       float weight_decay, int step, const amds_loss_scale_state* state, void* stream);
+/* One lane, launched after the guarded AdamW.  apply = 1: back-off (and skipped + 1) or growth as above; apply = 0 (a step that computed
+ * gradients but applies no update): scale and counters untouched.  Both record the count in last_nonfinite and reset it. */
+int amds_loss_scale_update(amds_loss_scale_state* state, int apply, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

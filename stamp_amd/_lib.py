@@ -339,6 +339,10 @@ PROTOTYPES = {
     "amds_attention_dropout_mask": (_i, [_vp, _i, _i, _i, _f, _u64, _u32, _vp]),
     "amds_convert_f16_bf16": (_i, [_vp, _vp, _l, _vp]),
     "amds_adamw": (_i, [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _vp]),
+    "amds_loss_scale_init": (_i, [_vp, _f, _i, _f, _f, _f, _f, _vp]),
+    "amds_grad_unscale_check": (_i, [_vp, _l, _vp, _vp]),
+    "amds_adamw_guarded": (_i, [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _vp, _vp]),
+    "amds_loss_scale_update": (_i, [_vp, _i, _vp]),
     "amds_gated_attn_pool_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "amds_gated_attn_pool": (_i, [_vp, C.POINTER(GapWeights), _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "amds_gated_attn_pool_batched_supported": (_i, [_i, _i, _i]),

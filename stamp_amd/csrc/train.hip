@@ -10,6 +10,9 @@
 //   amds_layernorm_bwd        dx (+ skip gradient), per-block partial d(gamma), d(beta)  -> amds_colsum finishes them
 //   amds_gelu_fwd / _bwd      exact-erf GELU on a stored pre-activation
 //   amds_adamw                fused decoupled-weight-decay Adam on one flat fp32 parameter buffer
+//   amds_loss_scale_init / amds_grad_unscale_check / amds_adamw_guarded / amds_loss_scale_update
+//                             dynamic loss scaling of fp16 training: a device-resident state, the gradients unscaled and their non-finite
+//                             values counted in one pass, an AdamW step that a non-finite count turns into a no-op, the scale's back-off / growth
 #include "common.h"
 
 namespace amds {
@@ -314,6 +317,107 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
         pi -= (lr / bc1) * mi / (sqrtf(vi) / sqrtf(bc2) + eps);
         p[i] = pi;
     }
+}
+
+// ---- dynamic loss scaling (include/amdstamp.h, "MIL training step") ----------------------------------------------------------
+// The state is device memory the host never reads inside a step: the unscale pass adds its workgroups' non-finite counts, the guarded
+// AdamW reads the count (every block the same value: nothing writes it during that launch) and the one-lane update launch after it moves
+// the scale and resets the count.  Every write of the state is a plain C++ store from one lane.
+__global__ void loss_scale_init_kernel(amds_loss_scale_state* st, float scale, int interval, float backoff, float growth, float min_scale,
+                                       float max_scale) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    amds_loss_scale_state s;
+    s.scale = scale; s.inv_scale = 1.0f / scale;
+    s.nonfinite = 0; s.last_nonfinite = 0; s.clean_steps = 0; s.skipped = 0; s.growth_interval = interval;
+    s.backoff = backoff; s.growth = growth; s.min_scale = min_scale; s.max_scale = max_scale; s.reserved = 0;
+    *st = s;
+}
+
+// g *= inv_scale in place, non-finite values counted (NaN compares false, +-inf exceeds FLT_MAX; scaling by a power of two keeps both).
+// VEC: 16-byte aligned g, float4 per lane over the first n & ~3 elements, the last n & 3 by the first lanes of the grid.
+template <bool VEC>
+__global__ void __launch_bounds__(256) grad_unscale_check_kernel(float* __restrict__ g, long n, amds_loss_scale_state* __restrict__ st) {
+    const float inv = st->inv_scale;
+    const long tid = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+    int bad = 0;
+    long tail = 0;
+    if (VEC) {
+        const long n4 = n >> 2;
+        float4* g4 = reinterpret_cast<float4*>(g);
+        for (long i = tid; i < n4; i += stride) {
+            float4 x = g4[i];
+            bad += !(fabsf(x.x) <= 3.402823466e38f);
+            bad += !(fabsf(x.y) <= 3.402823466e38f);
+            bad += !(fabsf(x.z) <= 3.402823466e38f);
+            bad += !(fabsf(x.w) <= 3.402823466e38f);
+            x.x *= inv; x.y *= inv; x.z *= inv; x.w *= inv;
+            g4[i] = x;
+        }
+        tail = n4 << 2;
+    }
+    for (long i = tail + tid; i < n; i += stride) {
+        const float x = g[i];
+        bad += !(fabsf(x) <= 3.402823466e38f);
+        g[i] = x * inv;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+    __shared__ int red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = bad;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int total = (red[0] + red[1]) + (red[2] + red[3]);
+        if (total) atomicAdd(&st->nonfinite, total);            // one atomic per workgroup, and none from a clean one
+    }
+}
+
+// adamw_kernel's update, gated on the step's non-finite count.  bc1 / bc2: the host's powf values for `step` -- used while no step was skipped, so a
+// run that never overflows keeps amds_adamw's bits; after a skip the bias corrections are torch's for t = step - skipped (applied steps only).
+__global__ void adamw_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
+                                     float lr, float b1, float b2, float eps, float wd, float bc1, float bc2, int step,
+                                     const amds_loss_scale_state* __restrict__ st) {
+    if (st->nonfinite != 0) return;
+    const int skipped = st->skipped;
+    if (skipped > 0) {
+        const float t = (float)(step - skipped);
+        bc1 = 1.0f - powf(b1, t);
+        bc2 = 1.0f - powf(b2, t);
+    }
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) {
+        float pi = p[i] * (1.0f - lr * wd);
+        const float gi = g[i];
+        const float mi = b1 * m[i] + (1.0f - b1) * gi;
+        const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+        m[i] = mi; v[i] = vi;
+        pi -= (lr / bc1) * mi / (sqrtf(vi) / sqrtf(bc2) + eps);
+        p[i] = pi;
+    }
+}
+
+// One lane, after the guarded AdamW (no block of that launch can still be reading the count).  apply: the step's scale decision
+// (GradScaler.update); otherwise the count is only recorded in last_nonfinite and reset.
+__global__ void loss_scale_update_kernel(amds_loss_scale_state* st, int apply) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const int bad = st->nonfinite;
+    st->last_nonfinite = bad;
+    if (apply) {
+        float s = st->scale;
+        int clean = st->clean_steps;
+        if (bad) {
+            s = fmaxf(s * st->backoff, st->min_scale);
+            clean = 0;
+            st->skipped = st->skipped + 1;
+        } else if (++clean >= st->growth_interval) {
+            s = fminf(s * st->growth, st->max_scale);
+            clean = 0;
+        }
+        st->clean_steps = clean;
+        st->scale = s;
+        st->inv_scale = 1.0f / s;
+    }
+    st->nonfinite = 0;
 }
 
 __global__ void f16_to_bf16_kernel(const f16* __restrict__ src, bf16* __restrict__ dst, long n) {
@@ -681,6 +785,46 @@ extern "C" int amds_adamw(float* p, const float* g, float* m, float* v, long n, 
     const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
     hipLaunchKernelGGL(adamw_kernel, dim3(grid1d(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2);
     AMDS_LAUNCH_CHECK("adamw_kernel");
+    return AMDS_OK;
+}
+
+extern "C" int amds_loss_scale_init(amds_loss_scale_state* state, float init_scale, int growth_interval, float backoff, float growth,
+                                    float min_scale, float max_scale, void* stream) {
+    AMDS_REQUIRE(state && init_scale > 0.f && growth_interval >= 1 && backoff > 0.f && backoff < 1.f && growth >= 1.f && min_scale > 0.f &&
+                 min_scale <= init_scale && init_scale <= max_scale, "amds_loss_scale_init: bad arguments");
+    hipLaunchKernelGGL(loss_scale_init_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, init_scale, growth_interval, backoff, growth,
+                       min_scale, max_scale);
+    AMDS_LAUNCH_CHECK("loss_scale_init_kernel");
+    return AMDS_OK;
+}
+
+extern "C" int amds_grad_unscale_check(float* g, long n, amds_loss_scale_state* state, void* stream) {
+    AMDS_REQUIRE(state && n >= 0 && (g || n == 0), "amds_grad_unscale_check: bad arguments");
+    if (n == 0) return AMDS_OK;
+    const bool vec = ((uintptr_t)g & 15) == 0;
+    const long work = vec ? (n + 3) / 4 : n;
+    const int grid = (int)min((long)2048, (work + 255) / 256);
+    if (vec) hipLaunchKernelGGL(grad_unscale_check_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, g, n, state);
+    else hipLaunchKernelGGL(grad_unscale_check_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, g, n, state);
+    AMDS_LAUNCH_CHECK("grad_unscale_check_kernel");
+    return AMDS_OK;
+}
+
+extern "C" int amds_adamw_guarded(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+                                  float weight_decay, int step, const amds_loss_scale_state* state, void* stream) {
+    AMDS_REQUIRE(p && g && m && v && state && n >= 0 && step >= 1, "amds_adamw_guarded: bad arguments");
+    if (n == 0) return AMDS_OK;
+    const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);       // amds_adamw's values
+    hipLaunchKernelGGL(adamw_guarded_kernel, dim3(grid1d(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay,
+                       bc1, bc2, step, state);
+    AMDS_LAUNCH_CHECK("adamw_guarded_kernel");
+    return AMDS_OK;
+}
+
+extern "C" int amds_loss_scale_update(amds_loss_scale_state* state, int apply, void* stream) {
+    AMDS_REQUIRE(state, "amds_loss_scale_update: bad arguments");
+    hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, apply);
+    AMDS_LAUNCH_CHECK("loss_scale_update_kernel");
     return AMDS_OK;
 }
 

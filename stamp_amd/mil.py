@@ -15,18 +15,27 @@ Lightning drives it (reference models/__init__.py:133-141, 239-279), and ``torch
 (heatmaps/__init__.py:36-56).  Modes:
   * ``.eval()`` under ``torch.no_grad()`` / ``inference_mode()``: inference kernels, fp16 MFMA operands, any bag length, ``mask``
     supported (restated literally from :355-381).
-  * gradient needed, or ``.train()``: training kernels, bf16 operands, fp32 accumulate / residual stream / statistics.  In
-    ``.train()`` mode the reference's dropout sites are live (project_features and nn.MultiheadAttention: `dropout`; both
-    feed-forward Dropouts: the hard-coded 0.5 of :160) with counter-based masks seeded from torch's CPU generator, and every
-    ALiBi `_RunningMeanScaler` buffer is updated before use (:24-29).  ``mask`` is not available on this path.
+  * gradient needed, or ``.train()``: training kernels, 16-bit operands by torch's float32_matmul_precision (as
+    `mil_train.HipMilVitTrainer`: bf16 at "medium", fp16 with a 2^10 loss scale at "high" / "highest"), fp32 accumulate / residual
+    stream / statistics.  In ``.train()`` mode the reference's dropout sites are live (project_features and nn.MultiheadAttention:
+    `dropout`; both feed-forward Dropouts: the hard-coded 0.5 of :160) with counter-based masks seeded from torch's CPU generator, and
+    every ALiBi `_RunningMeanScaler` buffer is updated before use (:24-29).  ``mask`` is not available on this path.
+    fp16 overflow: a torch optimiser cannot skip a step, so this path returns finite results instead.  Non-finite fp16 logits -> the
+    forward is re-run on bf16 operands (fp32's range; `HipViT(check="fallback")` does the same).  Non-finite un-scaled gradients (dbags
+    included) -> the backward is re-run from the saved activations at half the scale (exact: a power of two), at most
+    `_FP16_BWD_HALVINGS` times, then forward and backward on bf16 operands for that step.  Each check is one 4-byte device-to-host read;
+    `model.fp16_overflow_events` counts the calls that needed a remedy.
 There is no CPU / torch fallback: CPU tensors raise.
 """
 from __future__ import annotations
+
+import ctypes
 
 import torch
 from torch import nn
 
 from . import _lib, mil_core, ops
+from . import train_ops as T
 from .mil_core import PackedVit, VitDims
 
 
@@ -78,6 +87,49 @@ class _Saved:
     saved = None
     pk = None
     shapes = None
+    model = None
+    rerun_bf16 = None        # fp16 forward: () -> (bf16 pack, saved) of the same step, the backward's last resort
+
+
+_FP16_BWD_HALVINGS = 3       # fp16 backward re-runs at 2^-1 .. 2^-3 of the scale before the step falls back to bf16 operands
+
+
+def _all_finite(x: torch.Tensor) -> bool:
+    """amds_check_finite over an fp32 device tensor: one 4-byte device-to-host read (synchronises the stream)."""
+    if x.device.type != "cuda":          # (host tensors only come from the kernels' stand-ins of the CPU plumbing tests: nothing to guard)
+        return True
+    cnt = torch.empty(1, dtype=torch.int32, device=x.device)
+    host = ctypes.c_int(0)
+    rc = _lib.lib().amds_check_finite(x.data_ptr(), x.numel(), _lib.F32, cnt.data_ptr(), ctypes.byref(host), ops._stream())
+    if rc not in (0, _lib.ERR_RANGE):
+        _lib.check(rc, "check_finite")
+    return host.value == 0
+
+
+def _unscaled_checked(G: dict, dbags, names, need_params: bool, need_bags: bool, sc: float):
+    """The fp16 backward's outputs * (1 / sc): the parameter gradients gathered into ONE flat fp32 buffer (in `names` order) and dbags, each
+    un-scaled by `amds_grad_unscale_check` with the non-finite values counted into one state -> (gradients, dbags, all finite).  The bits
+    of G[n] * (1 / sc); one 4-byte read of the count."""
+    if not (need_params or need_bags):
+        return [], dbags, True
+    dev = dbags.device if need_bags else next(iter(G.values())).device
+    if dev.type != "cuda":               # (as in _all_finite: the stand-ins' host tensors are un-scaled, not guarded)
+        return [(G[n] * (1.0 / sc)).contiguous() for n in names] if need_params else [], dbags * (1.0 / sc) if need_bags else dbags, True
+    st = T.loss_scale_state(dev, sc)
+    gp = []
+    if need_params:
+        sizes = [G[n].numel() for n in names]
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+        o = 0
+        for n, k in zip(names, sizes):
+            gp.append(flat[o:o + k].view(G[n].shape))
+            gp[-1].copy_(G[n])
+            o += k
+        T.grad_unscale_check(flat, st)
+    if need_bags:
+        dbags = dbags.contiguous()
+        T.grad_unscale_check(dbags.view(-1), st)
+    return gp, dbags, int(st[T.LS_NONFINITE].item()) == 0
 
 
 def _unwrap_batched(t: torch.Tensor):
@@ -94,15 +146,31 @@ class _MilVitBackward(torch.autograd.Function):
 
     @staticmethod
     def forward(dlogits, holder, need_params, need_bags, names):
-        sc = getattr(holder, "loss_scale", 1.0)        # fp16 operands ("high"): the 16-bit gradient tensors carry a static power-of-two scale (mil_train.py)
-        G, dbags = mil_core.backward(holder.pk, holder.saved, dlogits * sc if sc != 1.0 else dlogits, need_params=need_params, need_bags=need_bags)
+        sc = getattr(holder, "loss_scale", 1.0)        # fp16 operands ("high"): the 16-bit gradient tensors carry a power-of-two scale (mil_train.py)
         if sc != 1.0:
-            dbags = dbags * (1.0 / sc) if need_bags else dbags
-            for k in (list(G) if need_params else ()):         # in place: the mapping mil_core.backward returned is kept as it is
-                G[k] = G[k] * (1.0 / sc)
+            return _MilVitBackward._fp16(dlogits, holder, need_params, need_bags, names, sc)
+        G, dbags = mil_core.backward(holder.pk, holder.saved, dlogits, need_params=need_params, need_bags=need_bags)
         outs = [dbags if need_bags else dlogits.new_zeros(())]
         outs += [G[n].contiguous() for n in names] if need_params else []
         return tuple(outs)
+
+    @staticmethod
+    def _fp16(dlogits, holder, need_params, need_bags, names, sc):
+        """The fp16 backward with its guard (module docstring): the scale halved on non-finite gradients, then bf16 operands."""
+        for _ in range(_FP16_BWD_HALVINGS + 1):
+            G, dbags = mil_core.backward(holder.pk, holder.saved, dlogits * sc, need_params=need_params, need_bags=need_bags)
+            gp, dbags, ok = _unscaled_checked(G, dbags, names, need_params, need_bags, sc)
+            if ok:
+                break
+            sc *= 0.5
+        else:       # non-finite at every scale tried: this step (and any later backward of the same forward) on bf16 operands, fp32's range
+            holder.pk, holder.saved = holder.rerun_bf16()
+            holder.loss_scale = 1.0
+            G, dbags = mil_core.backward(holder.pk, holder.saved, dlogits, need_params=need_params, need_bags=need_bags)
+            gp = [G[n].contiguous() for n in names] if need_params else []
+        if sc != holder.loss_scale:
+            holder.model.fp16_overflow_events += 1
+        return (dbags if need_bags else dlogits.new_zeros(()), *gp)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -136,9 +204,22 @@ class _MilVitFunction(torch.autograd.Function):
 
         # operand type by torch's own flag, as HipMilVitTrainer: "medium" -> bf16; "high" (the reference's training setting, train.py:519) / "highest" -> fp16
         act = torch.bfloat16 if torch.get_float32_matmul_precision() == "medium" else torch.float16
-        pk = PackedVit(model.dims, get, act, train=True)
-        logits, saved = mil_core.forward_train(pk, bags.detach(), None if coords is None else coords.detach(), training=training, seed=seed)
+        def run(dt):
+            pk = PackedVit(model.dims, get, dt, train=True)
+            return (pk, *mil_core.forward_train(pk, bags.detach(), None if coords is None else coords.detach(), training=training, seed=seed))
+
+        pk, logits, saved = run(act)
+        if act == torch.float16 and not _all_finite(logits):      # an fp16 activation overflowed: the same step (same dropout masks) on bf16 operands
+            model.fp16_overflow_events += 1
+            act = torch.bfloat16
+            pk, logits, saved = run(act)
         holder.pk, holder.saved, holder.loss_scale = pk, saved, (1.0 if act == torch.bfloat16 else 1024.0)
+        holder.model = model
+        if act == torch.float16:
+            def rerun_bf16():
+                pk16, _, saved16 = run(torch.bfloat16)
+                return pk16, saved16
+            holder.rerun_bf16 = rerun_bf16
         return logits
 
     @staticmethod
@@ -171,6 +252,7 @@ class VisionTransformer(nn.Module):
         self.transformer = _TransformerParams(dim_model, n_layers, n_heads, dim_feedforward, dropout, use_alibi)
         self.mlp_head = nn.Sequential(nn.Linear(dim_model, dim_output))
         self._param_names = [n for n, _ in self.named_parameters()]
+        self.fp16_overflow_events = 0           # fp16 training calls that needed a remedy (module docstring); not part of the state_dict
         self._packed: PackedVit | None = None
         self._packed_key = None
 

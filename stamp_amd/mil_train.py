@@ -23,9 +23,17 @@ Mixed precision (stated, not hidden): 16-bit MFMA operands for activations, weig
 stream and its gradient, fp32 LayerNorm / softmax statistics, fp32 master weights, gradients and Adam moments.  WHICH 16-bit type
 follows torch's own flag, like the TransMIL head's products do: the reference calls `torch.set_float32_matmul_precision("high")` before
 training (src/stamp/modeling/train.py:519) -- TF32-class products, 10 explicit mantissa bits per operand -- so under "high" (and
-"highest") the operands are **fp16** (10 explicit bits, like TF32) and the loss is scaled by a static 2^10 on its way into the backward
+"highest") the operands are **fp16** (10 explicit bits, like TF32) and the loss is scaled by 2^10 on its way into the backward
 (fp16's exponent range; the fp32 gradients are un-scaled before AdamW); under "medium" (bf16 products in torch's own wording) they are
 **bf16** (8 bits, fp32's exponent range, no loss scaling) -- the only mode before round 6.  `precision=` overrides the flag.
+fp16's range is finite, and one inf / NaN gradient would enter P, m and v through AdamW for good (the reference's TF32 products have fp32's
+range and cannot fail so).  So the fp16 scale is DYNAMIC by default, as torch's GradScaler: a device-resident state
+(`amds_loss_scale_state`) whose scale multiplies dlogits as a 0-d tensor; the un-scaling pass over the flat gradient also counts its
+non-finite values (`amds_grad_unscale_check`, replacing the plain multiply); AdamW is skipped ON THE DEVICE when the count is non-zero
+(`amds_adamw_guarded`: no write to P, m, v; bias corrections by applied steps, as torch's AdamW under GradScaler); a one-lane launch then
+halves the scale (floored at `min_loss_scale`) or doubles it after `scale_growth_interval` clean steps, capped at `loss_scale` -- so a
+run that never overflows keeps 2^10 and the static scale's bits exactly.  No host synchronisation inside a step; `skipped_steps` and
+`current_loss_scale` read the state when asked, `fit` records the skipped steps per epoch.  `dynamic_loss_scale=False`: the static scale.
 The loss on the [batch, classes] logits is the one tiny piece left to torch.
 """
 from __future__ import annotations
@@ -84,19 +92,23 @@ class OneCycleClock:
 class HipMilVitTrainer:
     def __init__(self, model: VisionTransformer, *, device="cuda", max_lr: float = 1e-4, div_factor: float = 25.0,
                  total_steps: int = 1000, weight_decay: float = 0.01, split_k: int = 32, dropout: bool | None = None,
-                 sched_interval: str = "epoch", precision: str | None = None, loss_scale: float = 1024.0) -> None:
+                 sched_interval: str = "epoch", precision: str | None = None, loss_scale: float = 1024.0, dynamic_loss_scale: bool = True,
+                 scale_growth_interval: int = 2000, min_loss_scale: float = 1.0) -> None:
         """dropout: None = as the reference's train mode (live when the model's rates are > 0; the feed-forward rate is always 0.5);
         False = all dropout sites off (deterministic steps, e.g. for parity tests against autograd).
         sched_interval: "epoch" (default; what Lightning does with the reference's bare scheduler, see the module docstring: call
         `epoch_end()` after every epoch -- `fit` does) or "step" (OneCycle advanced after every optimiser step).
         precision: None = torch.get_float32_matmul_precision() at construction ("high" under the reference's train_model_, train.py:519); "high" /
-        "highest" -> fp16 operands + static loss scale `loss_scale`; "medium" -> bf16 operands, no scaling (module docstring)."""
+        "highest" -> fp16 operands + loss scale `loss_scale`; "medium" -> bf16 operands, no scaling (module docstring).
+        dynamic_loss_scale (fp16 only): `loss_scale` is the initial scale and the cap; a step with a non-finite gradient is skipped on the device
+        and the scale halved (not below `min_loss_scale`); `scale_growth_interval` clean steps double it.  False = the static scale, unchecked."""
         self.precision = precision or torch.get_float32_matmul_precision()
         if self.precision not in ("medium", "high", "highest"):
             raise ValueError(f"precision must be 'medium', 'high' or 'highest', got {self.precision!r}")
         self.act = BF if self.precision == "medium" else torch.float16
         # fp16 gradients: a static power-of-two scale on dlogits (exact) lifts the 16-bit gradient tensors out of fp16's subnormal range; un-scaled in fp32
         self.loss_scale = 1.0 if self.act == BF else float(loss_scale)
+        self._ls = None                  # the device-resident loss-scale state (train_ops.loss_scale_state), fp16 + dynamic only
         self.model = model
         self.dims = model.dims
         self.alibi = bool(model.use_alibi)
@@ -127,6 +139,19 @@ class HipMilVitTrainer:
         self.clock = OneCycleClock(total_steps, max_lr, div_factor, sched_interval)
         self._lrs, self._b1s = self.clock.lrs, self.clock.b1s
         self.pk = PackedVit(self.dims, self.p, self.act, train=True)
+        if dynamic_loss_scale and self.act != BF:
+            self._ls = T.loss_scale_state(self.dev, self.loss_scale, growth_interval=scale_growth_interval, min_scale=min_loss_scale)
+            self._ls_scale = T.loss_scale_of(self._ls)
+
+    # ---- loss-scale read-outs (each synchronises when read; nothing inside a step does) ------------------------------------------------
+    @property
+    def skipped_steps(self) -> int:
+        """Optimiser steps skipped so far because a gradient was not finite (0 without a dynamic scale)."""
+        return 0 if self._ls is None else int(self._ls[T.LS_SKIPPED].item())
+
+    @property
+    def current_loss_scale(self) -> float:
+        return self.loss_scale if self._ls is None else float(T.loss_scale_of(self._ls).item())
 
     # ---- parameter views ------------------------------------------------------------------------------------------------
     def p(self, name: str) -> torch.Tensor:
@@ -165,7 +190,11 @@ class HipMilVitTrainer:
         (the reference itself is single-device, src/stamp/modeling/train.py:541-547).
 
         update=False computes loss, logits and gradients and leaves EVERY piece of state as it was: no optimiser step, and the ALiBi
-        running-mean buffers (which a train-mode forward updates before use, vision_tranformer.py:24-29) are put back afterwards."""
+        running-mean buffers (which a train-mode forward updates before use, vision_tranformer.py:24-29) are put back afterwards.  (With a
+        dynamic loss scale the gradients are un-scaled and checked; scale and counters stay.)
+
+        A step the dynamic loss scale skips (non-finite gradient) still advances the OneCycle clock (torch's scheduler under GradScaler),
+        keeps the forward's ALiBi running-mean update (as the reference module would) and returns its loss and logits."""
         if update or not self.alibi:
             return self._step(bags, targets, class_weights, update, data_parallel, coords, loss_fn, seed)
         stats_before = self.P[self._stat_idx].clone()
@@ -201,27 +230,37 @@ class HipMilVitTrainer:
             dlogits = torch.autograd.grad(loss, lg, allow_unused=True)[0] if loss.requires_grad else None
         if dlogits is None:      # e.g. a Cox batch without events (cox.py:219-224 returns a constant 0): nothing to learn from, no step
             return loss.detach(), logits
-        if self.loss_scale != 1.0:
+        if self._ls is not None:
+            dlogits = dlogits * self._ls_scale          # 0-d device tensor: no synchronisation
+        elif self.loss_scale != 1.0:
             dlogits = dlogits * self.loss_scale
         G, _ = mil_core.backward(self.pk, saved, dlogits, need_params=True, need_bags=False, split_k=self.split_k, grad_views=self.g)
         grouped = self._copy_grouped_grads(G) if self.alibi else ()
         for k, gk in G.items():          # (unpadded geometries: the library wrote into the flat buffer's views themselves -- nothing to copy)
             if k not in grouped and gk.data_ptr() != self.g(k).data_ptr():
                 self.g(k).copy_(gk)
-        if self.loss_scale != 1.0:
+        if self._ls is None and self.loss_scale != 1.0:
             self.G.mul_(1.0 / self.loss_scale)
         # ---- AdamW + OneCycleLR ---------------------------------------------------------------------------------------------------
         if dist_on:
-            average_gradients(self.G)
+            average_gradients(self.G)        # (dynamic scale: before the check, so every rank counts the same values and takes the same decision)
+        if self._ls is not None:
+            T.grad_unscale_check(self.G, self._ls)
         if update:
             self.step_count += 1
             lr, b1 = self.clock.current()
             stats = self.P[self._stat_idx].clone() if self.alibi else None      # buffers: not touched by the optimiser (weight decay)
-            T.adamw(self.P, self.G, self.m, self.v, lr, self.step_count, betas=(b1, 0.999), weight_decay=self.wd)
+            if self._ls is not None:
+                T.adamw_guarded(self.P, self.G, self.m, self.v, lr, self.step_count, self._ls, betas=(b1, 0.999), weight_decay=self.wd)
+                T.loss_scale_update(self._ls, apply=True)
+            else:
+                T.adamw(self.P, self.G, self.m, self.v, lr, self.step_count, betas=(b1, 0.999), weight_decay=self.wd)
             self.clock.after_step()
             if stats is not None:
                 self.P[self._stat_idx] = stats
             self._refresh()
+        elif self._ls is not None:
+            T.loss_scale_update(self._ls, apply=False)
         return loss.detach(), logits
 
     def _copy_grouped_grads(self, G: dict) -> set:
@@ -272,19 +311,28 @@ def fit(trainer: HipMilVitTrainer, train_batches, valid_batches, *, max_epochs: 
     After every epoch the validation loss (same objective, eval mode: no dropout, frozen scalers; Lightning's mean over batches
     weighted by batch size) is computed; training stops when it has not improved for `patience` epochs (EarlyStopping, mode min);
     the best epoch's weights are restored and copied into `trainer.model` (the reference copies the best checkpoint and reloads
-    it).  `num_sanity_val_steps=0` like the reference.  Returns the history."""
+    it).  `num_sanity_val_steps=0` like the reference.  Returns the history; `skipped_steps` holds the optimiser steps per epoch the dynamic
+    loss scale skipped (fp16 gradients not finite), and `log` is warned about each epoch that skipped any."""
     dev = trainer.dev
     best = {"loss": float("inf"), "epoch": -1, "P": None}
-    hist = {"train_loss": [], "validation_loss": [], "best_epoch": -1, "stopped_epoch": None}
+    hist = {"train_loss": [], "validation_loss": [], "skipped_steps": [], "best_epoch": -1, "stopped_epoch": None}
     wait = 0
+    skipped = getattr(trainer, "skipped_steps", 0)          # (any object with the trainer's step / predict / epoch_end drives this loop)
     for epoch in range(max_epochs):
-        tot, cnt = 0.0, 0
+        tot, cnt, steps = 0.0, 0, 0
         for bags, coords, _sizes, targets in train_batches():
             loss, _ = trainer.step(bags.to(dev), targets, class_weights, coords=None if coords is None else coords.to(dev), loss_fn=loss_fn)
             tot += float(loss) * bags.shape[0]
             cnt += bags.shape[0]
+            steps += 1
         trainer.epoch_end()
         hist["train_loss"].append(tot / max(cnt, 1))
+        now = getattr(trainer, "skipped_steps", 0)
+        hist["skipped_steps"].append(now - skipped)
+        if log and now > skipped:
+            log(f"warning: epoch {epoch}: {now - skipped} of {steps} optimiser steps skipped (fp16 gradients not finite); "
+                f"loss scale now {trainer.current_loss_scale:g}")
+        skipped = now
         vtot, vcnt = 0.0, 0
         for bags, coords, _sizes, targets in valid_batches():
             lg = trainer.predict(bags.to(dev), None if coords is None else coords.to(dev))

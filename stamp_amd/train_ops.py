@@ -189,6 +189,48 @@ def adamw(p, g, m, v, lr: float, step: int, betas=(0.9, 0.999), eps: float = 1e-
     _lib.check(_lib.lib().amds_adamw(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, betas[0], betas[1], eps, weight_decay, step, _stream()), "adamw")
 
 
+# ---- dynamic loss scaling (amds_loss_scale_state, include/amdstamp.h): the state is a 12-word int32 device tensor ----------------------------
+LS_WORDS = 12
+LS_SCALE, LS_INV_SCALE, LS_NONFINITE, LS_LAST_NONFINITE, LS_CLEAN_STEPS, LS_SKIPPED, LS_GROWTH_INTERVAL = range(7)
+
+
+def loss_scale_state(device, init_scale: float, growth_interval: int = 2000, backoff: float = 0.5, growth: float = 2.0,
+                     min_scale: float = 1.0, max_scale: float | None = None) -> torch.Tensor:
+    """A fresh device-resident loss-scale state (written by a one-lane kernel: no host-to-device copy).  max_scale None = init_scale."""
+    st = torch.empty(LS_WORDS, dtype=torch.int32, device=device)
+    _dev(st)
+    _lib.check(_lib.lib().amds_loss_scale_init(_p(st), float(init_scale), int(growth_interval), float(backoff), float(growth), float(min_scale),
+                                               float(init_scale if max_scale is None else max_scale), _stream()), "loss_scale_init")
+    return st
+
+
+def loss_scale_of(state: torch.Tensor) -> torch.Tensor:
+    """The current scale as a 0-d fp32 device tensor (a view of the state: multiplying by it needs no host synchronisation)."""
+    return state.view(torch.float32)[LS_SCALE]
+
+
+def grad_unscale_check(g: torch.Tensor, state: torch.Tensor) -> None:
+    """g *= 1/scale in place (fp32, contiguous), its non-finite values counted into the state."""
+    _dev(g, state)
+    assert g.dtype == torch.float32 and g.is_contiguous() and state.dtype == torch.int32 and state.numel() == LS_WORDS
+    _lib.check(_lib.lib().amds_grad_unscale_check(_p(g), g.numel(), _p(state), _stream()), "grad_unscale_check")
+
+
+def adamw_guarded(p, g, m, v, lr: float, step: int, state: torch.Tensor, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01) -> None:
+    """`adamw`, skipped on the device when the state counted a non-finite gradient; bias corrections by applied steps."""
+    _dev(p, g, m, v, state)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (p, g, m, v)) and p.numel() == g.numel() == m.numel() == v.numel()
+    assert state.dtype == torch.int32 and state.numel() == LS_WORDS
+    _lib.check(_lib.lib().amds_adamw_guarded(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, betas[0], betas[1], eps, weight_decay, step, _p(state),
+                                             _stream()), "adamw_guarded")
+
+
+def loss_scale_update(state: torch.Tensor, apply: bool = True) -> None:
+    """Close a step: back-off / growth when `apply` (GradScaler.update), then reset the step's count."""
+    _dev(state)
+    _lib.check(_lib.lib().amds_loss_scale_update(_p(state), int(bool(apply)), _stream()), "loss_scale_update")
+
+
 def attention_alibi_fwd_train(qkv: torch.Tensor, coords: torch.Tensor, inv_running_mean: torch.Tensor, bias_scale: torch.Tensor,
                               B: int, T: int, H: int):
     """ALiBi attention forward that saves what its backward needs: returns (out, U, Osm: bf16; lse fp32 [B,H,T])."""
