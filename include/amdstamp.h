@@ -784,6 +784,40 @@ int amds_mil_vit_forward(const amds_mil_vit_cfg* cfg_host, const amds_mil_vit_we
                          const float* coords, const uint8_t* mask, float* logits, int n_bags, int n_tiles, void* ws, size_t ws_bytes,
                          void* stream);
 
+/* ---- ragged bags: the same inference forward over bags of DIFFERENT lengths packed without padding, one call --------------------------------------------
+ * The reference validates and deploys one bag per call (src/stamp/modeling/train.py:467-477: `bag_size=None`, `batch_size=1`; deploy.py:390-456); its
+ * padding `mask` cannot stand in for that, since it blocks a pair only when BOTH tokens are padded (vision_tranformer.py:359-368).  Layout (the cu_seqlens
+ * convention): `offsets` is a DEVICE int32 array [n_bags + 1]; bag i owns tile rows offsets[i] .. offsets[i+1] - 1 of the packed feats [total_tiles][n_feats]
+ * (coords [total_tiles][2] alike), and its Tn_i = len_i + 1 token rows, class token first, start at row offsets[i] + i of the [total_tiles + n_bags]
+ * token-major tensors.  max_tiles >= every len_i.  The library cannot read `offsets` without a host synchronisation: the kernels clamp them (offsets to
+ * [0, total_tiles], lengths to [0, max_tiles]) so that a malformed array cannot address outside the buffers -- its results are then undefined; callers validate
+ * on the host (stamp_amd.mil_core.pack_bags).  Each bag's q | k | v rows must stay below the 2 GB of a buffer descriptor: (max_tiles + 1) * 3 * Ha * 128 < 2^31
+ * (AMDS_ERR_INVALID otherwise).  n_bags <= 65535; n_bags == 0 returns AMDS_OK and launches nothing.  Launches only, on `stream`; ws 256-byte aligned.
+ *
+ * amds_mil_vit_forward_ragged: logits fp32 [n_bags][classes], mask = None semantics (no padding exists), eval mode (vision_tranformer.py:332-384).  Bag i's row
+ * equals amds_mil_vit_forward on that bag alone, bit for bit, when the bag has at most amds_mil_vit_ragged_max_shared_tiles(cfg) tiles or is the call's only
+ * bag: the GEMM kernel of each layer's GEMMs is that of the longest bag's own call when that is the small-problem kernel, by shape otherwise (the default
+ * dispatch picks by M, amds_gemm_ex).  The class-row tail (amds_set_mil_cls_tail) runs, without ALiBi, when the context's switch is on and max_tiles + 1 <= 32768;
+ * every bag of <= 32767 tiles gets that decision in its own call too.  feats_dtype AMDS_F32 / AMDS_F16 / AMDS_BF16; coords required when cfg.alibi. */
+size_t amds_mil_vit_ragged_workspace_bytes(const amds_mil_vit_cfg* cfg_host, int n_bags, long total_tiles, int max_tiles);
+int amds_mil_vit_forward_ragged(const amds_mil_vit_cfg* cfg_host, const amds_mil_vit_weights* w_host, const void* feats, int feats_dtype,
+                                const float* coords, const int* offsets, float* logits, int n_bags, long total_tiles, int max_tiles, void* ws, size_t ws_bytes,
+                                void* stream);
+/* The largest tile count a bag may have and still share a ragged call with other bags bit-identically (32767 at most; -1 on a bad cfg).  Host-side, no launch. */
+int amds_mil_vit_ragged_max_shared_tiles(const amds_mil_vit_cfg* cfg_host);
+/* The attention of the ragged layout on its own, equal under each bag's slice to the fixed-pitch entry on that bag (amds_attention, amds_attention_alibi,
+ * amds_attention_row): qkv [total_tiles + n_bags][3 H 64] 16-bit token rows, H heads of 64 channels (reference vision_tranformer.py:191, 217-227; ALiBi
+ * :42-74).  amds_attention_varlen: out [total_tiles + n_bags][H 64] in dtype; amds_attention_alibi_varlen: coords fp32 [total_tiles + n_bags][2] of the TOKEN rows
+ * (class token at (0, 0)), head_scale [H], out bf16; amds_attention_row_varlen: the one-query form for the class-row tail, q [n_bags][ldq] and out [n_bags][ldo]
+ * compact (16-bit), max_tiles + 1 <= 32768.  Workspace: amds_attention_varlen_workspace_bytes(n_bags, total_tiles) (the per-call table built from `offsets`). */
+size_t amds_attention_varlen_workspace_bytes(int n_bags, long total_tiles);
+int amds_attention_varlen(const void* qkv, const int* offsets, void* out, int n_bags, long total_tiles, int max_tiles, int H, int dtype, void* ws,
+                          size_t ws_bytes, void* stream);
+int amds_attention_alibi_varlen(const void* qkv, const float* coords, const float* head_scale, const int* offsets, void* out, int n_bags, long total_tiles,
+                                int max_tiles, int H, int dtype, void* ws, size_t ws_bytes, void* stream);
+int amds_attention_row_varlen(const void* q, long ldq, const void* qkv, const int* offsets, void* out, long ldo, int n_bags, long total_tiles, int max_tiles,
+                              int H, int dtype, void* ws, size_t ws_bytes, void* stream);
+
 /* The TRAINING step of the same head, forward and backward as one call each (reference: the train-mode forward of
  * vision_tranformer.py:332-384 with its Dropout sites :157-169, :191, :314-318 live, and loss.backward() through it,
  * src/stamp/modeling/models/__init__.py:239-279).  cfg.dtype = AMDS_BF16 or AMDS_F16: the type of EVERY 16-bit tensor of the step (operand copies of the

@@ -254,6 +254,13 @@ PROTOTYPES = {
     "amds_linear_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "amds_mil_vit_workspace_bytes": (_sz, [_vp, _i, _i]),
     "amds_mil_vit_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "amds_mil_vit_ragged_workspace_bytes": (_sz, [_vp, _i, _l, _i]),
+    "amds_mil_vit_forward_ragged": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _l, _i, _vp, _sz, _vp]),
+    "amds_mil_vit_ragged_max_shared_tiles": (_i, [_vp]),
+    "amds_attention_varlen_workspace_bytes": (_sz, [_i, _l]),
+    "amds_attention_varlen": (_i, [_vp, _vp, _vp, _i, _l, _i, _i, _i, _vp, _sz, _vp]),
+    "amds_attention_alibi_varlen": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _l, _i, _i, _i, _vp, _sz, _vp]),
+    "amds_attention_row_varlen": (_i, [_vp, _l, _vp, _vp, _vp, _l, _i, _l, _i, _i, _i, _vp, _sz, _vp]),
     "amds_barspoon_workspace_bytes": (_sz, [_vp, _i, _i]),
     "amds_barspoon_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "amds_ticon_tile_workspace_bytes": (_sz, [_vp, _i]),

@@ -49,13 +49,19 @@ constexpr int FA_C_BYTES = FA_KT * 8;            // key coordinates (float2) of 
 #define FA_SPAN_OK(T, H) ((long)(T) * 3 * (H) * 128 < (1L << 31))
 __device__ __forceinline__ int attn_swz(int row) { return (((row >> 1) & 1) << 2) | ((row >> 2) & 3); }
 
-template <typename T, bool ALIBI, typename TO = T, bool MASK = false, bool DROP = false>
+// VARLEN (inference, plain or ALiBi; no MASK / DROP / lse): ragged bags packed without padding (amds_attention_varlen).  The grid is a flattened list of
+// (bag, 128-query block) work items built once per call from the bag offsets (varlen_plan_kernel): blockIdx.x indexes `vwork`, item = {first token row of
+// the bag, its token count Tn, q block, -}; Tn = 0 marks the slack at the end of the list (the host sizes the grid by a bound, not by the device-side sum).
+// Everything else is the fixed-pitch kernel: the same arithmetic per (bag, head, query) whatever the bag's neighbours.
+template <typename T, bool ALIBI, typename TO = T, bool MASK = false, bool DROP = false, bool VARLEN = false>
 __global__ void __launch_bounds__(256, 2) attn_flash_kernel(const T* __restrict__ qkv, TO* __restrict__ out, int Tn, int H,
                                                             const float* __restrict__ coords, const float* __restrict__ head_scale,
                                                             float* __restrict__ lse_out, const float* __restrict__ out_scale = nullptr,
                                                             TO* __restrict__ u_out = nullptr, TO* __restrict__ osm_out = nullptr,
                                                             const uint8_t* __restrict__ pad = nullptr, uint64_t seed = 0, uint32_t drop_stream = 0,
-                                                            uint32_t thr16 = 0, float keep_scale = 1.f, int mask_heads = 0) {
+                                                            uint32_t thr16 = 0, float keep_scale = 1.f, int mask_heads = 0,
+                                                            const int4* __restrict__ vwork = nullptr) {
+    static_assert(!(VARLEN && (MASK || DROP)), "the ragged form is the inference forward only");
     typedef typename Act<T>::vec8 vec8;
     constexpr int F2_STAGE = 2 * FA_K_BYTES + FA_C_BYTES;                // K rows | V rows | key coordinates (ALiBi)
     __shared__ __attribute__((aligned(16))) char smem[2 * F2_STAGE + (MASK ? 2 * FA_KT : 0)];
@@ -63,17 +69,26 @@ __global__ void __launch_bounds__(256, 2) attn_flash_kernel(const T* __restrict_
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
-    const int b = blockIdx.z, h = blockIdx.y, qblk = blockIdx.x;
+    const int b = blockIdx.z, h = blockIdx.y;
+    int qblk = blockIdx.x;
+    long row0 = (long)b * Tn;                                            // first token row of this bag
+    if constexpr (VARLEN) {
+        const int4 wk = vwork[blockIdx.x];
+        Tn = __builtin_amdgcn_readfirstlane(wk.y);
+        if (Tn <= 0) return;                                             // whole workgroup, before any barrier
+        row0 = __builtin_amdgcn_readfirstlane(wk.x);
+        qblk = __builtin_amdgcn_readfirstlane(wk.z);
+    }
     const int Dm = H * 64;
     const long ld = 3L * Dm;
-    const T* base = qkv + (long)b * Tn * ld + h * 64;
+    const T* base = qkv + row0 * ld + h * 64;
     const int ntile = (Tn + FA_KT - 1) / FA_KT;
 
     // LDS-DMA (attention_train.hip, attn_bwd_dkdv2_kernel): wave w requests 8-row pieces w and w + 4 of the K and V images, rows past the sequence read as 0;
     // ALiBi: the tile's 128 coordinate dwords by waves 0 and 1.  Only the padding flags (bytes at an odd stride) still travel through a register.
     const __amdgpu_buffer_rsrc_t rsrc_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base + Dm), 0, (int)((((long)Tn - 1) * ld + 64) * 2), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsrc_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base + 2 * Dm), 0, (int)((((long)Tn - 1) * ld + 64) * 2), 0x00020000);
-    const float* cbase = ALIBI ? coords + (long)b * Tn * 2 : nullptr;
+    const float* cbase = ALIBI ? coords + row0 * 2 : nullptr;
     const __amdgpu_buffer_rsrc_t rsrc_c = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ALIBI ? cbase : head_scale), 0, ALIBI ? Tn * 8 : 0, 0x00020000);
     uint8_t mreg = 0;
     const uint8_t* prow = nullptr;
@@ -275,7 +290,7 @@ __global__ void __launch_bounds__(256, 2) attn_flash_kernel(const T* __restrict_
     if (q < Tn) {
         const float inv = 1.0f / l;
         const float osc = (ALIBI && out_scale) ? out_scale[h] : 1.0f;
-        TO* orow = out + ((long)b * Tn + q) * Dm + h * 64;
+        TO* orow = out + (row0 + q) * Dm + h * 64;
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -287,7 +302,7 @@ __global__ void __launch_bounds__(256, 2) attn_flash_kernel(const T* __restrict_
                 if constexpr (ALIBI) {
                     if (u_out) {       // training: U = sum_k (dist / running_mean) v and the softmax part alone (out = Osm - bias_scale * U;
                                        // Osm cannot be rebuilt from the rounded out and U: |U| >> |Osm| cancels catastrophically)
-                        const long off = ((long)b * Tn + q) * Dm + h * 64 + dt * 32 + 8 * g + 4 * hi;
+                        const long off = (row0 + q) * Dm + h * 64 + dt * 32 + 8 * g + 4 * hi;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) w[e] = Act<TO>::from_f32(o2[dt][4 * g + e]);
                         *reinterpret_cast<typename Act<TO>::vec4*>(u_out + off) = w;
@@ -317,20 +332,30 @@ __device__ __forceinline__ float sum8_dpp(float v) {
 // phases) and a 16-way LDS reduction.  fp32 throughout; q [B][ldq] and out [B][ldo] are 16-bit rows of the heads' 64-channel slices.
 // DROP / lse: the training forward's form (amds_attention_fwd_train for query row `qrow` of every bag): dropout on the attention probabilities with the bits of
 // the blocked kernel (row key of (bag, head, qrow), one hash per key pair), the log2-domain log-sum-exp of the UNdropped softmax into lse[(b H + h) T + qrow].
-template <typename T, bool DROP = false>
+// VARLEN (inference): bag b's keys / values are the token rows vbags[b].x .. vbags[b].x + vbags[b].y - 1 of the packed qkv (varlen_plan_kernel; Tn is then the
+// launch's LDS bound, the bag's own count comes from the table); q / out stay compact [n_bags][ldq] / [n_bags][ldo].
+template <typename T, bool DROP = false, bool VARLEN = false>
 __global__ void __launch_bounds__(256) attn_row_kernel(const T* __restrict__ q, long ldq, const T* __restrict__ qkv, T* __restrict__ out, long ldo, int Tn, int H,
                                                        float* __restrict__ lse = nullptr, int qrow = 0, uint64_t seed = 0, uint32_t drop_stream = 0,
-                                                       uint32_t thr16 = 0, float keep_scale = 1.f) {
+                                                       uint32_t thr16 = 0, float keep_scale = 1.f, const int2* __restrict__ vbags = nullptr) {
+    static_assert(!(VARLEN && DROP), "the ragged form is the inference forward only");
     typedef typename Act<T>::vec8 vec8;
     typedef typename Act<T>::vec4 vec4;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h = blockIdx.x, b = blockIdx.y;
+    long row0 = (long)b * Tn;
+    if constexpr (VARLEN) {
+        const int2 bg = vbags[b];
+        row0 = __builtin_amdgcn_readfirstlane(bg.x);
+        Tn = min(__builtin_amdgcn_readfirstlane(bg.y), Tn);
+        if (Tn <= 0) return;
+    }
     extern __shared__ __attribute__((aligned(16))) float sS[];          // [Tn] scores -> weights | [16][64] partial outputs | [8] reductions
     float* sRed = sS + ((Tn + 3) & ~3);
     float* sW = sRed + 16 * 64;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int h = blockIdx.x, b = blockIdx.y;
     const int Dm = H * 64;
     const long ld = 3L * Dm;
-    const T* base = qkv + (long)b * Tn * ld + h * 64;
+    const T* base = qkv + row0 * ld + h * 64;
     // scores: eight lanes per key, one 16-byte chunk of the 128-byte key row each (a wave reads eight whole rows per instruction), the dot product summed over
     // the eight lanes by DPP.  (One key per thread -- 64 lanes on 64 different rows per instruction -- ran at 2.9 TB/s.)
     const int sub = tid & 7, kk = tid >> 3;
@@ -645,6 +670,106 @@ __global__ void __launch_bounds__(256) attn_row_alibi_bwd_kernel(const T* __rest
     }
 }
 
+// ---- ragged bags: the per-call table of the VARLEN kernels ---------------------------------------------------------------------------------------------------
+// One workgroup: bag i = tiles offsets[i] .. offsets[i+1] - 1, clamped so that a malformed array cannot address outside the buffers (offsets to [0, total],
+// lengths to [0, max_tiles]); its Tn = len + 1 token rows (class token first) start at row offsets[i] + i < total + n_bags.  Then the flattened (bag, q block)
+// list: an exclusive scan of the per-bag block counts (256 thread chunks + an LDS scan), each thread writes its bags' items, the slack up to `nwork` gets
+// Tn = 0.  Items past `nwork` (only possible for overlapping, malformed offsets) are dropped.
+__global__ void __launch_bounds__(256) varlen_plan_kernel(const int* __restrict__ offsets, int n, long total, int max_tiles, int2* __restrict__ bags,
+                                                          int4* __restrict__ work, long nwork) {
+    __shared__ long ssum[256];
+    const int tid = threadIdx.x;
+    const int per = (n + 255) / 256;
+    const int i0 = min(n, tid * per), i1 = min(n, i0 + per);
+    auto bag = [&](int i) {
+        const long a = min(max((long)offsets[i], 0L), total), e = min(max((long)offsets[i + 1], 0L), total);
+        const long len = min(max(e - a, 0L), (long)max_tiles);
+        return make_int2((int)(a + i), (int)(len + 1));
+    };
+    long acc = 0;
+    for (int i = i0; i < i1; ++i) {
+        const int2 bg = bag(i);
+        bags[i] = bg;
+        acc += (bg.y + 127) / 128;
+    }
+    ssum[tid] = acc;
+    __syncthreads();
+    for (int s = 1; s < 256; s <<= 1) {
+        const long v = tid >= s ? ssum[tid - s] : 0;
+        __syncthreads();
+        ssum[tid] += v;
+        __syncthreads();
+    }
+    long g = ssum[tid] - acc;
+    const long used = min(ssum[255], nwork);
+    for (int i = i0; i < i1; ++i) {
+        const int2 bg = bag(i);
+        const int nb = (bg.y + 127) / 128;
+        for (int k = 0; k < nb && g < nwork; ++k, ++g) work[g] = make_int4(bg.x, bg.y, k, 0);
+    }
+    for (long k = used + tid; k < nwork; k += 256) work[k] = make_int4(0, 0, 0, 0);
+}
+
+namespace {
+inline size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
+}  // namespace
+
+// sum over bags of ceil((len + 1) / 128) <= (total + n + 127 n) / 128
+long varlen_work_items(int n_bags, long total_tiles) { return (total_tiles + 128L * n_bags) / 128 + 1; }
+size_t varlen_table_bytes(int n_bags, long total_tiles) { return al256((size_t)n_bags * 8) + al256((size_t)varlen_work_items(n_bags, total_tiles) * 16); }
+const int2* varlen_table_bags(const void* table) { return reinterpret_cast<const int2*>(table); }
+
+int varlen_table_build(const int* offsets, int n_bags, long total_tiles, int max_tiles, void* table, hipStream_t st) {
+    char* t = reinterpret_cast<char*>(table);
+    hipLaunchKernelGGL(varlen_plan_kernel, dim3(1), dim3(256), 0, st, offsets, n_bags, total_tiles, max_tiles, reinterpret_cast<int2*>(t),
+                       reinterpret_cast<int4*>(t + al256((size_t)n_bags * 8)), varlen_work_items(n_bags, total_tiles));
+    AMDS_LAUNCH_CHECK("varlen_plan_kernel");
+    return AMDS_OK;
+}
+
+int attention_varlen_launch(const void* qkv, const float* coords, const float* head_scale, void* out, const void* table, int n_bags, long total_tiles,
+                            int H, int dtype, hipStream_t st) {
+    const int4* work = reinterpret_cast<const int4*>(reinterpret_cast<const char*>(table) + al256((size_t)n_bags * 8));
+    const dim3 grid((unsigned)varlen_work_items(n_bags, total_tiles), H, 1), block(256);
+    if (coords) {
+        if (dtype == AMDS_F16)
+            hipLaunchKernelGGL((attn_flash_kernel<f16, true, bf16, false, false, true>), grid, block, 0, st, (const f16*)qkv, (bf16*)out, 0, H, coords, head_scale,
+                               nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 1.f, 0, work);
+        else
+            hipLaunchKernelGGL((attn_flash_kernel<bf16, true, bf16, false, false, true>), grid, block, 0, st, (const bf16*)qkv, (bf16*)out, 0, H, coords, head_scale,
+                               nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 1.f, 0, work);
+        AMDS_LAUNCH_CHECK("attn_flash_kernel<alibi, varlen>");
+    } else {
+        if (dtype == AMDS_F16)
+            hipLaunchKernelGGL((attn_flash_kernel<f16, false, f16, false, false, true>), grid, block, 0, st, (const f16*)qkv, (f16*)out, 0, H, nullptr, nullptr,
+                               nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 1.f, 0, work);
+        else
+            hipLaunchKernelGGL((attn_flash_kernel<bf16, false, bf16, false, false, true>), grid, block, 0, st, (const bf16*)qkv, (bf16*)out, 0, H, nullptr, nullptr,
+                               nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 1.f, 0, work);
+        AMDS_LAUNCH_CHECK("attn_flash_kernel<varlen>");
+    }
+    return AMDS_OK;
+}
+
+int attention_row_varlen_launch(const void* q, long ldq, const void* qkv, void* out, long ldo, const void* table, int n_bags, int max_tiles, int H, int dtype,
+                                hipStream_t st) {
+    const int T = max_tiles + 1;
+    const size_t lds = ((size_t)((T + 3) & ~3) + 16 * 64 + 8) * 4;
+    const int2* bags = varlen_table_bags(table);
+    static bool attr_set[2] = {false, false};
+    if (dtype == AMDS_F16) {
+        if (!attr_set[0]) { AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_row_kernel<f16, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024)); attr_set[0] = true; }
+        hipLaunchKernelGGL((attn_row_kernel<f16, false, true>), dim3(H, n_bags), dim3(256), lds, st, (const f16*)q, ldq, (const f16*)qkv, (f16*)out, ldo, T, H,
+                           nullptr, 0, 0, 0, 0, 1.f, bags);
+    } else {
+        if (!attr_set[1]) { AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_row_kernel<bf16, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024)); attr_set[1] = true; }
+        hipLaunchKernelGGL((attn_row_kernel<bf16, false, true>), dim3(H, n_bags), dim3(256), lds, st, (const bf16*)q, ldq, (const bf16*)qkv, (bf16*)out, ldo, T, H,
+                           nullptr, 0, 0, 0, 0, 1.f, bags);
+    }
+    AMDS_LAUNCH_CHECK("attn_row_kernel<varlen>");
+    return AMDS_OK;
+}
+
 }  // namespace amds
 
 using namespace amds;
@@ -890,4 +1015,59 @@ extern "C" int amds_attention_fwd_train(const void* qkv, void* out, float* lse, 
     else { set_error("amds_attention_fwd_train: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
     AMDS_LAUNCH_CHECK("attn_flash_kernel<drop>");
     return AMDS_OK;
+}
+
+
+// ---- ragged bags (include/amdstamp.h, "ragged bags") ------------------------------------------------------------------------------------------------------------
+extern "C" size_t amds_attention_varlen_workspace_bytes(int n_bags, long total_tiles) {
+    if (n_bags < 0 || total_tiles < 0) return 0;
+    return varlen_table_bytes(n_bags, total_tiles);
+}
+
+static int varlen_check(const char* who, const void* qkv, const int* offsets, const void* out, int n_bags, long total_tiles, int max_tiles, int H, int dtype,
+                        const void* ws, size_t ws_bytes, int t_limit) {
+    AMDS_REQUIRE(qkv && offsets && out && ws, "%s: null pointer", who);
+    AMDS_REQUIRE(n_bags >= 0 && n_bags <= 65535 && total_tiles >= 0 && max_tiles >= 0 && max_tiles + 1 <= t_limit && H > 0 && H <= 65535 &&
+                 total_tiles + n_bags < (1L << 31) && FA_SPAN_OK(max_tiles + 1, H),
+                 "%s: bad shape n_bags=%d total_tiles=%ld max_tiles=%d H=%d (a bag's q | k | v rows must stay below the 2 GB of a buffer descriptor)", who, n_bags,
+                 total_tiles, max_tiles, H);
+    AMDS_REQUIRE(dtype == AMDS_F16 || dtype == AMDS_BF16, "%s: bad dtype %d", who, dtype);
+    const size_t need = varlen_table_bytes(n_bags, total_tiles);
+    if (ws_bytes < need) {
+        set_error("%s: workspace %zu < required %zu bytes", who, ws_bytes, need);
+        return AMDS_ERR_WORKSPACE;
+    }
+    AMDS_REQUIRE(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+    return AMDS_OK;
+}
+
+extern "C" int amds_attention_varlen(const void* qkv, const int* offsets, void* out, int n_bags, long total_tiles, int max_tiles, int H, int dtype, void* ws,
+                                     size_t ws_bytes, void* stream) {
+    int rc = varlen_check("amds_attention_varlen", qkv, offsets, out, n_bags, total_tiles, max_tiles, H, dtype, ws, ws_bytes, 1 << 30);
+    if (rc != AMDS_OK || n_bags == 0) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = varlen_table_build(offsets, n_bags, total_tiles, max_tiles, ws, st)) != AMDS_OK) return rc;
+    return attention_varlen_launch(qkv, nullptr, nullptr, out, ws, n_bags, total_tiles, H, dtype, st);
+}
+
+extern "C" int amds_attention_alibi_varlen(const void* qkv, const float* coords, const float* head_scale, const int* offsets, void* out, int n_bags,
+                                           long total_tiles, int max_tiles, int H, int dtype, void* ws, size_t ws_bytes, void* stream) {
+    AMDS_REQUIRE(coords && head_scale, "amds_attention_alibi_varlen: null pointer");
+    int rc = varlen_check("amds_attention_alibi_varlen", qkv, offsets, out, n_bags, total_tiles, max_tiles, H, dtype, ws, ws_bytes, 1 << 30);
+    if (rc != AMDS_OK || n_bags == 0) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = varlen_table_build(offsets, n_bags, total_tiles, max_tiles, ws, st)) != AMDS_OK) return rc;
+    return attention_varlen_launch(qkv, coords, head_scale, out, ws, n_bags, total_tiles, H, dtype, st);
+}
+
+extern "C" int amds_attention_row_varlen(const void* q, long ldq, const void* qkv, const int* offsets, void* out, long ldo, int n_bags, long total_tiles,
+                                         int max_tiles, int H, int dtype, void* ws, size_t ws_bytes, void* stream) {
+    AMDS_REQUIRE(q, "amds_attention_row_varlen: null pointer");
+    int rc = varlen_check("amds_attention_row_varlen", qkv, offsets, out, n_bags, total_tiles, max_tiles, H, dtype, ws, ws_bytes, 32768);
+    if (rc != AMDS_OK) return rc;
+    AMDS_REQUIRE(ldq >= H * 64 && ldo >= H * 64 && ldq % 8 == 0, "amds_attention_row_varlen: bad pitches ldq=%ld ldo=%ld", ldq, ldo);
+    if (n_bags == 0) return AMDS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = varlen_table_build(offsets, n_bags, total_tiles, max_tiles, ws, st)) != AMDS_OK) return rc;
+    return attention_row_varlen_launch(q, ldq, qkv, out, ldo, ws, n_bags, max_tiles, H, dtype, st);
 }

@@ -358,6 +358,17 @@ int layernorm_bwd_cast_dt(const float* dy, long dy_stride, const float* x, long 
                           int dx16_dtype, float p, uint64_t seed, uint32_t stream_id, void* stream);
 
 // amds_bgemm_f32 on the exact-fp32 MFMA whatever amds_set_matmul_precision says (transmil.hip): for the paths that promise exact fp32
+// ragged (variable-length) bags without padding, attention_flash.hip: a table built once per call from device offsets [n_bags + 1] (tile counts; bag i's
+// token rows, class token first, start at offsets[i] + i), lengths clamped to [0, max_tiles] and rows to the buffers on the device
+long varlen_work_items(int n_bags, long total_tiles);
+size_t varlen_table_bytes(int n_bags, long total_tiles);
+int varlen_table_build(const int* offsets, int n_bags, long total_tiles, int max_tiles, void* table, hipStream_t st);
+const int2* varlen_table_bags(const void* table);      // int2 {first token row, token count} per bag
+int attention_varlen_launch(const void* qkv, const float* coords, const float* head_scale, void* out, const void* table, int n_bags, long total_tiles,
+                            int H, int dtype, hipStream_t st);           // coords != NULL: ALiBi (out bf16)
+int attention_row_varlen_launch(const void* q, long ldq, const void* qkv, void* out, long ldo, const void* table, int n_bags, int max_tiles, int H,
+                                int dtype, hipStream_t st);
+int default_gemm_cfg(int M, int N, int K);
 int bgemm_f32_exact(const float* A, int lda, long sAo, long sAi, const float* B, int ldb, long sBo, long sBi, int transb, float* Cm, int ldc, long sCo, long sCi,
                     int outer, int inner, int M, int N, int K, float alpha, float diag, const float* bias, int accumulate, void* stream);
 }  // namespace amds

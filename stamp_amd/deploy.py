@@ -58,11 +58,47 @@ def model_from_checkpoint(ckpt: Mapping) -> torch.nn.Module:
     return model.eval()
 
 
+def _ragged_outputs(model, batches, device, bags_per_call: int, max_rows_per_call: int) -> list[torch.Tensor]:
+    """The per-batch outputs of the loop in `predict_`, with consecutive one-bag batches grouped (mil_core.group_bags) into ragged calls of a `vit` head
+    (`VisionTransformer.forward_ragged`): each batch's row is the one its own forward gives.  Batches of several bags keep their own forward."""
+    from . import mil_core
+
+    limit = mil_core.max_shared_tiles(model._infer_pack(torch.device(device)))
+    outs: list = []
+    pend: list = []
+
+    def flush():
+        if not pend:
+            return
+        for a, e in mil_core.group_bags([b.shape[0] for b, _ in pend], bags_per_call, max_rows_per_call, limit):
+            cs = None if pend[a][1] is None else [c for _, c in pend[a:e]]
+            out = model.forward_ragged([b for b, _ in pend[a:e]], coords=cs)
+            outs.extend(out.float().cpu().split(1, dim=0))
+        pend.clear()
+
+    for bags, coords, *_ in batches:
+        if bags.shape[0] == 1:
+            pend.append((bags[0].to(device), None if coords is None else coords[0].to(device)))
+            if len(pend) >= bags_per_call:
+                flush()
+            continue
+        flush()
+        out = model(bags.to(device), coords=None if coords is None else coords.to(device), mask=None)
+        outs.append(out.float().cpu())
+    flush()
+    return outs
+
+
 @torch.no_grad()
-def predict_(model: torch.nn.Module, batches: Iterable, patient_ids: Sequence[str], *, task: str, device="cuda") -> dict[str, torch.Tensor]:
+def predict_(model: torch.nn.Module, batches: Iterable, patient_ids: Sequence[str], *, task: str, device="cuda", bags_per_call: int = 1,
+             max_rows_per_call: int = 262144) -> dict[str, torch.Tensor]:
     """batches: iterable of (bags, coords, bag_sizes, targets) as the reference's test DataLoader yields them (full bags, batch 1,
     `modeling/data.py:255-277`); only bags / coords are used (`Lit*.predict_step`, `models/__init__.py:302-313`: `mask=None`).
-    Returns patient -> prediction on the CPU: class probabilities (classification), raw value (regression), risk score (survival)."""
+    Returns patient -> prediction on the CPU: class probabilities (classification), raw value (regression), risk score (survival).
+    bags_per_call > 1 (`vit` heads; other heads ignore it): consecutive bags share ONE ragged forward, at most `bags_per_call` bags and
+    `max_rows_per_call` token rows per call, a bag too long to share runs alone; every prediction is the one of the one-bag loop."""
+    if bags_per_call < 1 or max_rows_per_call < 1:
+        raise ValueError("bags_per_call and max_rows_per_call must be >= 1")
     if task not in ("classification", "regression", "survival"):
         raise ValueError(f"unknown task {task!r}")
     model = model.to(device).eval()
@@ -81,10 +117,15 @@ def predict_(model: torch.nn.Module, batches: Iterable, patient_ids: Sequence[st
             cat = {t: torch.softmax(v, dim=1) for t, v in cat.items()}
         n = next(iter(cat.values())).shape[0]
         return {pid: {t: cat[t][i] for t in cat} for i, pid in enumerate(list(patient_ids)[:n])}
-    outs = []
-    for bags, coords, *_ in batches:
-        out = model(bags.to(device), coords=None if coords is None else coords.to(device), mask=None)
-        outs.append(out.float().cpu())
+    from .mil import VisionTransformer
+
+    if bags_per_call > 1 and isinstance(model, VisionTransformer):
+        outs = _ragged_outputs(model, batches, device, bags_per_call, max_rows_per_call)
+    else:
+        outs = []
+        for bags, coords, *_ in batches:
+            out = model(bags.to(device), coords=None if coords is None else coords.to(device), mask=None)
+            outs.append(out.float().cpu())
     if not outs:
         return {}
     raw = torch.cat(outs, dim=0)

@@ -266,6 +266,21 @@ class VisionTransformer(nn.Module):
             self._packed_key = key
         return self._packed
 
+    def forward_ragged(self, bags, *, coords=None) -> torch.Tensor:
+        """Bags of DIFFERENT lengths in one library call: a list of [T_i, dim_input] tensors (coords: a list of [T_i, 2], required with ALiBi) ->
+        logits [N, dim_output], row i exactly `self(bags[i][None], coords=..., mask=None)` (packed without padding, so no mask is needed;
+        mil_core.forward_ragged: one library call, plus one per bag too long to share it).  Inference only: eval mode under torch.no_grad() / inference_mode()."""
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError("forward_ragged is the inference forward: call it in eval mode (.eval()) under torch.no_grad() or torch.inference_mode()")
+        bags = list(bags)
+        dev = bags[0].device if bags else next(self.parameters()).device
+        mil_core._validate_bags(bags, None if coords is None else list(coords), self.dim_input, self.use_alibi)
+        if bags and not bags[0].is_cuda:
+            raise RuntimeError("HIP MIL head needs bags on the GPU (no CPU fallback)")
+        if not bags:
+            return torch.empty(0, self.dim_output, dtype=torch.float32, device=dev)
+        return mil_core.forward_ragged(self._infer_pack(dev), bags, coords, device=dev)
+
     def forward(self, bags: torch.Tensor, *, coords: torch.Tensor | None = None, mask: torch.Tensor | None = None):
         if not bags.is_cuda:
             raise RuntimeError("HIP MIL head needs bags on the GPU (no CPU fallback)")

@@ -369,6 +369,158 @@ def forward_infer(pk: PackedVit, bags: torch.Tensor, coords: torch.Tensor | None
     return logits
 
 
+# ---- ragged inference forward: N bags of different lengths, no padding, one call ----------------------------------------------------
+MAX_SOLO_TILES = 32767          # a longer bag takes the full last block in its own call (amds_mil_vit_forward's class-row tail stops at 32768 tokens)
+
+
+@dataclass(frozen=True)
+class RaggedBags:
+    """Bags packed without padding (include/amdstamp.h, "ragged bags"): bag i = rows offsets[i] .. offsets[i+1] - 1 of `feats`."""
+    feats: torch.Tensor                     # [total_tiles, F], contiguous, on the device
+    coords: torch.Tensor | None             # [total_tiles, 2] fp32 or None
+    offsets: torch.Tensor                   # device int32 [n_bags + 1]
+    lengths: tuple                          # host tile counts
+
+    @property
+    def n_bags(self) -> int:
+        return len(self.lengths)
+
+    @property
+    def total_tiles(self) -> int:
+        return int(sum(self.lengths))
+
+    @property
+    def max_tiles(self) -> int:
+        return max(self.lengths, default=0)
+
+
+def _validate_bags(bags: list, coords: list | None, n_feats: int | None, need_coords: bool) -> list[int]:
+    """Host checks of a ragged batch (no device access) -> the tile counts."""
+    if coords is not None:
+        if len(coords) != len(bags):
+            raise ValueError(f"{len(coords)} coords for {len(bags)} bags")
+    if need_coords and coords is None and bags:
+        raise ValueError("use_alibi=True needs coords")
+    lengths = []
+    for i, b in enumerate(bags):
+        if not isinstance(b, torch.Tensor) or b.dim() != 2:
+            raise ValueError(f"bag {i} must be a [tiles, features] tensor, got {tuple(b.shape) if isinstance(b, torch.Tensor) else type(b)}")
+        if b.shape[0] < 1:
+            raise ValueError(f"bag {i} is empty (a bag needs at least one tile)")
+        if n_feats is not None and b.shape[1] != n_feats:
+            raise ValueError(f"bag {i} has {b.shape[1]} features, expected {n_feats}")
+        if b.shape[1] != bags[0].shape[1]:
+            raise ValueError(f"bag {i} has {b.shape[1]} features, bag 0 has {bags[0].shape[1]}")
+        if coords is not None and (coords[i] is None or tuple(coords[i].shape) != (b.shape[0], 2)):
+            raise ValueError(f"coords of bag {i} must be [{b.shape[0]}, 2], got {None if coords[i] is None else tuple(coords[i].shape)}")
+        lengths.append(int(b.shape[0]))
+    return lengths
+
+
+def pack_bags(bags, coords=None, *, n_feats: int | None = None, need_coords: bool = False, device=None) -> RaggedBags:
+    """bags: sequence of [T_i, F] tensors (coords: matching [T_i, 2] tensors or None) -> RaggedBags.  Validated on the host, before anything reaches the
+    device: every T_i >= 1, one F (= n_feats when given), coords present (need_coords: ALiBi) and shaped like their bags.  The offsets are built from the
+    host lengths and uploaded once."""
+    bags = list(bags)
+    if coords is not None:
+        coords = list(coords)
+    lengths = _validate_bags(bags, coords, n_feats, need_coords)
+    dev = torch.device(device) if device is not None else (bags[0].device if bags else torch.device("cuda"))
+    if not bags:
+        F_ = n_feats or 0
+        return RaggedBags(torch.empty(0, F_, device=dev), None, torch.zeros(1, dtype=torch.int32, device=dev), ())
+    dts = {b.dtype for b in bags}
+    dt = dts.pop() if len(dts) == 1 else torch.float32
+    if dt not in ops._DT:
+        dt = torch.float32
+    feats = torch.cat([b.to(dev, dt) for b in bags], dim=0).contiguous()
+    cc = torch.cat([c.to(dev, torch.float32) for c in coords], dim=0).contiguous() if coords is not None else None
+    offs = [0]
+    for n in lengths:
+        offs.append(offs[-1] + n)
+    if offs[-1] >= 2 ** 31 - len(lengths):
+        raise ValueError(f"{offs[-1]} tiles do not fit the 32-bit row index")
+    offsets = torch.tensor(offs, dtype=torch.int32).to(dev)
+    return RaggedBags(feats, cc, offsets, tuple(lengths))
+
+
+def max_shared_tiles(pk: PackedVit) -> int:
+    """Longest bag that shares a ragged call with others and keeps its own call's bits (amds_mil_vit_ragged_max_shared_tiles): a longer bag runs alone."""
+    cfg, _ = pk.c_structs()
+    n = int(_lib.lib().amds_mil_vit_ragged_max_shared_tiles(C.byref(cfg)))
+    if n < 0:
+        _lib.check(-1, "mil_vit_ragged_max_shared_tiles")
+    return n
+
+
+def group_bags(lengths, bags_per_call: int, max_rows_per_call: int, max_shared: int = MAX_SOLO_TILES) -> list[tuple[int, int]]:
+    """Consecutive bags -> [start, end) groups for the ragged forward: at most `bags_per_call` bags and `max_rows_per_call` token rows (tiles + one class
+    token per bag) per group; a bag longer than `max_shared` tiles (or than MAX_SOLO_TILES) is a group of its own, as is a bag whose rows alone exceed
+    the row limit.  Order is kept; host-only."""
+    if bags_per_call < 1 or max_rows_per_call < 1:
+        raise ValueError("bags_per_call and max_rows_per_call must be >= 1")
+    limit = min(int(max_shared), MAX_SOLO_TILES)
+    groups: list[tuple[int, int]] = []
+    start, rows = 0, 0
+    n = len(lengths)
+    for i, t in enumerate(lengths):
+        t = int(t)
+        solo = t > limit
+        if i > start and (solo or i - start >= bags_per_call or rows + t + 1 > max_rows_per_call):
+            groups.append((start, i))
+            start, rows = i, 0
+        rows += t + 1
+        if solo:
+            groups.append((i, i + 1))
+            start, rows = i + 1, 0
+    if start < n:
+        groups.append((start, n))
+    return groups
+
+
+def forward_infer_ragged(pk: PackedVit, rb: RaggedBags) -> torch.Tensor:
+    """RaggedBags -> logits [n_bags, C]: ONE library call (amds_mil_vit_forward_ragged, csrc/mil_vit_ragged.hip), scratch kept per device like
+    `forward_infer`.  Row i equals `forward_infer` on bag i alone when the bag has at most `max_shared_tiles(pk)` tiles or is the only one."""
+    d = pk.dims
+    dev = rb.feats.device
+    if rb.n_bags == 0:
+        return torch.empty(0, d.C, dtype=torch.float32, device=dev)
+    ops._dev(rb.feats)
+    if rb.feats.shape[1] != d.F:
+        raise ValueError(f"bags must have {d.F} features, got {rb.feats.shape[1]}")
+    if d.alibi and rb.coords is None:
+        raise ValueError("use_alibi=True needs coords")
+    cfg, wc = pk.c_structs()
+    lib = _lib.lib()
+    n, total, mx = rb.n_bags, rb.total_tiles, rb.max_tiles
+    need = lib.amds_mil_vit_ragged_workspace_bytes(C.byref(cfg), n, total, mx)
+    if need == 0:
+        _lib.check(-1, "mil_vit_ragged_workspace_bytes")
+    ws = ops.scratch("mil_vit_ragged", dev, need)
+    logits = torch.empty(n, d.C, dtype=torch.float32, device=dev)
+    cc = rb.coords if d.alibi else None
+    _lib.check(lib.amds_mil_vit_forward_ragged(C.byref(cfg), C.byref(wc), rb.feats.data_ptr(), ops._DT[rb.feats.dtype],
+                                               cc.data_ptr() if cc is not None else None, rb.offsets.data_ptr(), logits.data_ptr(), n, total, mx,
+                                               ws.data_ptr(), ws.numel(), ops._stream()), "mil_vit_forward_ragged")
+    return logits
+
+
+def forward_ragged(pk: PackedVit, bags, coords=None, *, device=None, bags_per_call: int | None = None, max_rows_per_call: int = 1 << 62) -> torch.Tensor:
+    """A list of bags [T_i, F] (coords [T_i, 2]) -> logits [N, C], row i bit-identical to `forward_infer` on bag i alone: validated and grouped on the
+    host (`group_bags`: a bag too long to share a call runs alone), one ragged library call per group."""
+    d = pk.dims
+    bags = list(bags)
+    cl = list(coords) if coords is not None else None
+    lengths = _validate_bags(bags, cl, d.F, d.alibi)
+    if not bags:
+        return forward_infer_ragged(pk, pack_bags(bags, cl, n_feats=d.F, device=device))
+    outs = []
+    for a, e in group_bags(lengths, bags_per_call or len(bags), max_rows_per_call, max_shared_tiles(pk)):
+        rb = pack_bags(bags[a:e], None if cl is None else cl[a:e], n_feats=d.F, need_coords=d.alibi, device=device)
+        outs.append(forward_infer_ragged(pk, rb))
+    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
+
 # ---- training forward / backward (bf16 operands, saved statistics) ----------------------------------------------------------------
 def _gelu_drop_fwd(z, out_dtype, p, seed, sid):
     if p <= 0.0:

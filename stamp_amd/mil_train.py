@@ -301,9 +301,72 @@ class HipMilVitTrainer:
             self._eval_pk_step = self.step_count
         return mil_core.forward_infer(self._eval_pk, bags, coords, None)
 
+    def _eval_pack(self) -> PackedVit:
+        if getattr(self, "_eval_pk_step", -1) != self.step_count or getattr(self, "_eval_pk", None) is None:
+            self._eval_pk = PackedVit(self.dims, self.p, torch.float16, train=False)
+            self._eval_pk_step = self.step_count
+        return self._eval_pk
+
+    @torch.no_grad()
+    def predict_ragged(self, bags, coords=None) -> torch.Tensor:
+        """Bags of different lengths (a list of [T_i, F] tensors, coords a list of [T_i, 2] or None) in ONE library call -> logits [N, C]; row i equals
+        `predict(bags[i][None], coords[i][None])` bit for bit (mil_core.forward_ragged: a bag longer than `max_shared_tiles()` runs alone)."""
+        bags = list(bags)
+        if not bags:
+            return torch.empty(0, self.dims.C, dtype=torch.float32, device=self.dev)
+        return mil_core.forward_ragged(self._eval_pack(), bags, coords, device=self.dev)
+
+    def max_shared_tiles(self) -> int:
+        return mil_core.max_shared_tiles(self._eval_pack())
+
+
+def _valid_loss(lg, targets, dev, class_weights, loss_fn):
+    if loss_fn is None:
+        return F.cross_entropy(lg, targets.to(dev, torch.float32), weight=None if class_weights is None else class_weights.to(dev, torch.float32))
+    return loss_fn(lg, targets.to(dev))
+
+
+def _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, per_call: int) -> tuple[float, int]:
+    """The validation sum of `fit` with consecutive one-bag batches run `per_call` at a time through `predict_ragged` (mil_core.group_bags decides the
+    groups): each batch's loss comes from its own logits row(s) exactly as in the one-bag loop, the group's losses reach the host in one read, and the
+    sum runs in batch order.  Batches of several bags keep the one-call `predict` of the default loop."""
+    vtot, vcnt = 0.0, 0
+    pend: list = []
+
+    def flush():
+        nonlocal vtot, vcnt
+        if not pend:
+            return
+        one = [i for i, (b, *_rest) in enumerate(pend) if b.shape[0] == 1]
+        rows: dict = {}
+        if one:
+            limit = trainer.max_shared_tiles() if hasattr(trainer, "max_shared_tiles") else mil_core.MAX_SOLO_TILES
+            lens = [pend[i][0].shape[1] for i in one]
+            for a, e in mil_core.group_bags(lens, per_call, 1 << 62, limit):
+                idx = one[a:e]
+                cs = None if pend[idx[0]][1] is None else [pend[i][1][0].to(dev) for i in idx]
+                lg = trainer.predict_ragged([pend[i][0][0].to(dev) for i in idx], cs)
+                for k, i in enumerate(idx):
+                    rows[i] = lg[k:k + 1]
+        losses = []
+        for i, (bags, coords, targets) in enumerate(pend):
+            lg = rows[i] if i in rows else trainer.predict(bags.to(dev), None if coords is None else coords.to(dev))
+            losses.append(_valid_loss(lg, targets, dev, class_weights, loss_fn).reshape(()))
+        for (bags, _c, _t), v in zip(pend, torch.stack(losses).tolist()):
+            vtot += float(v) * bags.shape[0]
+            vcnt += bags.shape[0]
+        pend.clear()
+
+    for bags, coords, _sizes, targets in valid_batches():
+        pend.append((bags, coords, targets))
+        if sum(b.shape[0] for b, *_ in pend) >= per_call:
+            flush()
+    flush()
+    return vtot, vcnt
+
 
 def fit(trainer: HipMilVitTrainer, train_batches, valid_batches, *, max_epochs: int, patience: int = 16, class_weights=None,
-        loss_fn=None, log=None) -> dict:
+        loss_fn=None, log=None, valid_bags_per_call: int = 1) -> dict:
     """The epoch loop of the reference's `train_model_` (src/stamp/modeling/train.py:504-564) around `HipMilVitTrainer.step`.
 
     train_batches / valid_batches: callables returning an iterable of (bags, coords, bag_sizes, targets) per epoch -- the
@@ -312,7 +375,11 @@ def fit(trainer: HipMilVitTrainer, train_batches, valid_batches, *, max_epochs: 
     weighted by batch size) is computed; training stops when it has not improved for `patience` epochs (EarlyStopping, mode min);
     the best epoch's weights are restored and copied into `trainer.model` (the reference copies the best checkpoint and reloads
     it).  `num_sanity_val_steps=0` like the reference.  Returns the history; `skipped_steps` holds the optimiser steps per epoch the dynamic
-    loss scale skipped (fp16 gradients not finite), and `log` is warned about each epoch that skipped any."""
+    loss scale skipped (fp16 gradients not finite), and `log` is warned about each epoch that skipped any.
+    valid_bags_per_call > 1: consecutive one-bag validation batches run that many at a time through ONE ragged call (`predict_ragged`), with one host
+    read of their losses per call instead of one per bag; the losses, and so the history and the restored epoch, are those of the default loop."""
+    if valid_bags_per_call < 1:
+        raise ValueError("valid_bags_per_call must be >= 1")
     dev = trainer.dev
     best = {"loss": float("inf"), "epoch": -1, "P": None}
     hist = {"train_loss": [], "validation_loss": [], "skipped_steps": [], "best_epoch": -1, "stopped_epoch": None}
@@ -334,7 +401,9 @@ def fit(trainer: HipMilVitTrainer, train_batches, valid_batches, *, max_epochs: 
                 f"loss scale now {trainer.current_loss_scale:g}")
         skipped = now
         vtot, vcnt = 0.0, 0
-        for bags, coords, _sizes, targets in valid_batches():
+        if valid_bags_per_call > 1:
+            vtot, vcnt = _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, valid_bags_per_call)
+        for bags, coords, _sizes, targets in (valid_batches() if valid_bags_per_call == 1 else ()):
             lg = trainer.predict(bags.to(dev), None if coords is None else coords.to(dev))
             if loss_fn is None:
                 vl = F.cross_entropy(lg, targets.to(dev, torch.float32), weight=None if class_weights is None else class_weights.to(dev, torch.float32))
