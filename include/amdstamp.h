@@ -868,6 +868,33 @@ int amds_mil_vit_train_backward(const amds_mil_vit_cfg* cfg_host, const amds_mil
                                 const amds_mil_vit_dropout* drop_host, int n_bags, int n_tiles, const void* saved, size_t saved_bytes,
                                 const amds_mil_vit_grads* grads_host, float* dbags, int split_k, void* ws, size_t ws_bytes, void* stream);
 
+/* Grad-CAM scores of every tile for every class from ONE call (reference src/stamp/heatmaps/__init__.py: `_gradcam_per_category` :36-56 up to and including
+ * line 54, `_gradcam_single` :115-139 line 137; the reference builds the [classes][tiles][n_feats] Jacobian with torch.func.jacrev and reduces it):
+ *   cam_raw[c][t] = | (1 / n_feats) * sum_f feats[t][f] * d logit_c / d feats[t][f] |,     fp32 [classes][n_bags * n_tiles], before any softmax.
+ * `saved`: the arena of an amds_mil_vit_train_forward call made with dropout off (p_proj = p_att = p_ff = 0, AMDS_ERR_INVALID otherwise) and `drop_host` the
+ * struct of that forward (cls_tail decides the arena's layout).  The class loop runs inside: for each class the backward's launch sequence with
+ * dlogits = scale * e_c and no parameter gradients (no weight-gradient GEMMs, no column sums), down to the gradient dxp at the projection's output; there one
+ * row-dot kernel forms dz = gelu'(z) * dxp in registers and reduces sum_d dz[t][d] * (z[t][d] - proj_b[d]) against the saved 16-bit pre-activation z -- which
+ * equals sum_f feats[t][f] * (dz W_proj)[t][f] -- multiplies by 1 / (n_feats * scale) and stores |.|.  Neither dbags nor anything else of size
+ * [tiles][n_feats] is written.  `scale`: a power of two; 1 for bf16 operands, 1024 for fp16 (the 16-bit gradient tensors carry it, as in training); overflow
+ * shows as non-finite values in cam_raw (amds_check_finite).  All classes share `ws` (amds_mil_vit_gradcam_workspace_bytes, 256-byte aligned; 0 on a bad
+ * configuration).  Deterministic; launches only, on `stream`. */
+size_t amds_mil_vit_gradcam_workspace_bytes(const amds_mil_vit_cfg* cfg_host, int n_bags, int n_tiles);
+int amds_mil_vit_gradcam(const amds_mil_vit_cfg* cfg_host, const amds_mil_vit_weights* w_host, const amds_mil_vit_dropout* drop_host, int n_bags, int n_tiles,
+                         const void* saved, size_t saved_bytes, float scale, float* cam_raw, void* ws, size_t ws_bytes, void* stream);
+
+/* out[t][c] = softmax over t of in[c][t]: fp32 [classes][n] -> fp32 [n][classes] (reference src/stamp/heatmaps/__init__.py:55-56: `torch.softmax(cam, dim=-1)`
+ * then `permute(-1, -2)`).  One workgroup per class; maximum and sum over the n tiles by fixed-order reductions (no float atomics): deterministic.
+ * 1 <= classes <= 65535, 1 <= n < 2^31. */
+int amds_softmax_over_tiles(const float* in, float* out, int classes, long n, void* stream);
+
+/* `_vals_to_im` (reference src/stamp/heatmaps/__init__.py:142-156): vals fp32 [n][k], xy int64 [n][2] grid coordinates (column 0 = x, column 1 = y),
+ * out fp32 [h][w][k], zero-filled by the call, then out[y][x][:] = vals[t][:].  Where several tiles name one cell the HIGHEST tile index wins (what the
+ * reference's indexed assignment does on the CPU): a first pass records the winning index per cell with an integer maximum, a second copies -- deterministic.
+ * cell_ws: int32 [h * w + 1] scratch.  A coordinate outside [0, w) x [0, h) is never dereferenced; the call counts them, SYNCHRONISES `stream` (one 4-byte
+ * read) and returns AMDS_ERR_INVALID if there was one (`out` is then unspecified). */
+int amds_scatter_grid(const float* vals, const int64_t* xy, float* out, int* cell_ws, long n, int k, int h, int w, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * barspoon head, deploy / validation forward as one call (reference src/stamp/modeling/models/barspoon.py:27-205
  * `EncDecTransformer` in eval mode: projector, sinusoidal position encoding, pre-norm transformer encoder over the tiles, one class

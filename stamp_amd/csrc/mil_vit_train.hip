@@ -87,9 +87,12 @@ struct WsPlan {
     size_t cs_bytes, lnb_bytes, sums_bytes;
 };
 
-void plan_ws(const Dims& d, int split_k, WsPlan* p) {
+// `lean`: the plan of a backward that stops at the projection's output with no parameter gradients (amds_mil_vit_gradcam): the buffers only the weight
+// gradients, the column sums and the projection's own backward touch take no room.
+void plan_ws(const Dims& d, int split_k, WsPlan* p, bool lean = false) {
     size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    auto take_always = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    auto take = [&](size_t bytes) { return take_always(lean ? 0 : bytes); };
     const size_t M = d.M, Mt = d.Mt;
     const long unit = 64L * split_k;
     p->Mp = upl(d.M, unit);
@@ -97,13 +100,13 @@ void plan_ws(const Dims& d, int split_k, WsPlan* p) {
     const size_t Mpp = (size_t)(p->Mp > p->Mtp ? p->Mp : p->Mtp);
     const int wg = std::max(std::max(3 * d.Da, d.FFp), d.Dp);                       // widest gradient matrix that gets transposed
     const int wa = std::max(std::max(std::max(d.FFp, d.Dp), d.Da), d.Fp);           // widest activation matrix
-    p->dx = take(M * d.Dp * 4);
-    p->dh = take(M * d.Dp * 4);
-    p->g16 = take(M * d.Dp * 2);
-    p->du = take(M * d.FFp * 2);
-    p->dz = take(M * d.FFp * 2);
-    p->datt = take(M * d.Da * 2);
-    p->dqkv = take(M * 3 * d.Da * 2);
+    p->dx = take_always(M * d.Dp * 4);
+    p->dh = take_always(M * d.Dp * 4);
+    p->g16 = take_always(M * d.Dp * 2);
+    p->du = take_always(M * d.FFp * 2);
+    p->dz = take_always(M * d.FFp * 2);
+    p->datt = take_always(M * d.Da * 2);
+    p->dqkv = take_always(M * 3 * d.Da * 2);
     p->tg = take((size_t)wg * Mpp * 2);
     p->ta = take((size_t)wa * Mpp * 2);
     const size_t nk = std::max(std::max((size_t)3 * d.Da * d.Dp, (size_t)d.FFp * d.Dp), std::max((size_t)d.Dp * d.Da, (size_t)d.Dp * d.Fp));
@@ -117,7 +120,7 @@ void plan_ws(const Dims& d, int split_k, WsPlan* p) {
     p->cs_bytes = std::max<size_t>(cs, 4);
     p->cs = take(p->cs_bytes);
     p->lnb_bytes = std::max<size_t>(amds_layernorm_bwd_workspace_bytes((int)d.M, d.D), 4);
-    p->lnb = take(p->lnb_bytes);
+    p->lnb = take_always(p->lnb_bytes);
     // the column sums the backward postpones to ONE launch at its end (amds_colsum_multi): per-64-row partials of every LayerNorm's parameter gradients
     // and the chunk partials of every bias gradient, each in its own region
     {
@@ -127,11 +130,11 @@ void plan_ws(const Dims& d, int split_k, WsPlan* p) {
         p->sums_bytes = b + 4096;
         p->sums = take(p->sums_bytes);
     }
-    p->dqs = take((size_t)d.Bb * d.Ha * d.S * 4);
-    p->dbsp = take((size_t)d.Bb * d.Ha * d.S * 4);
+    p->dqs = take_always((size_t)d.Bb * d.Ha * d.S * 4);
+    p->dbsp = take_always((size_t)d.Bb * d.Ha * d.S * 4);
     p->dbst = take(M * d.Ha * 4);
-    p->gsc = take((size_t)2 * d.D * 4);                 // LayerNorm parameter gradients nobody asked for (need_params = false)
-    p->dcls = take((size_t)d.Bb * d.D * 4);
+    p->gsc = take_always((size_t)2 * d.D * 4);                 // LayerNorm parameter gradients nobody asked for (need_params = false)
+    p->dcls = take_always((size_t)d.Bb * d.D * 4);
     p->dlt = take((size_t)d.Bb * d.C * 4);
     p->dxp = take(Mt * d.Dp * 4);
     p->dzp = take(Mt * d.Dp * 2);
@@ -202,6 +205,58 @@ int gelu_drop_fwd(const void* z, void* u, long n, int zdt, int udt, float p, uin
 }
 int gelu_drop_bwd(const void* z, const void* du, void* dz, long n, int zdt, int dudt, int dzdt, float p, uint64_t seed, uint32_t sid, void* st) {
     return p > 0.f ? amds_gelu_dropout_bwd(z, du, dz, n, zdt, dudt, dzdt, p, seed, sid, st) : amds_gelu_bwd(z, du, dz, n, zdt, dudt, dzdt, st);
+}
+
+// ---- Grad-CAM tail (amds_mil_vit_gradcam) ------------------------------------------------------------------------------------------------------------------
+// reference src/stamp/heatmaps/__init__.py:54 / :137: cam[t] = |mean_f feats[t][f] * d logit / d feats[t][f]|.  With z = feats W_proj^T + b the projection's
+// pre-activation and dz = gelu'(z) * dxp its gradient, d logit / d feats[t][:] = dz[t][:] W_proj, so the mean is (1 / F) sum_d dz[t][d] (z[t][d] - b[d]): a dot
+// product per tile row over quantities the backward already holds -- no dbags GEMM, no [tiles][F] gradient.
+struct CamTail {
+    float* out;         // [n_bags * n_tiles] of one class
+    float mul;          // 1 / (n_feats * scale)
+};
+
+// dlogits of the class loop: basis[c][b][j] = scale * (j == c)
+__global__ void cam_basis_kernel(float* __restrict__ basis, int Bb, int C, float scale) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < C * Bb * C) basis[i] = (i % C == i / (Bb * C)) ? scale : 0.f;
+}
+
+// One wave per tile row, 8 columns per lane and step (16-byte loads: 8 x 16-bit z, 2 x 4 fp32 dx / bias), fp32 throughout, a fixed-order butterfly over the 64 lanes:
+// deterministic.  dx holds the class-token rows too ([Bb][Tn + 1][Dp]); tile row r of bag b is its row r + b + 1.  Columns D..Dp are skipped (z - b is zero there).
+template <typename T>
+__global__ void __launch_bounds__(256) cam_rowdot_kernel(const float* __restrict__ dx, const T* __restrict__ zp, const float* __restrict__ bias, float* __restrict__ out,
+                                                         long Mt, int Tn, int D, int Dp, float mul) {
+    typedef typename Act<T>::vec8 vec8;
+    const int lane = threadIdx.x & 63;
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= Mt) return;                                         // (whole waves leave together; no barrier below)
+    const float* dxr = dx + (r + r / Tn + 1) * Dp;
+    const T* zr = zp + r * Dp;
+    float acc = 0.f;
+    for (int c0 = lane * 8; c0 < D; c0 += 512) {
+        const vec8 zv = *reinterpret_cast<const vec8*>(zr + c0);
+        const f32x4 g0 = *reinterpret_cast<const f32x4*>(dxr + c0), g1 = *reinterpret_cast<const f32x4*>(dxr + c0 + 4);
+        const f32x4 b0 = *reinterpret_cast<const f32x4*>(bias + c0), b1 = *reinterpret_cast<const f32x4*>(bias + c0 + 4);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float x = (float)zv[e];
+            const float g = e < 4 ? g0[e & 3] : g1[e & 3], b = e < 4 ? b0[e & 3] : b1[e & 3];
+            const float dg = 0.5f * (1.0f + erff(x * 0.70710678118654752440f)) + x * 0.39894228040143267794f * __expf(-0.5f * x * x);       // gelu'(z), as amds_gelu_bwd
+            acc += (c0 + e < D) ? (g * dg) * (x - b) : 0.f;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if (lane == 0) out[r] = fabsf(acc * mul);
+}
+
+int cam_rowdot(const float* dx, const void* zp, const float* bias, float* out, const Dims& d, float mul, hipStream_t st) {
+    const unsigned grid = (unsigned)((d.Mt + 3) / 4);
+    if (d.dt == AMDS_BF16) hipLaunchKernelGGL((cam_rowdot_kernel<bf16>), dim3(grid), dim3(256), 0, st, dx, (const bf16*)zp, bias, out, d.Mt, d.Tn, d.D, d.Dp, mul);
+    else hipLaunchKernelGGL((cam_rowdot_kernel<f16>), dim3(grid), dim3(256), 0, st, dx, (const f16*)zp, bias, out, d.Mt, d.Tn, d.D, d.Dp, mul);
+    AMDS_LAUNCH_CHECK("cam_rowdot_kernel");
+    return AMDS_OK;
 }
 
 #define RC(call)                          \
@@ -377,11 +432,14 @@ extern "C" int amds_mil_vit_train_forward(const amds_mil_vit_cfg* cfg_host, cons
     return amds_linear_f32(clsn, w.head_w, w.head_b, logits, Bb, d.C, D, 0, stream);
 }
 
-extern "C" int amds_mil_vit_train_backward(const amds_mil_vit_cfg* cfg_host, const amds_mil_vit_weights* w_host, const float* dlogits,
-                                           const amds_mil_vit_dropout* drop_host, int n_bags, int n_tiles, const void* saved, size_t saved_bytes,
-                                           const amds_mil_vit_grads* grads_host, float* dbags, int split_k, void* ws, size_t ws_bytes, void* stream) {
+// The backward's launch sequence.  `cam` NULL: amds_mil_vit_train_backward as declared.  `cam` set (amds_mil_vit_gradcam; no parameter gradients, no dbags, lean
+// workspace plan): the same launches down to dx of the first block, then ONE row-dot launch in place of the projection's GELU backward and its dbags GEMM.
+static int mil_vit_backward_body(const amds_mil_vit_cfg* cfg_host, const amds_mil_vit_weights* w_host, const float* dlogits, const amds_mil_vit_dropout* drop_host,
+                                 int n_bags, int n_tiles, const void* saved, size_t saved_bytes, const amds_mil_vit_grads* grads_host, float* dbags, int split_k,
+                                 void* ws, size_t ws_bytes, void* stream, const CamTail* cam) {
     AMDS_REQUIRE(cfg_host && w_host && dlogits && saved && drop_host && ws, "amds_mil_vit_train_backward: null pointer");
-    AMDS_REQUIRE(grads_host || dbags, "amds_mil_vit_train_backward: nothing to compute (no gradient buffers, no dbags)");
+    AMDS_REQUIRE(grads_host || dbags || cam, "amds_mil_vit_train_backward: nothing to compute (no gradient buffers, no dbags)");
+    AMDS_REQUIRE(!cam || (!grads_host && !dbags), "amds_mil_vit_gradcam: takes no gradient buffers");
     AMDS_REQUIRE(split_k > 0 && split_k <= 1024, "amds_mil_vit_train_backward: bad split_k=%d", split_k);
     Dims d;
     RC(make_dims(cfg_host, n_bags, n_tiles, &d));
@@ -389,7 +447,7 @@ extern "C" int amds_mil_vit_train_backward(const amds_mil_vit_cfg* cfg_host, con
     SavedPlan sp;
     plan_saved(d, &sp);
     WsPlan wp;
-    plan_ws(d, split_k, &wp);
+    plan_ws(d, split_k, &wp, cam != nullptr);
     if (saved_bytes < sp.total || ws_bytes < wp.total) {
         set_error("amds_mil_vit_train_backward: arena %zu / workspace %zu < required %zu / %zu bytes", saved_bytes, ws_bytes, sp.total, wp.total);
         return AMDS_ERR_WORKSPACE;
@@ -679,6 +737,7 @@ extern "C" int amds_mil_vit_train_backward(const amds_mil_vit_cfg* cfg_host, con
     }
     // ---- class token, project_features ------------------------------------------------------------------------------------------------------
     if (need_params) RC(colsum(dx, (long)S * Dp, G->class_token, Bb, Dp, AMDS_F32, true));                                     // class-token rows (dx is final here)
+    if (cam) return cam_rowdot(dx, sv + sp.zp, w.proj_b, cam->out, d, cam->mul, st);
     float* dxp = reinterpret_cast<float*>(wk + wp.dxp);
     void* dzp = wk + wp.dzp;
     hipLaunchKernelGGL(drop_cls_rows_kernel, dim3((unsigned)Mt), dim3(128), 0, st, dx, dxp, Dp, d.Tn);
@@ -698,5 +757,54 @@ extern "C" int amds_mil_vit_train_backward(const amds_mil_vit_cfg* cfg_host, con
     if (dbags) RC(gemm(dzp, Dp, w.proj_wt, Dp, Mt, Fp, Dp, AMDS_EPI_BIAS_F32, dbags, Fp, nullptr, stream));                 // [Mt][Fp] fp32 (padded columns = 0)
     if (n_def > 0) RC(amds_sum_partials_multi(def_part, def_out, def_count, n_def, split_k, stream));
     RC(flush_sums());
+    return AMDS_OK;
+}
+
+extern "C" int amds_mil_vit_train_backward(const amds_mil_vit_cfg* cfg_host, const amds_mil_vit_weights* w_host, const float* dlogits,
+                                           const amds_mil_vit_dropout* drop_host, int n_bags, int n_tiles, const void* saved, size_t saved_bytes,
+                                           const amds_mil_vit_grads* grads_host, float* dbags, int split_k, void* ws, size_t ws_bytes, void* stream) {
+    return mil_vit_backward_body(cfg_host, w_host, dlogits, drop_host, n_bags, n_tiles, saved, saved_bytes, grads_host, dbags, split_k, ws, ws_bytes, stream, nullptr);
+}
+
+// ---- amds_mil_vit_gradcam (include/amdstamp.h): |mean_f feats * d logit_c / d feats| per tile and class, no [tiles][n_feats] tensor ----------------------------
+namespace {
+constexpr int CAM_SPLIT_K = 1;          // (the lean plan holds no split-K buffers; the value only has to be valid)
+size_t cam_basis_bytes(const Dims& d) { return al((size_t)d.C * d.Bb * d.C * 4); }
+}  // namespace
+
+extern "C" size_t amds_mil_vit_gradcam_workspace_bytes(const amds_mil_vit_cfg* cfg_host, int n_bags, int n_tiles) {
+    Dims d;
+    if (make_dims(cfg_host, n_bags, n_tiles, &d) != AMDS_OK) return 0;
+    WsPlan p;
+    plan_ws(d, CAM_SPLIT_K, &p, true);
+    return p.total + cam_basis_bytes(d);
+}
+
+extern "C" int amds_mil_vit_gradcam(const amds_mil_vit_cfg* cfg_host, const amds_mil_vit_weights* w_host, const amds_mil_vit_dropout* drop_host, int n_bags,
+                                    int n_tiles, const void* saved, size_t saved_bytes, float scale, float* cam_raw, void* ws, size_t ws_bytes, void* stream) {
+    AMDS_REQUIRE(cfg_host && w_host && drop_host && saved && cam_raw && ws, "amds_mil_vit_gradcam: null pointer");
+    AMDS_REQUIRE(drop_host->p_proj == 0.f && drop_host->p_att == 0.f && drop_host->p_ff == 0.f,
+                 "amds_mil_vit_gradcam: the arena must come from a forward with dropout off (p = 0)");
+    int ex = 0;
+    AMDS_REQUIRE(scale > 0.f && scale <= 16777216.f && frexpf(scale, &ex) == 0.5f, "amds_mil_vit_gradcam: scale=%g is not a power of two", (double)scale);
+    Dims d;
+    RC(make_dims(cfg_host, n_bags, n_tiles, &d));
+    WsPlan wp;
+    plan_ws(d, CAM_SPLIT_K, &wp, true);
+    if (ws_bytes < wp.total + cam_basis_bytes(d)) {
+        set_error("amds_mil_vit_gradcam: workspace %zu < required %zu bytes", ws_bytes, wp.total + cam_basis_bytes(d));
+        return AMDS_ERR_WORKSPACE;
+    }
+    AMDS_REQUIRE(((uintptr_t)ws & 255) == 0, "amds_mil_vit_gradcam: workspace must be 256-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    float* basis = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + wp.total);       // [classes][n_bags][classes]: dlogits = scale * e_c for every bag
+    const int nb = d.C * d.Bb * d.C;
+    hipLaunchKernelGGL(cam_basis_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, basis, d.Bb, d.C, scale);
+    AMDS_LAUNCH_CHECK("cam_basis_kernel");
+    for (int c = 0; c < d.C; ++c) {
+        const CamTail tail{cam_raw + (size_t)c * d.Mt, 1.0f / ((float)d.F * scale)};
+        RC(mil_vit_backward_body(cfg_host, w_host, basis + (size_t)c * d.Bb * d.C, drop_host, n_bags, n_tiles, saved, saved_bytes, nullptr, nullptr, CAM_SPLIT_K, ws,
+                                 wp.total, stream, &tail));
+    }
     return AMDS_OK;
 }

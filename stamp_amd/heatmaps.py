@@ -1,0 +1,259 @@
+"""Whole-slide heat-map scores on the HIP path: the arithmetic of the reference's `stamp heatmaps` for ONE slide, everything on the device.
+
+Reference: src/stamp/heatmaps/__init__.py -- `_gradcam_per_category` :36-56, `_gradcam_single` :115-139, `_vals_to_im` :142-156, the grid coordinates
+:376 with `get_stride` (src/stamp/modeling/data.py:1150-1161), the slide score :392-403, the one-tile-bag scores :417-427, the per-category support /
+attention / score maps :464-498 and the regression branch's normalisations :593-597.  Rendering (matplotlib, colour maps, overlays, PNG files, openslide
+thumbnails, ranked-tile export) is not here: every function returns tensors the reference's plotting code takes as they are.
+
+Two routes to the Grad-CAM scores:
+  * fused (`stamp_amd.mil.VisionTransformer`, with or without ALiBi): one eval-mode training forward that keeps its activations
+    (`mil_core.forward_train`), then ONE library call for all classes (`mil_core.gradcam` -> amds_mil_vit_gradcam) that never forms the
+    [classes, tiles, features] Jacobian, then amds_softmax_over_tiles.  Operand type as the module's autograd path: bf16 at
+    float32_matmul_precision "medium", else fp16 with the 2^10 scale on the basis vectors; non-finite fp16 logits or scores -> the same slide again on
+    bf16 operands and `model.fp16_overflow_events += 1`.
+  * jacrev (any module with the reference's ``forward(bags, coords=, mask=)``: TransMIL, a torch model; can be forced for the `vit` head): the
+    reference's own three lines on the device.
+The module is put in eval mode for the duration of a call; ALiBi running means are not updated; no parameter receives a `.grad` and `feats` needs no
+`requires_grad`.  There is no CPU fallback: CPU tensors raise.
+"""
+from __future__ import annotations
+
+import contextlib
+from dataclasses import dataclass
+
+import torch
+
+from . import _lib, mil_core, ops
+from .mil import VisionTransformer, _all_finite
+
+_FP16_SCALE = 1024.0            # the power of two the fp16 basis vectors carry (as `_MilVitFunction`'s loss scale)
+MAX_BAGS_PER_CALL = 32768       # one-tile bags per inference call of `tile_scores` (the attention kernels' grids take at most 65535 bags)
+
+
+@contextlib.contextmanager
+def _eval_mode(model: torch.nn.Module):
+    was = model.training
+    model.eval()
+    try:
+        yield
+    finally:
+        model.train(was)
+
+
+def _check_inputs(feats: torch.Tensor, coords: torch.Tensor | None) -> None:
+    if not feats.is_cuda or (coords is not None and not coords.is_cuda):
+        raise RuntimeError("HIP MIL head needs bags on the GPU (no CPU fallback)")
+    if feats.dim() != 2:
+        raise ValueError(f"feats must be [tiles, features], got {tuple(feats.shape)}")
+    if coords is not None and tuple(coords.shape) != (feats.shape[0], 2):
+        raise ValueError(f"coords must be [{feats.shape[0]}, 2], got {tuple(coords.shape)}")
+
+
+def _pick(model, method: str) -> str:
+    if method not in ("auto", "fused", "jacrev"):
+        raise ValueError(f"method must be 'auto', 'fused' or 'jacrev', got {method!r}")
+    fused_ok = isinstance(model, VisionTransformer)
+    if method == "fused" and not fused_ok:
+        raise ValueError(f"method='fused' needs a stamp_amd.mil.VisionTransformer, got {type(model).__name__}")
+    return ("fused" if fused_ok else "jacrev") if method == "auto" else method
+
+
+def _cam_raw_fused(model: VisionTransformer, feats: torch.Tensor, coords: torch.Tensor | None) -> torch.Tensor:
+    """-> cam_raw [C, N] (module docstring, the fused route)."""
+    dev = feats.device
+    tensors = dict(model.named_parameters())
+    tensors.update(dict(model.named_buffers()))
+    get = lambda n: tensors[n].detach().to(dev, torch.float32)  # noqa: E731
+    bags = feats.detach().unsqueeze(0)
+    cc = None if coords is None else coords.detach().unsqueeze(0)
+
+    def forward(dt):
+        pk = mil_core.PackedVit(model.dims, get, dt, True)
+        logits, saved = mil_core.forward_train(pk, bags, cc, training=False)
+        return pk, logits, saved
+
+    if torch.get_float32_matmul_precision() != "medium":
+        pk, logits, saved = forward(torch.float16)
+        if _all_finite(logits):                 # (checked before the class loop is spent on an overflowed forward)
+            cam = mil_core.gradcam(pk, saved, scale=_FP16_SCALE)
+            if _all_finite(cam):
+                return cam
+        model.fp16_overflow_events += 1         # an fp16 activation or gradient overflowed: the same slide on bf16 operands (fp32's range)
+    pk, _, saved = forward(torch.bfloat16)
+    return mil_core.gradcam(pk, saved, scale=1.0)
+
+
+def _cam_raw_jacrev(model: torch.nn.Module, feats: torch.Tensor, coords: torch.Tensor | None, squeeze_all: bool) -> torch.Tensor:
+    """The reference's lines :43-54 (`squeeze_all`: :126-137) -> cam before the softmax, [C, N] (or [N])."""
+    from torch.func import jacrev
+
+    feats = feats.detach().float()
+    cu = None if coords is None else coords.detach().unsqueeze(0)
+
+    def f(bags):
+        out = model.forward(bags.unsqueeze(0), coords=cu, mask=None)
+        return out.squeeze() if squeeze_all else out.squeeze(0)
+
+    with torch.enable_grad():
+        jac = jacrev(f)(feats)
+    return (feats * jac).mean(-1).abs()
+
+
+def _softmax_over_tiles(cam_raw: torch.Tensor) -> torch.Tensor:
+    """fp32 [C, N] -> softmax over the tiles, transposed: [N, C] (amds_softmax_over_tiles; reference :55-56)."""
+    ops._dev(cam_raw)
+    cam_raw = cam_raw.contiguous().float()
+    Cn, N = cam_raw.shape
+    out = torch.empty(N, Cn, dtype=torch.float32, device=cam_raw.device)
+    _lib.check(_lib.lib().amds_softmax_over_tiles(cam_raw.data_ptr(), out.data_ptr(), Cn, N, ops._stream()), "softmax_over_tiles")
+    return out
+
+
+def gradcam(model: torch.nn.Module, feats: torch.Tensor, coords: torch.Tensor | None = None, *, raw: bool = False, method: str = "auto") -> torch.Tensor:
+    """reference `_gradcam_per_category` (:36-56): feats [N, F] fp16 / fp32, coords [N, 2] (micrometres; required by an ALiBi head) -> [N, C] fp32, the
+    per-class Grad-CAM scores soft-maxed over the tiles; `raw=True`: the scores before that softmax (line 54), [N, C].  `method`: "auto" (fused for the
+    HIP `vit` head, else jacrev), "fused", "jacrev"."""
+    _check_inputs(feats, coords)
+    route = _pick(model, method)
+    with _eval_mode(model):
+        if route == "fused":
+            cam_raw = _cam_raw_fused(model, feats, coords)
+            return cam_raw.t().contiguous() if raw else _softmax_over_tiles(cam_raw)
+        cam_raw = _cam_raw_jacrev(model, feats, coords, squeeze_all=False)
+        if cam_raw.dim() != 2:
+            raise ValueError(f"the model must return [1, classes] logits for one bag, its Jacobian reduced to {tuple(cam_raw.shape)}")
+        return (cam_raw if raw else torch.softmax(cam_raw, dim=-1)).permute(-1, -2)
+
+
+def gradcam_single(model: torch.nn.Module, feats: torch.Tensor, coords: torch.Tensor | None = None, *, method: str = "auto") -> torch.Tensor:
+    """reference `_gradcam_single` (:115-139), regression / survival models (dim_output == 1): -> [N] fp32, |mean_f feats * d output / d feats|."""
+    _check_inputs(feats, coords)
+    route = _pick(model, method)
+    n_out = getattr(model, "dim_output", getattr(model, "n_classes", None))
+    if n_out is not None and n_out != 1:
+        raise ValueError(f"gradcam_single is for single-output models (dim_output == 1), this one has {n_out} outputs: use gradcam")
+    with _eval_mode(model):
+        if route == "fused":
+            return _cam_raw_fused(model, feats, coords)[0]
+        cam = _cam_raw_jacrev(model, feats, coords, squeeze_all=True)
+        if cam.dim() != 1:
+            raise ValueError(f"gradcam_single is for single-output models, the Jacobian reduced to {tuple(cam.shape)}")
+        return cam
+
+
+def tile_scores(model: torch.nn.Module, feats: torch.Tensor, coords: torch.Tensor | None = None, *, tiles_per_call: int | None = None) -> torch.Tensor:
+    """reference :417-427: every tile as a bag of its own under an all-False mask, softmax over the classes -> [N, C] fp32.  The module's masked inference
+    forward in chunks of `tiles_per_call` bags (default: all at once, at most MAX_BAGS_PER_CALL per call); one chunk equals
+    ``torch.softmax(model(feats.unsqueeze(-2), coords=coords.unsqueeze(-2), mask=zeros), 1)`` bit for bit."""
+    _check_inputs(feats, coords)
+    N = feats.shape[0]
+    step = MAX_BAGS_PER_CALL if tiles_per_call is None else int(tiles_per_call)
+    if step < 1:
+        raise ValueError("tiles_per_call must be >= 1")
+    outs = []
+    with _eval_mode(model), torch.no_grad():
+        for a in range(0, N, step):
+            e = min(N, a + step)
+            logits = model(feats[a:e].unsqueeze(-2), coords=None if coords is None else coords[a:e].unsqueeze(-2),
+                           mask=torch.zeros(e - a, 1, dtype=torch.bool, device=feats.device))
+            outs.append(torch.softmax(logits, dim=1))
+    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
+
+def grid_coords(coords_um: torch.Tensor, stride_um: float | None = None) -> torch.Tensor:
+    """reference :376: tile coordinates in micrometres [N, 2] -> int64 grid coordinates (the top-left tile of the grid is a multiple of the stride from
+    (0, 0)); `stride_um` None: `get_stride` (modeling/data.py:1150-1161), the smallest step between two distinct x or two distinct y values."""
+    if coords_um.dim() != 2 or coords_um.shape[1] != 2:
+        raise ValueError(f"coords must be [tiles, 2], got {tuple(coords_um.shape)}")
+    coords_um = coords_um.float()
+    if stride_um is None:
+        steps = []
+        for axis in (0, 1):
+            v = coords_um[:, axis].unique(sorted=True)
+            if v.numel() < 2:
+                raise ValueError("get_stride needs at least two distinct x and two distinct y coordinates; pass stride_um")
+            steps.append((v[1:] - v[:-1]).min())
+        stride_um = float(torch.stack(steps).min().item())
+    return (coords_um / stride_um).round().long()
+
+
+def vals_to_im(vals: torch.Tensor, coords_norm: torch.Tensor) -> torch.Tensor:
+    """reference `_vals_to_im` (:142-156): vals [N, ...], int64 grid coordinates [N, 2] (column 0 = x) -> [H, W, ...] with H = max y + 1, W = max x + 1,
+    zeros where no tile lies (amds_scatter_grid).  Where several tiles share a cell the highest tile index wins.  A negative coordinate raises."""
+    ops._dev(vals, coords_norm)
+    if coords_norm.dim() != 2 or coords_norm.shape[1] != 2 or coords_norm.shape[0] != vals.shape[0] or vals.shape[0] < 1:
+        raise ValueError(f"coords_norm must be [{vals.shape[0]}, 2] with at least one tile, got {tuple(coords_norm.shape)}")
+    xy = coords_norm.to(torch.int64).contiguous()
+    w, h = (int(v) + 1 for v in xy.max(0).values.tolist())          # the one host read: the image's shape
+    if h < 1 or w < 1:
+        raise ValueError("negative grid coordinates")
+    N = vals.shape[0]
+    v32 = vals.detach().reshape(N, -1).float().contiguous()
+    k = v32.shape[1]
+    out = torch.empty(h, w, k, dtype=torch.float32, device=vals.device)
+    cells = torch.empty(h * w + 1, dtype=torch.int32, device=vals.device)
+    _lib.check(_lib.lib().amds_scatter_grid(v32.data_ptr(), xy.data_ptr(), out.data_ptr(), cells.data_ptr(), N, k, h, w, ops._stream()), "scatter_grid")
+    return out.reshape(h, w, *vals.shape[1:]).to(vals.dtype)
+
+
+def _top2(x: torch.Tensor):
+    """(index of the largest, largest, second largest) along dim 1; ties go to the LOWER class index (torch.argmax returns the first maximum)."""
+    i1 = x.argmax(dim=1, keepdim=True)
+    v1 = x.gather(1, i1)
+    v2 = x.scatter(1, i1, float("-inf")).max(dim=1).values
+    return i1.squeeze(1), v1.squeeze(1), v2
+
+
+def category_maps(gradcam: torch.Tensor, scores: torch.Tensor):
+    """reference :464-498 for every category at once: gradcam [N, C] (soft-maxed over the tiles), scores [N, C] -> (support, attention, category_score),
+    each [C, N].  support: a class's score minus its nearest competitor's; attention: the class's Grad-CAM score where it is the top class, else the
+    strongest other class's, each normalised by its maximum; category_score = support * attention / max(attention).  Where two classes tie for a tile's
+    top score the lower class index counts as the top one."""
+    if gradcam.shape != scores.shape or scores.dim() != 2 or scores.shape[1] < 2:
+        raise ValueError(f"gradcam and scores must both be [tiles, classes >= 2], got {tuple(gradcam.shape)} and {tuple(scores.shape)}")
+    Cn = scores.shape[1]
+    top, s1, s2 = _top2(scores)
+    gtop, g1, g2 = _top2(gradcam)
+    cls = torch.arange(Cn, device=scores.device)[:, None]           # [C, 1]
+    is_top = top[None, :] == cls                                    # [C, N]
+    support = torch.where(is_top, scores.t() - s2[None, :], scores.t() - s1[None, :])
+    others = torch.where(gtop[None, :] == cls, g2[None, :], g1[None, :])         # max over the other classes
+    attention = torch.where(is_top, gradcam.t() / gradcam.max(), others / others.max(dim=1, keepdim=True).values)
+    score = support * attention / attention.max(dim=1, keepdim=True).values
+    return support, attention, score
+
+
+@dataclass
+class SlideHeatmap:
+    """What the reference's `heatmaps_` computes for one slide before it starts drawing."""
+    task: str
+    slide_score: torch.Tensor                   # classification: softmax over the classes [C] (:403); regression: the output, 0-dim (:587)
+    coords_norm: torch.Tensor                   # int64 [N, 2]
+    gradcam: torch.Tensor                       # [N, C] (:407-411) or [N] (:590-592)
+    gradcam_2d: torch.Tensor                    # [H, W, C] (:412-415); regression: [H, W] min / max normalised (:594-597)
+    scores: torch.Tensor | None = None          # [N, C] (:417-427)
+    scores_2d: torch.Tensor | None = None       # [H, W, C] (:428-430)
+    support: torch.Tensor | None = None         # [C, N] (:471-475)
+    attention: torch.Tensor | None = None       # [C, N] (:483-494)
+    category_score: torch.Tensor | None = None  # [C, N] (:496-498)
+    tile_relevance: torch.Tensor | None = None  # regression: gradcam / max [N] (:593)
+
+
+def slide_heatmap(model: torch.nn.Module, feats: torch.Tensor, coords_um: torch.Tensor, *, task: str) -> SlideHeatmap:
+    """One slide, `task` "classification" (:401-498) or "regression" (:586-597): slide score, Grad-CAM scores, per-tile scores, their 2-D arrangements and
+    the per-category maps -- the tensors the reference's plotting takes from here."""
+    if task not in ("classification", "regression"):
+        raise ValueError(f"task must be 'classification' or 'regression', got {task!r}")
+    _check_inputs(feats, coords_um)
+    with _eval_mode(model), torch.no_grad():
+        logits = model(feats.unsqueeze(0), coords=coords_um.unsqueeze(0), mask=None).squeeze(0)          # :392-399
+    cn = grid_coords(coords_um)
+    if task == "regression":
+        cam = gradcam_single(model, feats, coords_um)
+        g2 = vals_to_im(cam, cn)
+        g2 = (g2 - g2.min()) / (g2.max() - g2.min() + 1e-8)
+        return SlideHeatmap(task, logits.squeeze(), cn, cam, g2, tile_relevance=cam / cam.max().clamp(min=1e-8))
+    cam = gradcam(model, feats, coords_um)
+    scores = tile_scores(model, feats, coords_um)
+    support, attention, cat = category_maps(cam, scores)
+    return SlideHeatmap(task, logits.softmax(0), cn, cam, vals_to_im(cam, cn), scores, vals_to_im(scores, cn), support, attention, cat)

@@ -718,6 +718,27 @@ def backward(pk: PackedVit, saved: dict, dlogits: torch.Tensor, *, need_params: 
     return G, dbags
 
 
+def gradcam(pk: PackedVit, saved: dict, *, scale: float = 1.0) -> torch.Tensor:
+    """-> cam_raw fp32 [C, Bb * Tn] = |mean_f bags * d logit_c / d bags| for every class (reference src/stamp/heatmaps/__init__.py:54, :137, before any
+    softmax) from the arena of an eval-mode `forward_train`: ONE library call (amds_mil_vit_gradcam) that loops over the class basis vectors
+    `scale * e_c` itself and ends each backward in a row-dot against the saved projection pre-activation -- no dbags, no Jacobian.  `scale`: the power of
+    two the 16-bit gradient tensors carry (1024 for an fp16 pack, as `_MilVitFunction`); the kernel divides it out."""
+    d = pk.dims
+    Bb, Tn, _ = saved["shape"]
+    arena = saved["arena"]
+    dev = arena.device
+    cfg, wc = pk.c_structs()
+    lib = _lib.lib()
+    need = lib.amds_mil_vit_gradcam_workspace_bytes(C.byref(cfg), Bb, Tn)
+    if need == 0:
+        _lib.check(-1, "mil_vit_gradcam_workspace_bytes")
+    ws = ops.scratch("mil_vit_gradcam", dev, need)
+    cam = torch.empty(d.C, Bb * Tn, dtype=torch.float32, device=dev)
+    _lib.check(lib.amds_mil_vit_gradcam(C.byref(cfg), C.byref(wc), C.byref(saved["drop"]), Bb, Tn, arena.data_ptr(), arena.numel(), float(scale),
+                                        cam.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()), "mil_vit_gradcam")
+    return cam
+
+
 def flops_per_bag(T_: int = 1024, Fd: int = 1024, D: int = 512, FF: int = 512, L: int = 2) -> float:
     """matmul FLOPs of one forward (2 per MAC): projection + L x (qkv, attention, out, fc1, fc2); training ~ 3x."""
     S = T_ + 1

@@ -519,6 +519,86 @@ def golden_mil_vit_train() -> None:
         save(f"mil_vit_train_{tag}.npz", **arrs)
 
 
+def exec_loop_body(path: Path, first: int, last: int, glb: dict) -> dict:
+    """exec the statements of a `for` loop's body that lie in the line range [first, last] of a reference file (inline arithmetic that is not a
+    function of its own), in the order they stand there; the loop variables come from `glb`."""
+    tree = ast.parse(path.read_text())
+    for node in ast.walk(tree):
+        if isinstance(node, ast.For):
+            body = [n for n in node.body if n.lineno >= first and n.end_lineno <= last]
+            if body and node.lineno < first and node.end_lineno >= last:
+                exec(compile(ast.Module(body=body, type_ignores=[]), str(path), "exec"), glb)
+                return glb
+    raise AssertionError(f"no loop body at {path}:{first}-{last}")
+
+
+def golden_heatmaps() -> None:
+    """One slide's heat-map quantities from the reference's own functions (src/stamp/heatmaps/__init__.py): `_gradcam_per_category` :36-56,
+    `_gradcam_single` :115-139, `_vals_to_im` :142-156, the one-tile-bag scores :417-427 and the per-category maps :468-498 (inline statements,
+    lifted by line range); grid coordinates by `get_stride` (modeling/data.py:1150-1161) and :376."""
+    from typing import Optional, cast
+
+    from torch import Tensor
+    from torch.func import jacrev
+
+    vt = sys.modules.get("stamp.modeling.models.vision_tranformer") or load_by_path(
+        "stamp.modeling.models.vision_tranformer", REF / "modeling" / "models" / "vision_tranformer.py")
+    hm_path = REF / "heatmaps" / "__init__.py"
+    glb = exec_defs(hm_path, {"_gradcam_per_category", "_gradcam_single", "_vals_to_im"},
+                    dict(torch=torch, Tensor=Tensor, jacrev=jacrev, cast=cast, Optional=Optional))
+    get_stride = exec_defs(REF / "modeling" / "data.py", {"get_stride"}, dict(torch=torch, Tensor=Tensor, cast=cast))["get_stride"]
+
+    class OneLogit(torch.nn.Module):
+        def __init__(self, model, c):
+            super().__init__()
+            self.model, self.c = model, c
+
+        def forward(self, bags, *, coords, mask):
+            return self.model(bags, coords=coords, mask=mask)[:, self.c]
+
+    N, GW, GH = 61, 9, 8
+    for tag, use_alibi, kw in (
+        ("plain", False, dict(dim_output=3, dim_input=48, dim_model=64, n_layers=2, n_heads=2, dim_feedforward=96)),
+        ("alibi", True, dict(dim_output=2, dim_input=40, dim_model=64, n_layers=2, n_heads=4, dim_feedforward=64)),
+    ):
+        torch.manual_seed(27 if use_alibi else 26)
+        model = vt.VisionTransformer(dropout=0.0, use_alibi=use_alibi, **kw)
+        single = vt.VisionTransformer(dropout=0.0, use_alibi=use_alibi, **{**kw, "dim_output": 1})
+        with torch.no_grad():       # a head as a trained one has it: class rows that differ (a fresh Linear's rows give nearly parallel maps)
+            model.mlp_head[0].weight.mul_(4.0)
+        feats = torch.randn(N, kw["dim_input"])
+        cells = torch.randperm(GW * GH)[:N]
+        coords_um = torch.stack([cells % GW, cells // GW], dim=1).float() * 256.0
+        if use_alibi:
+            for m in (model, single):
+                m.train()
+                with torch.no_grad():
+                    for i in range(2):
+                        m(feats[None] + i, coords=coords_um[None] * (1 + i), mask=None)
+        model.eval()
+        single.eval()
+        stride = get_stride(coords_um)
+        coords_norm = (coords_um / stride).round().long()                                      # :376
+        cam = glb["_gradcam_per_category"](model, feats, coords_um).detach()
+        cam_raw = torch.stack([glb["_gradcam_single"](OneLogit(model, c), feats, coords_um).detach() for c in range(kw["dim_output"])], dim=1)
+        cam_single = glb["_gradcam_single"](single, feats, coords_um).detach()
+        with torch.no_grad():
+            slide_logits = model(feats.unsqueeze(0), coords=coords_um.unsqueeze(0), mask=None).squeeze(0)
+            scores = torch.softmax(model(feats.unsqueeze(-2), coords=coords_um.unsqueeze(-2), mask=torch.zeros(N, 1, dtype=torch.bool)), dim=1)
+        cam_2d = glb["_vals_to_im"](cam, coords_norm)
+        support, attention, cat_score = [], [], []
+        for pos_idx in range(kw["dim_output"]):
+            env = dict(torch=torch, scores=scores, gradcam=cam, pos_idx=pos_idx, model=types.SimpleNamespace(categories=list(range(kw["dim_output"]))))
+            exec_loop_body(hm_path, 468, 498, env)
+            support.append(env["category_support"]); attention.append(env["attention"]); cat_score.append(env["category_score"])
+        arrs = dict(feats=feats.numpy(), coords_um=coords_um.numpy(), coords_norm=coords_norm.numpy(), stride_um=np.float32(stride), cam=cam.numpy(),
+                    cam_raw=cam_raw.numpy(), cam_single=cam_single.numpy(), scores=scores.numpy(), slide_logits=slide_logits.numpy(), cam_2d=cam_2d.numpy(),
+                    support=torch.stack(support).numpy(), attention=torch.stack(attention).numpy(), category_score=torch.stack(cat_score).numpy(),
+                    **sd_np(model), **sd_np(single, "single:"))
+        arrs["hparams"] = np.array([kw[k] for k in ("dim_output", "dim_input", "dim_model", "n_layers", "n_heads", "dim_feedforward")])
+        save(f"heatmaps_{tag}.npz", **arrs)
+
+
 def golden_transmil() -> None:
     tm = load_by_path("stamp.modeling.models.trans_mil", REF / "modeling" / "models" / "trans_mil.py")
     for tag, T, dim_in, dim_h in (("t50", 50, 24, 64), ("t300", 300, 32, 64)):
@@ -1065,6 +1145,7 @@ def main() -> None:
     golden_get_coords()
     golden_mil_vit()
     golden_mil_vit_train()
+    golden_heatmaps()
     golden_transmil()
     golden_mlp_cox_transforms()
     golden_bag()
