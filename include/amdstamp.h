@@ -977,6 +977,9 @@ int amds_landmark_mean(const float* x, long sxo, long sxi, int ld, float* out, i
                        float scale, void* stream);
 /* z0 = x^T / (max row-abs-sum * max col-abs-sum), maxima over ALL nmat matrices (trans_mil.py:23-28). scratch8: 8 B. */
 int amds_pinv_init(const float* x, float* z, int nmat, int n, void* scratch8, void* stream);
+/* The same start with the maxima taken per `group` CONSECUTIVE matrices (nmat a multiple of group): with group = 8 every bag's 8 head matrices get the scale the
+ * reference computes for that bag at batch 1 (trans_mil.py:26-28 with b = 1).  group = nmat gives the bits of amds_pinv_init.  scratch: 8 B per group. */
+int amds_pinv_init_grouped(const float* x, float* z, int nmat, int n, int group, void* scratch, void* stream);
 /* out[z][t][c] += sum_k w[i][k] v[z][t+k-taps/2][c]: per-head depth-wise conv along the sequence (trans_mil.py:71-78,150-151). */
 int amds_dwconv_seq(const float* v, long svo, long svi, int ldv, const float* w, float* out, long soo, long soi, int ldo,
                     int outer, int inner, int n, int d, int taps, void* stream);
@@ -1019,6 +1022,34 @@ size_t amds_transmil_workspace_bytes(const amds_transmil_cfg* cfg_host, int n_ba
  * [n_bags][classes].  Launches only, on `stream`; ws 256-byte aligned. */
 int amds_transmil_forward(const amds_transmil_cfg* cfg_host, const amds_transmil_weights* w_host, const void* bags, int bags_dtype, float* logits,
                           int n_bags, int n_tiles, void* ws, size_t ws_bytes, void* stream);
+
+/* The same forward over RAGGED bags: n_bags bags of different tile counts packed without padding, one call, every bag computed as the reference computes it
+ * at batch 1 (validation and deploy: modeling/train.py:467-477 `bag_size=None, batch_size=1`; deploy.py:390-456).  Per bag of T tiles (m = dim / 2):
+ *   side = ceil(sqrt(T)), n = side^2 + 1 token rows (class token, the tiles, the FIRST tiles again)                         trans_mil.py:306-314
+ *   pad = (m - n % m) % m zero rows in FRONT, np = n + pad, l = np / m tokens per landmark                                    :96-100, :113
+ *   PPEG on the bag's own side x side grid                                                                                    :274-283
+ *   the pseudo-inverse start scaled by the maxima over THIS bag's 8 head matrices (amds_pinv_init_grouped)                  :26-28 with b = 1
+ * Zero-padding bags to a common length would change every one of these, and a dense batch shares ONE pinv scale among its bags (six iterations do not
+ * converge it: ~1e-4 on logits of ~1), so neither stands in for the one-bag loop.  The call keeps every bag's padded token rows in one buffer, bags ordered by
+ * np: token-row work (_fc1, LayerNorms, to_qkv, to_out, _fc2) runs once over all rows, landmark-sized work (sim2, the pinv chain in chunks of 256 matrices)
+ * once over all bags, and the products that see the token count once per BUCKET of bags with equal np, as ordinary batched calls of the kernels above.
+ *   amds_transmil_ragged_plan    host only: the per-bag records in the library's order (by np, then caller order) for the caller to upload; `orig` = caller index
+ *   tiles_host                   the tile counts in the caller's order, HOST memory: everything is validated and every launch sized without reading the device
+ *   feats                        [sum tiles][n_feats] in the caller's order, AMDS_F32 / AMDS_F16 / AMDS_BF16
+ *   table_dev                    n_bags records of amds_transmil_ragged_plan for the SAME tiles_host, device memory
+ *   logits                       fp32 [n_bags][classes] in the caller's order
+ * n_bags * 8 <= 65535 (one launch's batch dimension); n_bags = 0 returns AMDS_OK and launches nothing.  Follows the context's matmul precision and class-row
+ * tail (amds_set_mil_cls_tail) like amds_transmil_forward.  Launches only, on `stream`; ws 256-byte aligned. */
+typedef struct {
+    long tile_off;                                 /* first row of the bag in feats */
+    long row_off;                                  /* first row of the bag's np padded token rows in the call's token buffers */
+    int tiles, side, n, pad, np;
+    int orig;                                      /* the bag's index in the caller's order */
+} amds_transmil_bag;
+int amds_transmil_ragged_plan(const amds_transmil_cfg* cfg_host, int n_bags, const int* tiles_host, amds_transmil_bag* table_host);
+size_t amds_transmil_ragged_workspace_bytes(const amds_transmil_cfg* cfg_host, int n_bags, const int* tiles_host);
+int amds_transmil_forward_ragged(const amds_transmil_cfg* cfg_host, const amds_transmil_weights* w_host, const void* feats, int feats_dtype, const int* tiles_host,
+                                 const amds_transmil_bag* table_dev, float* logits, int n_bags, void* ws, size_t ws_bytes, void* stream);
 
 /* One TransMIL layer's attention in TRAINING, forward and backward as one call each (reference trans_mil.py:81-163 with mask = None, the
  * residual of :263, `to_out`'s Dropout(0.1) of :66 live when p_drop > 0; loss.backward() through it, models/__init__.py:239-279):

@@ -112,6 +112,12 @@ class TransMilWeights(C.Structure):
                [(n, C.c_void_p) for n in ("ppeg_w7", "ppeg_b7", "ppeg_w5", "ppeg_b5", "ppeg_w3", "ppeg_b3", "norm_w", "norm_b", "fc2_w", "fc2_b")]
 
 
+class TransMilBag(C.Structure):
+    """amds_transmil_bag: one record of the ragged TransMIL forward's per-bag table (amds_transmil_ragged_plan)."""
+    _fields_ = [("tile_off", C.c_long), ("row_off", C.c_long), ("tiles", C.c_int), ("side", C.c_int), ("n", C.c_int), ("pad", C.c_int), ("np", C.c_int),
+                ("orig", C.c_int)]
+
+
 class TransMilLayerGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("norm_w", "norm_b", "qkv_w", "out_w", "out_b", "conv_w")]
 
@@ -280,6 +286,9 @@ PROTOTYPES = {
     "amds_nystrom_attn_fwd": (_i, [_vp, _i, _vp, _vp, _i, _i, _f, C.c_uint64, C.c_uint32, _vp, _sz, _vp]),
     "amds_nystrom_attn_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _f, C.c_uint64, C.c_uint32, _vp, _sz, _vp, _sz, _vp]),
     "amds_transmil_forward": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _sz, _vp]),
+    "amds_transmil_ragged_plan": (_i, [_vp, _i, _vp, _vp]),
+    "amds_transmil_ragged_workspace_bytes": (_sz, [_vp, _i, _vp]),
+    "amds_transmil_forward_ragged": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "amds_mil_vit_train_saved_bytes": (_sz, [_vp, _i, _i]),
     "amds_mil_vit_train_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "amds_mil_vit_train_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
@@ -293,6 +302,7 @@ PROTOTYPES = {
     "amds_softmax_rows": (_i, [_vp, _l, _i, _vp]),
     "amds_landmark_mean": (_i, [_vp, _l, _l, _i, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "amds_pinv_init": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "amds_pinv_init_grouped": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "amds_dwconv_seq_row": (_i, [_vp, _l, _l, _i, _vp, _vp, _l, _l, _i, _i, _i, _i, _i, _i, _vp]),
     "amds_dwconv_seq": (_i, [_vp, _l, _l, _i, _vp, _vp, _l, _l, _i, _i, _i, _i, _i, _i, _vp]),
     "amds_ppeg": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

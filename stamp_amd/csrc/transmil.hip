@@ -9,6 +9,7 @@
 //   amds_softmax_rows     in-place row softmax, any row length
 //   amds_landmark_mean    segment sums of l consecutive tokens divided by l  (:114-124)
 //   amds_pinv_init        z0 = x^T / (max_j sum_i |x_ij| * max_i sum_j |x_ij|), maxima over ALL batches and heads (:26-28)
+//   amds_pinv_init_grouped  the same with the maxima per group of consecutive matrices (a bag's 8 heads: the reference at batch 1; transmil_ragged.hip)
 //   amds_dwconv_seq       depth-wise (per head) 33-tap convolution along the sequence, added in place (:150-151)
 //   amds_ppeg             x + dw7x7(x) + dw5x5(x) + dw3x3(x) on the sqrt(T) x sqrt(T) token grid (:274-283)
 #include "common.h"
@@ -616,8 +617,9 @@ __global__ void landmark_mean4_kernel(const float* __restrict__ x, long sxo, lon
 // meet in LDS.  (Round 1's form -- a thread per row walking it element by element, every load of a wave touching 64 cache lines -- took 243 us per call at
 // 512 matrices of 256 x 256: 0.55 TB/s.)  A HALF-wave per row (its sum by DPP, no LDS round trips), NV = float4 per lane and row: n <= 128 NV.
 template <int NV>
-__global__ void __launch_bounds__(256) absmax_kernel(const float* __restrict__ x, int n, unsigned* __restrict__ out2) {
+__global__ void __launch_bounds__(256) absmax_kernel(const float* __restrict__ x, int n, unsigned* __restrict__ out2, int group) {
     __shared__ float sc[8][128 * NV];
+    out2 += 2 * (blockIdx.x / group);                           // one pair of maxima per `group` consecutive matrices (group = all of them: ONE pair)
     const float* p = x + (long)blockIdx.x * n * n;
     const int lane = threadIdx.x & 63, l31 = lane & 31, half = threadIdx.x >> 5;           // eight half-waves, a row each, two rows of a half-wave in flight
     f32x4 cs[NV];
@@ -660,8 +662,9 @@ __global__ void __launch_bounds__(256) absmax_kernel(const float* __restrict__ x
     }
 }
 // any n (unaligned rows, n > 1024): a thread per row / column
-__global__ void __launch_bounds__(256) absmax_any_kernel(const float* __restrict__ x, int n, unsigned* __restrict__ out2) {
+__global__ void __launch_bounds__(256) absmax_any_kernel(const float* __restrict__ x, int n, unsigned* __restrict__ out2, int group) {
     const float* p = x + (long)blockIdx.x * n * n;
+    out2 += 2 * (blockIdx.x / group);
     float rmax = 0.f, cmax = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) {
         float rs = 0.f, cs = 0.f;
@@ -672,8 +675,9 @@ __global__ void __launch_bounds__(256) absmax_any_kernel(const float* __restrict
     if ((threadIdx.x & 63) == 0) { atomicMax(out2, __float_as_uint(rmax)); atomicMax(out2 + 1, __float_as_uint(cmax)); }
 }
 // z = x^T / (mx[0] * mx[1]) per matrix, 32 x 32 tiles through LDS (both sides coalesced; the 16 x 16 direct form read 64-byte pieces: 114 us per call)
-__global__ void __launch_bounds__(256) transpose_scale_kernel(const float* __restrict__ x, float* __restrict__ z, int n, const unsigned* __restrict__ mx) {
+__global__ void __launch_bounds__(256) transpose_scale_kernel(const float* __restrict__ x, float* __restrict__ z, int n, const unsigned* __restrict__ mx, int group) {
     __shared__ float t[32][33];
+    mx += 2 * (blockIdx.z / group);
     const float inv = 1.0f / (__uint_as_float(mx[0]) * __uint_as_float(mx[1]));
     const long base = (long)blockIdx.z * n * n;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;                      // 32 x 8
@@ -1466,17 +1470,29 @@ extern "C" int amds_landmark_mean(const float* x, long sxo, long sxi, int ld, fl
     return AMDS_OK;
 }
 
-extern "C" int amds_pinv_init(const float* x, float* z, int nmat, int n, void* scratch8, void* stream) {
-    AMDS_REQUIRE(x && z && scratch8 && nmat > 0 && nmat <= 65535 && n > 0, "amds_pinv_init: bad arguments");
+// maxima per `group` consecutive matrices; scratch: 8 B per group
+static int pinv_init_at(const float* x, float* z, int nmat, int n, int group, void* scratch, void* stream) {
+    using namespace amds;
     hipStream_t st = (hipStream_t)stream;
-    AMDS_HIP(hipMemsetAsync(scratch8, 0, 8, st));
-    if (n % 4 == 0 && n <= 256 && ((uintptr_t)x & 15) == 0) hipLaunchKernelGGL((absmax_kernel<2>), dim3(nmat), dim3(256), 0, st, x, n, (unsigned*)scratch8);
-    else if (n % 4 == 0 && n <= 1024 && ((uintptr_t)x & 15) == 0) hipLaunchKernelGGL((absmax_kernel<8>), dim3(nmat), dim3(256), 0, st, x, n, (unsigned*)scratch8);
-    else hipLaunchKernelGGL(absmax_any_kernel, dim3(nmat), dim3(256), 0, st, x, n, (unsigned*)scratch8);
+    AMDS_HIP(hipMemsetAsync(scratch, 0, (size_t)8 * (nmat / group), st));
+    if (n % 4 == 0 && n <= 256 && ((uintptr_t)x & 15) == 0) hipLaunchKernelGGL((absmax_kernel<2>), dim3(nmat), dim3(256), 0, st, x, n, (unsigned*)scratch, group);
+    else if (n % 4 == 0 && n <= 1024 && ((uintptr_t)x & 15) == 0) hipLaunchKernelGGL((absmax_kernel<8>), dim3(nmat), dim3(256), 0, st, x, n, (unsigned*)scratch, group);
+    else hipLaunchKernelGGL(absmax_any_kernel, dim3(nmat), dim3(256), 0, st, x, n, (unsigned*)scratch, group);
     AMDS_LAUNCH_CHECK("absmax_kernel");
-    hipLaunchKernelGGL(transpose_scale_kernel, dim3(cdiv(n, 32), cdiv(n, 32), nmat), dim3(256), 0, st, x, z, n, (const unsigned*)scratch8);
+    hipLaunchKernelGGL(transpose_scale_kernel, dim3(cdiv(n, 32), cdiv(n, 32), nmat), dim3(256), 0, st, x, z, n, (const unsigned*)scratch, group);
     AMDS_LAUNCH_CHECK("transpose_scale_kernel");
     return AMDS_OK;
+}
+
+extern "C" int amds_pinv_init(const float* x, float* z, int nmat, int n, void* scratch8, void* stream) {
+    AMDS_REQUIRE(x && z && scratch8 && nmat > 0 && nmat <= 65535 && n > 0, "amds_pinv_init: bad arguments");
+    return pinv_init_at(x, z, nmat, n, nmat, scratch8, stream);
+}
+
+extern "C" int amds_pinv_init_grouped(const float* x, float* z, int nmat, int n, int group, void* scratch, void* stream) {
+    AMDS_REQUIRE(x && z && scratch && nmat > 0 && nmat <= 65535 && n > 0, "amds_pinv_init_grouped: bad arguments");
+    AMDS_REQUIRE(group > 0 && nmat % group == 0, "amds_pinv_init_grouped: %d matrices are no whole number of groups of %d", nmat, group);
+    return pinv_init_at(x, z, nmat, n, group, scratch, stream);
 }
 
 extern "C" int amds_dwconv_seq(const float* v, long svo, long svi, int ldv, const float* w, float* out, long soo, long soi, int ldo,

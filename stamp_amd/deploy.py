@@ -60,15 +60,24 @@ def model_from_checkpoint(ckpt: Mapping) -> torch.nn.Module:
 
 def _ragged_outputs(model, batches, device, bags_per_call: int, max_rows_per_call: int) -> list[torch.Tensor]:
     """The per-batch outputs of the loop in `predict_`, with consecutive one-bag batches grouped (mil_core.group_bags) into ragged calls of a `vit` head
-    (`VisionTransformer.forward_ragged`): each batch's row is the one its own forward gives.  Batches of several bags keep their own forward."""
+    (`VisionTransformer.forward_ragged`): each batch's row is the one its own forward gives.  Batches of several bags keep their own forward.
+    A TransMIL head groups by padded token rows (`TransMIL.forward_ragged`, transmil_core.group_bags_padded): each batch's row is the batch-1 forward's to fp32
+    rounding (the packed products may take another tile shape than a one-bag call's)."""
     from . import mil_core
+    from .mil import TransMIL
 
-    limit = mil_core.max_shared_tiles(model._infer_pack(torch.device(device)))
+    trans = isinstance(model, TransMIL)
+    limit = 0 if trans else mil_core.max_shared_tiles(model._infer_pack(torch.device(device)))
     outs: list = []
     pend: list = []
 
     def flush():
         if not pend:
+            return
+        if trans:
+            out = model.forward_ragged([b for b, _ in pend], bags_per_call=bags_per_call, max_rows_per_call=max_rows_per_call)
+            outs.extend(out.float().cpu().split(1, dim=0))
+            pend.clear()
             return
         for a, e in mil_core.group_bags([b.shape[0] for b, _ in pend], bags_per_call, max_rows_per_call, limit):
             cs = None if pend[a][1] is None else [c for _, c in pend[a:e]]
@@ -95,8 +104,9 @@ def predict_(model: torch.nn.Module, batches: Iterable, patient_ids: Sequence[st
     """batches: iterable of (bags, coords, bag_sizes, targets) as the reference's test DataLoader yields them (full bags, batch 1,
     `modeling/data.py:255-277`); only bags / coords are used (`Lit*.predict_step`, `models/__init__.py:302-313`: `mask=None`).
     Returns patient -> prediction on the CPU: class probabilities (classification), raw value (regression), risk score (survival).
-    bags_per_call > 1 (`vit` heads; other heads ignore it): consecutive bags share ONE ragged forward, at most `bags_per_call` bags and
-    `max_rows_per_call` token rows per call, a bag too long to share runs alone; every prediction is the one of the one-bag loop."""
+    bags_per_call > 1 (`vit` and TransMIL heads; other heads ignore it): consecutive bags share ONE ragged forward, at most `bags_per_call` bags and
+    `max_rows_per_call` token rows per call (TransMIL: padded token rows), a bag too long to share runs alone; every prediction is the one of the one-bag
+    loop (`vit`: bit for bit; TransMIL: to fp32 rounding, every bag with its own grid, padding and pseudo-inverse scale as at batch 1)."""
     if bags_per_call < 1 or max_rows_per_call < 1:
         raise ValueError("bags_per_call and max_rows_per_call must be >= 1")
     if task not in ("classification", "regression", "survival"):
@@ -117,9 +127,9 @@ def predict_(model: torch.nn.Module, batches: Iterable, patient_ids: Sequence[st
             cat = {t: torch.softmax(v, dim=1) for t, v in cat.items()}
         n = next(iter(cat.values())).shape[0]
         return {pid: {t: cat[t][i] for t in cat} for i, pid in enumerate(list(patient_ids)[:n])}
-    from .mil import VisionTransformer
+    from .mil import TransMIL, VisionTransformer
 
-    if bags_per_call > 1 and isinstance(model, VisionTransformer):
+    if bags_per_call > 1 and isinstance(model, (VisionTransformer, TransMIL)):
         outs = _ragged_outputs(model, batches, device, bags_per_call, max_rows_per_call)
     else:
         outs = []

@@ -585,6 +585,24 @@ class TransMIL(nn.Module):
             self._cw, self._cw_keep, self._cw_key = w, keep, key
         return self._cw
 
+    def forward_ragged(self, bags, *, coords=None, bags_per_call: int | None = None, max_rows_per_call: int = 1 << 62) -> torch.Tensor:
+        """Bags of DIFFERENT lengths in one library call: a list of [T_i, dim_input] tensors -> logits [N, dim_output] in the list's order, row i what the
+        reference computes for bag i at batch 1 -- its own square grid, front padding, PPEG grid and pseudo-inverse scale (trans_mil.py:306-314, :96-100, :26-28;
+        csrc/transmil_ragged.hip).  `coords` is accepted and ignored like in `forward`.  At most `bags_per_call` bags and `max_rows_per_call` padded token rows
+        per library call (transmil_core.group_bags_padded; default: one call).  Inference only: eval mode under torch.no_grad() / inference_mode()."""
+        from . import mil_core, transmil_core
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError("forward_ragged is the inference forward: call it in eval mode (.eval()) under torch.no_grad() or torch.inference_mode()")
+        bags = list(bags)
+        dev = bags[0].device if bags else next(self.parameters()).device
+        mil_core._validate_bags(bags, None, self._fc1[0].in_features, False)
+        if bags and not bags[0].is_cuda:
+            raise RuntimeError("HIP TransMIL needs bags on the GPU (no CPU fallback)")
+        if not bags:
+            return torch.empty(0, self.n_classes, dtype=torch.float32, device=dev)
+        dims = (self._fc1[0].in_features, self.dim_hidden, self.n_classes)
+        return transmil_core.forward_ragged(self._c_weights(dev), dims, bags, bags_per_call=bags_per_call, max_rows_per_call=max_rows_per_call)
+
     def _forward_c(self, h: torch.Tensor) -> torch.Tensor:
         import ctypes as C
         Bb, T, F = h.shape

@@ -245,3 +245,99 @@ def backward(saved: dict, dlogits: torch.Tensor, *, need_params: bool = True, ne
     return G, (dbags.view(Bb, Tn, Fd) if need_bags else None)
 
 
+# ---- ragged inference: bags of different lengths in one library call (amds_transmil_forward_ragged, csrc/transmil_ragged.hip) ------------------
+MAX_BAGS_PER_CALL = 65535 // HEADS          # bags x 8 heads is one launch's batch dimension
+
+
+def bag_geometry(tiles: int, m: int) -> dict:
+    """The token geometry the reference gives ONE bag of `tiles` tiles with m = dim_hidden // 2 landmarks: side = ceil(sqrt(T)) and n = side^2 + 1 token rows
+    (trans_mil.py:306-314), pad = front padding to a multiple of m, np = n + pad (:96-100), l = ceil(n / m) tokens per landmark (:113).  Host only."""
+    tiles, m = int(tiles), int(m)
+    if tiles < 1 or m < 1:
+        raise ValueError(f"a bag needs at least one tile and one landmark, got tiles={tiles} m={m}")
+    side = math.isqrt(tiles - 1) + 1
+    n = side * side + 1
+    pad = (m - n % m) % m
+    return dict(side=side, n=n, pad=pad, np=n + pad, l=(n + m - 1) // m)
+
+
+def ragged_plan(lengths, dim_hidden: int):
+    """Tile counts in the caller's order -> (table, buckets, perm): `table` the library's per-bag records (a ctypes array of _lib.TransMilBag, filled by
+    amds_transmil_ragged_plan) in the library's order -- by np, then caller order --, `buckets` [(first slot, bags, np)] the runs of equal np the bucketed
+    products run over, `perm[slot]` the caller index (the library un-permutes the logits itself).  Host only."""
+    import ctypes as C
+    lengths = [int(t) for t in lengths]
+    n = len(lengths)
+    cfg = _lib.TransMilCfg(1, int(dim_hidden), 1)
+    tiles = (C.c_int * max(n, 1))(*lengths)
+    table = (_lib.TransMilBag * max(n, 1))()
+    _lib.check(_lib.lib().amds_transmil_ragged_plan(C.byref(cfg), n, tiles, table), "transmil_ragged_plan")
+    buckets: list[tuple[int, int, int]] = []
+    for s in range(n):
+        if buckets and buckets[-1][2] == table[s].np:
+            buckets[-1] = (buckets[-1][0], buckets[-1][1] + 1, table[s].np)
+        else:
+            buckets.append((s, 1, table[s].np))
+    return table, buckets, [table[s].orig for s in range(n)]
+
+
+def group_bags_padded(lengths, dim_hidden: int, bags_per_call: int, max_rows_per_call: int) -> list[tuple[int, int]]:
+    """Consecutive bags -> [start, end) groups for the ragged TransMIL forward: at most `bags_per_call` bags (and MAX_BAGS_PER_CALL) and `max_rows_per_call`
+    PADDED token rows (sum of np_i, `bag_geometry`) per group -- the rows the workspace scales with; a bag whose padded rows alone exceed the limit is a group
+    of its own.  Order is kept; host-only."""
+    if bags_per_call < 1 or max_rows_per_call < 1:
+        raise ValueError("bags_per_call and max_rows_per_call must be >= 1")
+    cap = min(int(bags_per_call), MAX_BAGS_PER_CALL)
+    m = int(dim_hidden) // 2
+    groups: list[tuple[int, int]] = []
+    start, rows = 0, 0
+    for i, t in enumerate(lengths):
+        r = bag_geometry(t, m)["np"]
+        if i > start and (i - start >= cap or rows + r > max_rows_per_call):
+            groups.append((start, i))
+            start, rows = i, 0
+        rows += r
+    if start < len(lengths):
+        groups.append((start, len(lengths)))
+    return groups
+
+
+def forward_infer_ragged(w: "_lib.TransMilWeights", dims: tuple[int, int, int], bags: list) -> torch.Tensor:
+    """Bags [T_i, dim_input] on one device -> logits [N, dim_output], ONE library call: row i is the reference's forward of bag i at batch 1."""
+    import ctypes as C
+    Fd, Cd, Cc = dims
+    dev = bags[0].device
+    n = len(bags)
+    lengths = [int(b.shape[0]) for b in bags]
+    dts = {b.dtype for b in bags}
+    dt = dts.pop() if len(dts) == 1 else torch.float32
+    if dt not in ops._DT:
+        dt = torch.float32
+    feats = (bags[0].to(dt) if n == 1 else torch.cat([b.to(dt) for b in bags], dim=0)).contiguous()
+    lib = _lib.lib()
+    cfg = _lib.TransMilCfg(Fd, Cd, Cc)
+    tiles = (C.c_int * n)(*lengths)
+    table = (_lib.TransMilBag * n)()
+    _lib.check(lib.amds_transmil_ragged_plan(C.byref(cfg), n, tiles, table), "transmil_ragged_plan")
+    need = lib.amds_transmil_ragged_workspace_bytes(C.byref(cfg), n, tiles)
+    if need == 0:
+        _lib.check(-1, "transmil_ragged_workspace_bytes")
+    table_dev = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+    ws = ops.scratch("transmil_ragged", dev, need)
+    logits = torch.empty(n, Cc, dtype=torch.float32, device=dev)
+    ops.sync_float32_matmul_precision()
+    _lib.check(lib.amds_transmil_forward_ragged(C.byref(cfg), C.byref(w), feats.data_ptr(), ops._DT[feats.dtype], tiles, table_dev.data_ptr(), logits.data_ptr(), n,
+                                                ws.data_ptr(), ws.numel(), ops._stream()), "transmil_forward_ragged")
+    return logits
+
+
+def forward_ragged(w: "_lib.TransMilWeights", dims: tuple[int, int, int], bags: list, *, bags_per_call: int | None = None,
+                   max_rows_per_call: int = 1 << 62) -> torch.Tensor:
+    """A list of bags [T_i, dim_input] -> logits [N, dim_output] in the list's order: grouped on the host (`group_bags_padded`), one ragged library call per group.
+    Workspace per call: 28 * dim_hidden bytes per padded token row of the call (x, y, yp, merged, qkv) + 48 * dim_hidden bytes per padded row of its LARGEST
+    bucket of equal np (attn1, attn3, attn1 pinv) + 54 * dim_hidden^2 bytes per bag (landmarks, attn2 and the chain's buffers) + 4 * dim_input bytes per tile
+    (fp16 / bf16 bags): at dim_hidden 512 at most 38 KB per padded row and 14 MB per bag."""
+    lengths = [int(b.shape[0]) for b in bags]
+    outs = [forward_infer_ragged(w, dims, bags[a:e])
+            for a, e in group_bags_padded(lengths, dims[1], bags_per_call or max(len(bags), 1), max_rows_per_call)]
+    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
