@@ -10,6 +10,13 @@
  *     (reference src/stamp/preprocessing/__init__.py:290-336), so failures must come back as values;
  *   - no hidden allocation and no device synchronisation: the caller owns all memory, passes a
  *     workspace (size from the matching *_workspace_bytes) and a hipStream_t (as void*);
+ *   - a workspace is scratch: a call ignores what `ws` holds on entry and writes nothing outside [ws, ws + *_workspace_bytes); the `saved` arena of
+ *     a training forward is a pure output of that forward (every byte the backward reads is written by it) and read-only afterwards.  Two calls
+ *     may share a workspace when they do not overlap in time; a result never depends on what ran there before (tests/test_gpu_abi_contract.py runs the
+ *     whole-model calls on poisoned and on used workspaces; DESIGN.md section 5.1 names the entry points whose line rests on reading the code);
+ *   - a kernel reads and writes the elements it is given and nothing else: not the columns between a row's width and its leading dimension, not
+ *     the bytes in front of or behind a tensor, not the rows of another bag of the batch (tests/test_gpu_abi_*.py).  Padding a kernel DOES read
+ *     is stated at its entry point (the GEMMs' K is a multiple of 64: pad with amds_cast_pad, which writes the zeros itself);
  *   - row-major contiguous tensors; leading dimensions passed where views are allowed;
  *   - "act dtype": AMDS_F16 (default; fp16 operands, fp32 accumulate) or AMDS_BF16.
  *
@@ -445,6 +452,8 @@ size_t amds_vit_workspace_diag_offset(const amds_vit_cfg* cfg_host, int batch);
 int amds_vit_forward(const amds_vit_cfg* cfg_host, const amds_vit_weights* w_host,
                      const uint8_t* tiles, void* feats_f16, int B, int chunk,
                      void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored, except the int32[2] range counters at amds_vit_workspace_diag_offset, which the call ADDS to (the caller zeroes them);
+ *     nothing outside [ws, ws + amds_vit_workspace_bytes(cfg, chunk)) is written. */
 
 /* The guard a host runs over features BEFORE it persists them (the reference writes `model(tiles)[:, 0].half()` straight into the .h5,
  * src/stamp/preprocessing/__init__.py:324-345; its per-slide try/except :328-336 is the only place an error can surface).  Counts the
@@ -462,12 +471,16 @@ int amds_check_finite(const void* x, long n, int dtype, int* count_dev, int* cou
 int amds_vit_forward_tokens(const amds_vit_cfg* cfg_host, const amds_vit_weights* w_host,
                             const uint8_t* tiles, void* feats_f16, float* tokens_f32, int B, int chunk,
                             void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored, except the int32[2] range counters at amds_vit_workspace_diag_offset, which the call ADDS to (the caller zeroes them);
+ *     nothing outside [ws, ws + amds_vit_workspace_bytes(cfg, chunk)) is written. */
 
 /* Same result as amds_vit_forward, with consecutive chunks alternating between `stream` and one library-owned side
  * stream so that two chunks are in flight (ws must hold 2 x amds_vit_workspace_bytes(chunk)); `stream` waits for the
  * side stream before the call's work is considered complete. */
 int amds_vit_forward_overlapped(amds_ctx* ctx, const amds_vit_cfg* cfg_host, const amds_vit_weights* w_host, const uint8_t* tiles,
                                 void* feats_f16, int B, int chunk, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored, except the int32[2] range counters at amds_vit_workspace_diag_offset, which the call ADDS to (the caller zeroes them);
+ *     nothing outside [ws, ws + 2 * amds_vit_workspace_bytes(cfg, chunk)) is written. */
 
 /* Building blocks of the exact class-token path (exposed for tests; amds_vit_forward calls them when exact_host is set).
  *   amds_attention_cls_f32   out[b][h*hd..] = softmax(q[b][h*hd..] . K_b,h^T / sqrt(hd)) V_b,h in fp32: ONE fp32 query row per (tile, head)
@@ -550,6 +563,8 @@ size_t amds_swin_workspace_bytes(const amds_swin_cfg* cfg_host, int batch);
  * value; either may be NULL.  The (u8/255 - mean)/std transform (ctranspath.py:56-64) is folded into the stem. */
 int amds_swin_forward(const amds_swin_cfg* cfg_host, const amds_swin_weights* w_host, const uint8_t* tiles,
                       void* feats_f16, float* feats_f32, int B, int chunk, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_swin_workspace_bytes(cfg, chunk)) is written. */
 
 /* ConvStem + patch LayerNorm (ctranspath.py:386-444, 905-911): u8 tiles -> fp32 tokens x [B][(img/4)^2][embed].
  * params (fp32, BatchNorm folded): a[3]=1/(255 std), b[3]=-mean/std, 2 pad, w1[27][C/8], b1[C/8], w2[9*C/8][C/4],
@@ -595,6 +610,8 @@ int amds_macenko_normalize_u8(const uint8_t* tiles, uint8_t* out, float* fit_out
 size_t amds_supertiles_to_tiles_workspace_bytes(int n, int S, int k, int t);
 int amds_supertiles_to_tiles_u8(const uint8_t* rgba, uint8_t* tiles, int n, int S, int k, int t, const int* bounds, const int* coef,
                                 int ksize, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_supertiles_to_tiles_workspace_bytes) is written. */
 
 /* Resize(O, bicubic) + CenterCrop(t) on RGB u8 tiles -- the transform some of the reference's extractors put in front of their model
  * (src/stamp/preprocessing/extractor/gigapath.py:21-28: Resize(256, BICUBIC), CenterCrop(224)).  torchvision's Resize on a PIL
@@ -604,6 +621,8 @@ int amds_supertiles_to_tiles_u8(const uint8_t* rgba, uint8_t* tiles, int n, int 
 size_t amds_tile_resize_crop_workspace_bytes(int n, int S, int t);
 int amds_tile_resize_crop_u8(const uint8_t* tiles, uint8_t* out, int n, int S, int O, int t, const int* bounds, const int* coef, int ksize, void* ws,
                              size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_tile_resize_crop_workspace_bytes) is written. */
 
 /* Keep-mask compaction on the device, between the texture filter and the tile encoder (reference tiling.py:171-193 `_tiles_with_tissue`
  * drops the rejected tiles one by one on the host): rows i < n of src (row_bytes each, a multiple of 16) whose score[i] >= cutoff (score NULL:
@@ -649,6 +668,8 @@ size_t amds_ticon_tile_workspace_bytes(const amds_ticon_weights* w_host, int n_t
 /* emb: [n_tiles][in_dim] AMDS_F32 / AMDS_F16 (the tile encoder's feature rows); out: [n_tiles][dim] in out_dtype (AMDS_F32 or AMDS_F16). */
 int amds_ticon_tile_forward(const amds_ticon_weights* w_host, const void* emb, int emb_dtype, void* out, int out_dtype, int n_tiles, void* ws,
                             size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_ticon_tile_workspace_bytes) is written. */
 
 /* ------------------------------------------------------------------------------------------------
  * Gated-attention pooling (CHIEF slide encoder; reference
@@ -674,6 +695,8 @@ size_t amds_gated_attn_pool_workspace_bytes(int N, int F, int L, int D);
  * amds_gated_attn_pool_batched_supported(F, L, D) -- CHIEF's two size_args are -- else the six-launch form below. */
 int amds_gated_attn_pool(const float* x, const amds_gap_weights* w_host, float* out, float* attn_raw,
                          int N, int F, int L, int D, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_gated_attn_pool_workspace_bytes) is written. */
 
 /* MANY bags in one launch -- what the reference's per-slide loop (src/stamp/encoding/encoder/__init__.py:42-118 `encode_slides_`, chief.py:119-127
  * `_generate_slide_embedding`, :129-135 the patient concatenation) and EAGLE's scoring pass (eagle.py:96-118) hand over when the feature matrices of
@@ -692,12 +715,16 @@ int amds_gated_attn_pool_batched_supported(int F, int L, int D);
 size_t amds_gated_attn_pool_batched_workspace_bytes(long total_rows, int bags, int F, int L, int D);
 int amds_gated_attn_pool_batched(const float* x, const long long* row_offsets, int bags, long total_rows, const amds_gap_weights* w_host, float* out,
                                  float* attn_raw, int F, int L, int D, int mode, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_gated_attn_pool_batched_workspace_bytes) is written. */
 
 /* The six-launch form (two exact-fp32 GEMMs through HBM, gate, softmax statistics, partial pooling, reduce; csrc/gap.hip): any F, L multiple of 4.
  * amds_gated_attn_pool falls back to it for shapes the fused kernel does not take; exported for the A/B in tools/gap_only.py. */
 size_t amds_gated_attn_pool_unfused_workspace_bytes(int N, int F, int L, int D);
 int amds_gated_attn_pool_unfused(const float* x, const amds_gap_weights* w_host, float* out, float* attn_raw,
                                  int N, int F, int L, int D, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_gated_attn_pool_unfused_workspace_bytes) is written. */
 
 /* EAGLE's tile selection (reference src/stamp/encoding/encoder/eagle.py:106-118: `torch.topk(attention_raw, min(25, N))`, then the mean of
  * the matching rows of the aggregation features): idx_out[r], r < k, = index of the r-th largest score (ties: the lower index first),
@@ -711,6 +738,8 @@ int amds_topk_rows_mean(const float* score, int n, int k, const void* rows, long
 size_t amds_proj_head_l2norm_workspace_bytes(int rows, int in_dim, int proj_dim);
 int amds_proj_head_l2norm(const void* feats, int feats_dtype, const float* w1, const float* b1, const float* w2, const float* b2, float* out, int rows,
                           int in_dim, int proj_dim, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_proj_head_l2norm_workspace_bytes) is written. */
 
 /* ------------------------------------------------------------------------------------------------
  * Small rows of the MIL path
@@ -783,6 +812,8 @@ size_t amds_mil_vit_workspace_bytes(const amds_mil_vit_cfg* cfg_host, int n_bags
 int amds_mil_vit_forward(const amds_mil_vit_cfg* cfg_host, const amds_mil_vit_weights* w_host, const void* bags, int bags_dtype,
                          const float* coords, const uint8_t* mask, float* logits, int n_bags, int n_tiles, void* ws, size_t ws_bytes,
                          void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_mil_vit_workspace_bytes) is written. */
 
 /* ---- ragged bags: the same inference forward over bags of DIFFERENT lengths packed without padding, one call --------------------------------------------
  * The reference validates and deploys one bag per call (src/stamp/modeling/train.py:467-477: `bag_size=None`, `batch_size=1`; deploy.py:390-456); its
@@ -803,6 +834,8 @@ size_t amds_mil_vit_ragged_workspace_bytes(const amds_mil_vit_cfg* cfg_host, int
 int amds_mil_vit_forward_ragged(const amds_mil_vit_cfg* cfg_host, const amds_mil_vit_weights* w_host, const void* feats, int feats_dtype,
                                 const float* coords, const int* offsets, float* logits, int n_bags, long total_tiles, int max_tiles, void* ws, size_t ws_bytes,
                                 void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_mil_vit_ragged_workspace_bytes) is written. */
 /* The largest tile count a bag may have and still share a ragged call with other bags bit-identically (32767 at most; -1 on a bad cfg).  Host-side, no launch. */
 int amds_mil_vit_ragged_max_shared_tiles(const amds_mil_vit_cfg* cfg_host);
 /* The attention of the ragged layout on its own, equal under each bag's slice to the fixed-pitch entry on that bag (amds_attention, amds_attention_alibi,
@@ -813,10 +846,16 @@ int amds_mil_vit_ragged_max_shared_tiles(const amds_mil_vit_cfg* cfg_host);
 size_t amds_attention_varlen_workspace_bytes(int n_bags, long total_tiles);
 int amds_attention_varlen(const void* qkv, const int* offsets, void* out, int n_bags, long total_tiles, int max_tiles, int H, int dtype, void* ws,
                           size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_attention_varlen_workspace_bytes) is written. */
 int amds_attention_alibi_varlen(const void* qkv, const float* coords, const float* head_scale, const int* offsets, void* out, int n_bags, long total_tiles,
                                 int max_tiles, int H, int dtype, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_attention_varlen_workspace_bytes) is written. */
 int amds_attention_row_varlen(const void* q, long ldq, const void* qkv, const int* offsets, void* out, long ldo, int n_bags, long total_tiles, int max_tiles,
                               int H, int dtype, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_attention_varlen_workspace_bytes) is written. */
 
 /* The TRAINING step of the same head, forward and backward as one call each (reference: the train-mode forward of
  * vision_tranformer.py:332-384 with its Dropout sites :157-169, :191, :314-318 live, and loss.backward() through it,
@@ -867,6 +906,8 @@ int amds_mil_vit_train_forward(const amds_mil_vit_cfg* cfg_host, const amds_mil_
 int amds_mil_vit_train_backward(const amds_mil_vit_cfg* cfg_host, const amds_mil_vit_weights* w_host, const float* dlogits,
                                 const amds_mil_vit_dropout* drop_host, int n_bags, int n_tiles, const void* saved, size_t saved_bytes,
                                 const amds_mil_vit_grads* grads_host, float* dbags, int split_k, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_mil_vit_train_workspace_bytes) is written. */
 
 /* Grad-CAM scores of every tile for every class from ONE call (reference src/stamp/heatmaps/__init__.py: `_gradcam_per_category` :36-56 up to and including
  * line 54, `_gradcam_single` :115-139 line 137; the reference builds the [classes][tiles][n_feats] Jacobian with torch.func.jacrev and reduces it):
@@ -882,6 +923,8 @@ int amds_mil_vit_train_backward(const amds_mil_vit_cfg* cfg_host, const amds_mil
 size_t amds_mil_vit_gradcam_workspace_bytes(const amds_mil_vit_cfg* cfg_host, int n_bags, int n_tiles);
 int amds_mil_vit_gradcam(const amds_mil_vit_cfg* cfg_host, const amds_mil_vit_weights* w_host, const amds_mil_vit_dropout* drop_host, int n_bags, int n_tiles,
                          const void* saved, size_t saved_bytes, float scale, float* cam_raw, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_mil_vit_gradcam_workspace_bytes) is written. */
 
 /* out[t][c] = softmax over t of in[c][t]: fp32 [classes][n] -> fp32 [n][classes] (reference src/stamp/heatmaps/__init__.py:55-56: `torch.softmax(cam, dim=-1)`
  * then `permute(-1, -2)`).  One workgroup per class; maximum and sum over the n tiles by fixed-order reductions (no float atomics): deterministic.
@@ -940,6 +983,8 @@ size_t amds_barspoon_workspace_bytes(const amds_barspoon_cfg* cfg_host, int n_ba
  * logits fp32 [n_bags][sum_t n_out_t], target t at column offset sum_{s<t} n_out_s.  Launches only, on `stream`; ws 256-byte aligned. */
 int amds_barspoon_forward(const amds_barspoon_cfg* cfg_host, const amds_barspoon_weights* w_host, const void* bags, int bags_dtype,
                           const float* positions, float* logits, int n_bags, int n_tiles, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_barspoon_workspace_bytes) is written. */
 
 /* ------------------------------------------------------------------------------------------------
  * TransMIL building blocks (reference src/stamp/modeling/models/trans_mil.py), fp32 throughout
@@ -1022,6 +1067,8 @@ size_t amds_transmil_workspace_bytes(const amds_transmil_cfg* cfg_host, int n_ba
  * [n_bags][classes].  Launches only, on `stream`; ws 256-byte aligned. */
 int amds_transmil_forward(const amds_transmil_cfg* cfg_host, const amds_transmil_weights* w_host, const void* bags, int bags_dtype, float* logits,
                           int n_bags, int n_tiles, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_transmil_workspace_bytes) is written. */
 
 /* The same forward over RAGGED bags: n_bags bags of different tile counts packed without padding, one call, every bag computed as the reference computes it
  * at batch 1 (validation and deploy: modeling/train.py:467-477 `bag_size=None, batch_size=1`; deploy.py:390-456).  Per bag of T tiles (m = dim / 2):
@@ -1050,6 +1097,8 @@ int amds_transmil_ragged_plan(const amds_transmil_cfg* cfg_host, int n_bags, con
 size_t amds_transmil_ragged_workspace_bytes(const amds_transmil_cfg* cfg_host, int n_bags, const int* tiles_host);
 int amds_transmil_forward_ragged(const amds_transmil_cfg* cfg_host, const amds_transmil_weights* w_host, const void* feats, int feats_dtype, const int* tiles_host,
                                  const amds_transmil_bag* table_dev, float* logits, int n_bags, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_transmil_ragged_workspace_bytes) is written. */
 
 /* One TransMIL layer's attention in TRAINING, forward and backward as one call each (reference trans_mil.py:81-163 with mask = None, the
  * residual of :263, `to_out`'s Dropout(0.1) of :66 live when p_drop > 0; loss.backward() through it, models/__init__.py:239-279):
@@ -1070,6 +1119,8 @@ int amds_nystrom_attn_fwd(const amds_transmil_layer* w_host, int dim, const floa
 int amds_nystrom_attn_bwd(const amds_transmil_layer* w_host, int dim, const float* dx, float* dy, const amds_nystrom_grads* grads_host, int n_bags,
                           int n_tokens, float p_drop, uint64_t seed, uint32_t stream_id, const void* saved, size_t saved_bytes, void* ws,
                           size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_nystrom_attn_workspace_bytes) is written. */
 
 /* The whole TransMIL TRAINING step's forward and backward, one call each: the loop around amds_nystrom_attn_fwd / _bwd (reference
  * trans_mil.py:299-325 in train mode -- Dropout(0.1) on both `to_out`s, dropout sites 1 and 2 of `seed` -- and loss.backward() through it).
@@ -1090,6 +1141,8 @@ int amds_transmil_train_forward(const amds_transmil_cfg* cfg_host, const amds_tr
 int amds_transmil_train_backward(const amds_transmil_cfg* cfg_host, const amds_transmil_weights* w_host, const float* dlogits, float p_drop, uint64_t seed,
                                  int n_bags, int n_tiles, const void* saved, size_t saved_bytes, const amds_transmil_grads* grads_host, float* dbags, void* ws,
                                  size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_transmil_train_workspace_bytes) is written. */
 
 /* Backward pieces of the TransMIL head (training: the reference differentiates trans_mil.py with autograd inside
  * LitTileClassifier._step, src/stamp/modeling/models/__init__.py:239-279); fp32 like the forward.  The matrix products of the
@@ -1110,11 +1163,17 @@ int amds_landmark_mean_bwd(const float* dout, float* dx, long sxo, long sxi, int
 size_t amds_dwconv_seq_wgrad_workspace_bytes(int outer, int inner, int taps);
 int amds_dwconv_seq_wgrad(const float* dout, long soo, long soi, int ldo, const float* v, long svo, long svi, int ldv, float* dw,
                           int outer, int inner, int n, int d, int taps, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_dwconv_seq_wgrad_workspace_bytes) is written. */
 size_t amds_ppeg_wgrad_workspace_bytes(int B, int C);
 int amds_ppeg_wgrad(const float* x, const float* dy, float* dcorr, int B, int H, int W, int C, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_ppeg_wgrad_workspace_bytes) is written. */
 int amds_relu_bwd(const float* h, const float* dh, float* dz, long n, void* stream);
 size_t amds_pinv_init_bwd_workspace_bytes(int nmat);
 int amds_pinv_init_bwd(const float* x, const float* dz0, float* dx, int nmat, int n, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_pinv_init_bwd_workspace_bytes) is written. */
 
 /* ------------------------------------------------------------------------------------------------
  * MIL training step (reference src/stamp/modeling/models/__init__.py:133-141, 239-279): bf16 MFMA operands,
@@ -1150,6 +1209,8 @@ int amds_cast_transpose_multi(const amds_cast_entry* entries_host, int n, void* 
 /* out[n] (+)= sum_m x[m][n]; deterministic two-stage reduction (bias gradients, split-K partial sums). */
 size_t amds_colsum_workspace_bytes(int M, int N);
 int amds_colsum(const void* x, long ld, float* out, int M, int N, int in_dtype, int accumulate, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_colsum_workspace_bytes) is written. */
 /* out_i[e] = sum over s < rows of part_i[s * count_i + e], e < count_i, for up to 32 (part, out, count) triples in ONE launch, with the association of
  * amds_colsum(part_i, count_i, out_i, rows, count_i, AMDS_F32, ...) (same bits): the split-K partials of every weight gradient of a backward pass
  * (amds_wgrad_tn) summed behind the last of them instead of one reduction launch per matrix.  counts: multiples of 4; pointers 16-byte aligned. */
@@ -1182,6 +1243,8 @@ size_t amds_layernorm_bwd_workspace_bytes(int rows, int cols);
 int amds_layernorm_bwd(const float* dy, long dy_stride, const float* x, long x_stride, const float* mean, const float* rstd,
                        const float* gamma, float* dx, long dx_stride, int add_skip, float* dgamma, float* dbeta, int accumulate_params,
                        int rows, int cols, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_layernorm_bwd_workspace_bytes) is written. */
 /* Same, and dx (after the skip add) also goes out as bf16 rows into dx_bf16 -- the operand of the GEMMs that take dx next -- multiplied by the mask and
  * scale of dropout site (seed, stream_id) at rate p when p > 0 (the bits of amds_dropout_cast_bwd over a [rows][cols] tensor): the backward of
  * `x = x + Dropout(...)` / of a plain residual add without a separate cast pass over dx.  dx_bf16 may be NULL (= amds_layernorm_bwd). */
@@ -1189,6 +1252,8 @@ int amds_layernorm_bwd_cast(const float* dy, long dy_stride, const float* x, lon
                             const float* gamma, float* dx, long dx_stride, int add_skip, float* dgamma, float* dbeta, int accumulate_params,
                             int rows, int cols, void* ws, size_t ws_bytes, void* dx_bf16, long dx_bf16_stride, float p, uint64_t seed,
                             uint32_t stream_id, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_layernorm_bwd_workspace_bytes) is written. */
 /* amds_layernorm_bwd_cast without its two parameter-gradient reductions: the per-64-row partials go to dgamma_part / dbeta_part, fp32
  * [ceil(rows / 64)][cols] each, for the caller to sum when it likes (kind-0 entries of amds_colsum_multi: ceil(rows / 64) rows of `cols`). */
 int amds_layernorm_bwd_partials(const float* dy, long dy_stride, const float* x, long x_stride, const float* mean, const float* rstd,

@@ -587,7 +587,7 @@ def forward_train(pk: PackedVit, bags: torch.Tensor, coords: torch.Tensor | None
     need = lib.amds_mil_vit_train_saved_bytes(C.byref(cfg), Bb, Tn)
     if need == 0:
         _lib.check(-1, "mil_vit_train_saved_bytes")
-    arena = torch.empty(need, dtype=torch.uint8, device=dev)
+    arena = ops.alloc(need, torch.uint8, dev)
     logits = torch.empty(Bb, d.C, dtype=torch.float32, device=dev)
     drop = _drop_struct(d, training, seed, dev.index or 0)
     _lib.check(lib.amds_mil_vit_train_forward(C.byref(cfg), C.byref(wc), bags.data_ptr(), ops._DT[bags.dtype], c.data_ptr() if c is not None else None,
@@ -605,7 +605,7 @@ def _grad_buffers(d: VitDims, dev):
            ("fc2_b", (d.Dp,))]
     al = lambda n: (n + 63) // 64 * 64  # noqa: E731   (256-byte aligned sub-buffers)
     total = sum(al(math.prod(sh)) for _, sh in sizes) + d.L * sum(al(math.prod(sh)) for _, sh in per)
-    flat = torch.empty(total, dtype=torch.float32, device=dev)
+    flat = ops.alloc(total, torch.float32, dev)
     off = 0
 
     def view(sh):
@@ -682,7 +682,7 @@ def backward(pk: PackedVit, saved: dict, dlogits: torch.Tensor, *, need_params: 
         gc = direct[0]
     elif need_params:
         _flat, gc, _lg, top, layers = _grad_buffers(d, dev)
-    dbp = torch.empty(Bb * Tn, d.Fp, dtype=torch.float32, device=dev) if need_bags else None
+    dbp = ops.alloc((Bb * Tn, d.Fp), torch.float32, dev) if need_bags else None
     arena = saved["arena"]
     _lib.check(lib.amds_mil_vit_train_backward(C.byref(cfg), C.byref(wc), dlogits.data_ptr(), C.byref(saved["drop"]), Bb, Tn, arena.data_ptr(), arena.numel(),
                                                C.byref(gc) if gc is not None else None, dbp.data_ptr() if dbp is not None else None, split_k,

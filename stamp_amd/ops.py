@@ -39,6 +39,12 @@ def scratch(tag: str, dev: torch.device, nbytes: int) -> torch.Tensor:
     return ws
 
 
+def alloc(shape, dtype: torch.dtype, dev: torch.device) -> torch.Tensor:
+    """The buffers a whole-model wrapper hands the library besides `scratch` -- saved arenas, flat gradient buffers, d(bags): uninitialised device memory.
+    One module-level function, so that a test can hand out guarded, poisoned memory instead (tests/guarded.py)."""
+    return torch.empty(shape, dtype=dtype, device=dev)
+
+
 def _p(t: torch.Tensor | None) -> int | None:
     return None if t is None else t.data_ptr()
 

@@ -115,7 +115,7 @@ def nystrom_forward(y: torch.Tensor, P: _Nys, x_res: torch.Tensor, p_drop: float
     need = lib.amds_nystrom_attn_saved_bytes(Cd, b, n)
     if need == 0:
         _lib.check(-1, "nystrom_attn_saved_bytes")
-    arena = torch.empty(need, dtype=torch.uint8, device=y.device)
+    arena = ops.alloc(need, torch.uint8, y.device)
     L = _layer_struct(P)
     ops.sync_float32_matmul_precision()
     _lib.check(lib.amds_nystrom_attn_fwd(C.byref(L), Cd, y.data_ptr(), x_res.data_ptr(), b, n, float(p_drop), int(seed) & (2 ** 64 - 1), int(sid),
@@ -192,7 +192,7 @@ def forward_train(get, bags: torch.Tensor, dims: tuple[int, int, int], *, traini
     need = lib.amds_transmil_train_saved_bytes(C.byref(cfg), Bb, Tn)
     if need == 0:
         _lib.check(-1, "transmil_train_saved_bytes")
-    arena = torch.empty(need, dtype=torch.uint8, device=dev)
+    arena = ops.alloc(need, torch.uint8, dev)
     logits = torch.empty(Bb, Cc, dtype=torch.float32, device=dev)
     p_out = P_OUT if training else 0.0
     ops.sync_float32_matmul_precision()
