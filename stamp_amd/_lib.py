@@ -412,6 +412,14 @@ def ctx(device: int = 0) -> int:
     return _ctx[device]
 
 
+def ctx_of(device=None) -> int:
+    """The library context of `device`: a torch.device, a device index or None.  None and a CUDA device without an index mean torch's
+    current device (not device 0)."""
+    import torch
+    index = getattr(device, "index", device)
+    return ctx(torch.cuda.current_device() if index is None else int(index))
+
+
 def destroy_contexts() -> None:
     for h in _ctx.values():
         lib().amds_destroy(h)

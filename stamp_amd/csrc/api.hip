@@ -39,7 +39,7 @@ struct amds_ctx {
 namespace amds {
 std::atomic<int> g_prof_any{0};
 namespace {
-constexpr int MAX_DEV = 64, PROF_MAX = 1 << 15;
+constexpr int PROF_MAX = 1 << 15;
 amds_ctx* g_ctx[MAX_DEV] = {};
 std::mutex g_tab;
 amds_ctx* current_ctx() {

@@ -9,7 +9,8 @@
 // rules: S^T = K Q^T keeps a query's scores in one lane, the key order inside 16-key groups is such that P is
 // already the MFMA B operand).  Scores never leave registers: N^2 is never materialised, K/V are re-read once per
 // 128-query block (L2-resident: 2 x T x 128 B per head).
-#include "common.h"
+#include <optional>
+#include "launch.h"
 
 namespace amds {
 
@@ -727,47 +728,78 @@ int varlen_table_build(const int* offsets, int n_bags, long total_tiles, int max
     return AMDS_OK;
 }
 
+// ---- launchers --------------------------------------------------------------------------------------------------------------------------------------------------
+// The optional arguments of attn_flash_kernel; an entry names those of its variant and leaves the rest off.
+struct FlashOpt {
+    const float* coords = nullptr;          // ALIBI: token coordinates and the per-head factor of the distance (1 / running mean; inference: bias scale folded in)
+    const float* head_scale = nullptr;
+    float* lse = nullptr;                   // training: log-sum-exp per query
+    const float* bias_scale = nullptr;      // ALiBi training: out = Osm - bias_scale U, both saved
+    void* u = nullptr;
+    void* osm = nullptr;
+    const uint8_t* pad = nullptr;           // MASK
+    int mask_heads = 0;
+    float p = 0.f;                          // DROP
+    uint64_t seed = 0;
+    uint32_t stream_id = 0;
+    const int4* vwork = nullptr;            // VARLEN: the work list and its length (the grid's x; T is then unused)
+    unsigned n_work = 0;
+};
+
+// One launch of the streaming kernel: grid, profiler scope and the dtype ladder.  The variant is the entry's (template flags), the operand type the call's;
+// OUT_AS_IN = false: bf16 out / U / Osm whatever the operands (the ALiBi forms, see the kernel comment).  `who` names the entry in the dtype message.
+template <bool ALIBI, bool MASK = false, bool DROP = false, bool VARLEN = false, bool OUT_AS_IN = !ALIBI>
+static int flash_launch(const char* who, const char* kname, const void* qkv, void* out, int B, int T, int H, int dtype, const FlashOpt& o, hipStream_t st) {
+    const dim3 grid(VARLEN ? o.n_work : (unsigned)((T + 127) / 128), H, B), block(256);
+    std::optional<ProfScope> prof;          // (the ragged forms are timed by their callers)
+    if constexpr (!VARLEN) prof.emplace(PROF_ATTN, (ALIBI ? 6.0 : 4.0) * B * H * (double)T * T * 64, st);
+    const DropParams d(o.p);
+    const bool ok = dispatch_16(dtype, [&](auto t) {
+        typedef AMDS_TAG_T(t) TI;
+        typedef std::conditional_t<OUT_AS_IN, TI, bf16> TO;
+        hipLaunchKernelGGL((attn_flash_kernel<TI, ALIBI, TO, MASK, DROP, VARLEN>), grid, block, 0, st, (const TI*)qkv, (TO*)out, T, H, o.coords, o.head_scale, o.lse,
+                           o.bias_scale, (TO*)o.u, (TO*)o.osm, o.pad, o.seed, o.stream_id, d.thr, d.scale, o.mask_heads, o.vwork);
+    });
+    if (!ok) { set_error("%s: bad dtype %d", who, dtype); return AMDS_ERR_INVALID; }
+    AMDS_LAUNCH_CHECK(kname);
+    return AMDS_OK;
+}
+
 int attention_varlen_launch(const void* qkv, const float* coords, const float* head_scale, void* out, const void* table, int n_bags, long total_tiles,
                             int H, int dtype, hipStream_t st) {
-    const int4* work = reinterpret_cast<const int4*>(reinterpret_cast<const char*>(table) + al256((size_t)n_bags * 8));
-    const dim3 grid((unsigned)varlen_work_items(n_bags, total_tiles), H, 1), block(256);
-    if (coords) {
-        if (dtype == AMDS_F16)
-            hipLaunchKernelGGL((attn_flash_kernel<f16, true, bf16, false, false, true>), grid, block, 0, st, (const f16*)qkv, (bf16*)out, 0, H, coords, head_scale,
-                               nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 1.f, 0, work);
-        else
-            hipLaunchKernelGGL((attn_flash_kernel<bf16, true, bf16, false, false, true>), grid, block, 0, st, (const bf16*)qkv, (bf16*)out, 0, H, coords, head_scale,
-                               nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 1.f, 0, work);
-        AMDS_LAUNCH_CHECK("attn_flash_kernel<alibi, varlen>");
-    } else {
-        if (dtype == AMDS_F16)
-            hipLaunchKernelGGL((attn_flash_kernel<f16, false, f16, false, false, true>), grid, block, 0, st, (const f16*)qkv, (f16*)out, 0, H, nullptr, nullptr,
-                               nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 1.f, 0, work);
-        else
-            hipLaunchKernelGGL((attn_flash_kernel<bf16, false, bf16, false, false, true>), grid, block, 0, st, (const bf16*)qkv, (bf16*)out, 0, H, nullptr, nullptr,
-                               nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 1.f, 0, work);
-        AMDS_LAUNCH_CHECK("attn_flash_kernel<varlen>");
-    }
-    return AMDS_OK;
+    FlashOpt o;
+    o.vwork = reinterpret_cast<const int4*>(reinterpret_cast<const char*>(table) + al256((size_t)n_bags * 8));
+    o.n_work = (unsigned)varlen_work_items(n_bags, total_tiles);
+    o.coords = coords;
+    o.head_scale = head_scale;
+    if (coords) return flash_launch<true, false, false, true>("attention_varlen_launch", "attn_flash_kernel<alibi, varlen>", qkv, out, 1, 0, H, dtype, o, st);
+    return flash_launch<false, false, false, true>("attention_varlen_launch", "attn_flash_kernel<varlen>", qkv, out, 1, 0, H, dtype, o, st);
+}
+
+// One launch of the one-query kernel (q rows at pitch ldq from element q_off, out rows at pitch ldo from element o_off, one per bag);
+// LDS: [T] weights | [16][64] partial sums | [8] reductions
+template <bool DROP, bool VARLEN = false>
+static int row_launch(const char* who, const char* kname, const void* q, long q_off, long ldq, const void* qkv, void* out, long o_off, long ldo, int B, int T, int H,
+                      int dtype, float* lse, int qrow, float p, uint64_t seed, uint32_t stream_id, const int2* bags, hipStream_t st) {
+    const size_t lds = ((size_t)((T + 3) & ~3) + 16 * 64 + 8) * 4;
+    const DropParams d(p);
+    int rc = AMDS_OK;
+    const bool ok = dispatch_16(dtype, &rc, [&](auto t) -> int {
+        typedef AMDS_TAG_T(t) TT;
+        AMDS_HIP(lds_opt_in<attn_row_kernel<TT, DROP, VARLEN>>(140 * 1024));
+        hipLaunchKernelGGL((attn_row_kernel<TT, DROP, VARLEN>), dim3(H, B), dim3(256), lds, st, (const TT*)q + q_off, ldq, (const TT*)qkv, (TT*)out + o_off, ldo, T, H, lse,
+                           qrow, seed, stream_id, d.thr, d.scale, bags);
+        AMDS_LAUNCH_CHECK(kname);
+        return AMDS_OK;
+    });
+    if (!ok) { set_error("%s: bad dtype %d", who, dtype); return AMDS_ERR_INVALID; }
+    return rc;
 }
 
 int attention_row_varlen_launch(const void* q, long ldq, const void* qkv, void* out, long ldo, const void* table, int n_bags, int max_tiles, int H, int dtype,
                                 hipStream_t st) {
-    const int T = max_tiles + 1;
-    const size_t lds = ((size_t)((T + 3) & ~3) + 16 * 64 + 8) * 4;
-    const int2* bags = varlen_table_bags(table);
-    static bool attr_set[2] = {false, false};
-    if (dtype == AMDS_F16) {
-        if (!attr_set[0]) { AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_row_kernel<f16, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024)); attr_set[0] = true; }
-        hipLaunchKernelGGL((attn_row_kernel<f16, false, true>), dim3(H, n_bags), dim3(256), lds, st, (const f16*)q, ldq, (const f16*)qkv, (f16*)out, ldo, T, H,
-                           nullptr, 0, 0, 0, 0, 1.f, bags);
-    } else {
-        if (!attr_set[1]) { AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_row_kernel<bf16, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024)); attr_set[1] = true; }
-        hipLaunchKernelGGL((attn_row_kernel<bf16, false, true>), dim3(H, n_bags), dim3(256), lds, st, (const bf16*)q, ldq, (const bf16*)qkv, (bf16*)out, ldo, T, H,
-                           nullptr, 0, 0, 0, 0, 1.f, bags);
-    }
-    AMDS_LAUNCH_CHECK("attn_row_kernel<varlen>");
-    return AMDS_OK;
+    return row_launch<false, true>("attention_row_varlen_launch", "attn_row_kernel<varlen>", q, 0, ldq, qkv, out, 0, ldo, n_bags, max_tiles + 1, H, dtype, nullptr, 0, 0.f, 0,
+                                   0, varlen_table_bags(table), st);
 }
 
 }  // namespace amds
@@ -778,34 +810,14 @@ extern "C" int amds_attention(const void* qkv, void* out, int B, int T, int H, i
     AMDS_REQUIRE(qkv && out, "amds_attention: null pointer");
     AMDS_REQUIRE(B >= 0 && T > 0 && H > 0 && H <= 65535 && B <= 65535 && FA_SPAN_OK(T, H), "amds_attention: bad shape B=%d T=%d H=%d", B, T, H);
     if (B == 0) return AMDS_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((T + 127) / 128, H, B), block(256);
-    ProfScope prof(PROF_ATTN, 4.0 * B * H * (double)T * T * 64, st);
-    if (dtype == AMDS_F16) hipLaunchKernelGGL((attn_flash_kernel<f16, false>), grid, block, 0, st, (const f16*)qkv, (f16*)out, T, H, nullptr, nullptr, nullptr);
-    else if (dtype == AMDS_BF16) hipLaunchKernelGGL((attn_flash_kernel<bf16, false>), grid, block, 0, st, (const bf16*)qkv, (bf16*)out, T, H, nullptr, nullptr, nullptr);
-    else { set_error("amds_attention: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
-    AMDS_LAUNCH_CHECK("attn_flash_kernel");
-    return AMDS_OK;
+    return flash_launch<false>("amds_attention", "attn_flash_kernel", qkv, out, B, T, H, dtype, FlashOpt{}, (hipStream_t)stream);
 }
 
 extern "C" int amds_attention_row(const void* q, long ldq, const void* qkv, void* out, long ldo, int B, int T, int H, int dtype, void* stream) {
     AMDS_REQUIRE(q && qkv && out, "amds_attention_row: null pointer");
     AMDS_REQUIRE(B >= 0 && T > 0 && T <= 32768 && H > 0 && H <= 65535 && B <= 65535 && ldq >= H * 64 && ldo >= H * 64 && ldq % 8 == 0, "amds_attention_row: bad shape B=%d T=%d H=%d", B, T, H);
     if (B == 0) return AMDS_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = ((size_t)((T + 3) & ~3) + 16 * 64 + 8) * 4;
-    static bool attr_set[2] = {false, false};
-    const int ti = dtype == AMDS_F16 ? 0 : 1;
-    if (dtype != AMDS_F16 && dtype != AMDS_BF16) { set_error("amds_attention_row: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
-    if (!attr_set[ti]) {
-        if (ti == 0) AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_row_kernel<f16>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-        else AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_row_kernel<bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-        attr_set[ti] = true;
-    }
-    if (ti == 0) hipLaunchKernelGGL((attn_row_kernel<f16>), dim3(H, B), dim3(256), lds, st, (const f16*)q, ldq, (const f16*)qkv, (f16*)out, ldo, T, H);
-    else hipLaunchKernelGGL((attn_row_kernel<bf16>), dim3(H, B), dim3(256), lds, st, (const bf16*)q, ldq, (const bf16*)qkv, (bf16*)out, ldo, T, H);
-    AMDS_LAUNCH_CHECK("attn_row_kernel");
-    return AMDS_OK;
+    return row_launch<false>("amds_attention_row", "attn_row_kernel", q, 0, ldq, qkv, out, 0, ldo, B, T, H, dtype, nullptr, 0, 0.f, 0, 0, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int amds_attention_row_fwd_train(const void* qkv, void* out, float* lse, int B, int T, int H, int qrow, int dtype, float p, uint64_t seed,
@@ -815,23 +827,11 @@ extern "C" int amds_attention_row_fwd_train(const void* qkv, void* out, float* l
                  "amds_attention_row_fwd_train: bad arguments B=%d T=%d H=%d row=%d p=%f", B, T, H, qrow, p);
     AMDS_REQUIRE(dtype == AMDS_F16 || dtype == AMDS_BF16, "amds_attention_row_fwd_train: bad dtype %d", dtype);
     if (B == 0) return AMDS_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = ((size_t)((T + 3) & ~3) + 16 * 64 + 8) * 4;
     const long Dm = (long)H * 64, ldq = (long)T * 3 * Dm, ldo = (long)T * Dm;
-    const uint32_t thr = p > 0.f ? drop_thr16(p) : 0;
-    const float ks = p > 0.f ? drop_scale(thr) : 1.f;
-    static bool attr[4] = {false, false, false, false};
-#define AMDS_ROW_FWD(TT, DR, IDX)                                                                                                                         \
-    do {                                                                                                                                                  \
-        if (!attr[IDX]) { AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_row_kernel<TT, DR>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024)); attr[IDX] = true; } \
-        hipLaunchKernelGGL((attn_row_kernel<TT, DR>), dim3(H, B), dim3(256), lds, st, (const TT*)qkv + (long)qrow * 3 * Dm, ldq, (const TT*)qkv,          \
-                           (TT*)out + (long)qrow * Dm, ldo, T, H, lse, qrow, seed, stream_id, thr, ks);                                                   \
-    } while (0)
-    if (dtype == AMDS_F16) { if (p > 0.f) AMDS_ROW_FWD(f16, true, 0); else AMDS_ROW_FWD(f16, false, 1); }
-    else { if (p > 0.f) AMDS_ROW_FWD(bf16, true, 2); else AMDS_ROW_FWD(bf16, false, 3); }
-#undef AMDS_ROW_FWD
-    AMDS_LAUNCH_CHECK("attn_row_kernel<train>");
-    return AMDS_OK;
+    const long q_off = (long)qrow * 3 * Dm, o_off = (long)qrow * Dm;      // the query row and its output row inside the [B][T] tensors
+    const char *who = "amds_attention_row_fwd_train", *kname = "attn_row_kernel<train>";
+    if (p > 0.f) return row_launch<true>(who, kname, qkv, q_off, ldq, qkv, out, o_off, ldo, B, T, H, dtype, lse, qrow, p, seed, stream_id, nullptr, (hipStream_t)stream);
+    return row_launch<false>(who, kname, qkv, q_off, ldq, qkv, out, o_off, ldo, B, T, H, dtype, lse, qrow, 0.f, seed, stream_id, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int amds_attention_row_bwd_train(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int T, int H, int qrow,
@@ -843,20 +843,19 @@ extern "C" int amds_attention_row_bwd_train(const void* qkv, const void* out, co
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = ((size_t)((T + 3) & ~3) + 16 * 64) * 4;
     const long Dm = (long)H * 64, ldo = (long)T * Dm;
-    const uint32_t thr = p > 0.f ? drop_thr16(p) : 0;
-    const float ks = p > 0.f ? drop_scale(thr) : 1.f;
-    static bool attr[4] = {false, false, false, false};
-#define AMDS_ROW_BWD(TT, DR, IDX)                                                                                                                         \
-    do {                                                                                                                                                  \
-        if (!attr[IDX]) { AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_row_bwd_kernel<TT, DR>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024)); attr[IDX] = true; } \
-        hipLaunchKernelGGL((attn_row_bwd_kernel<TT, DR>), dim3(H, B), dim3(256), lds, st, (const TT*)qkv, (const TT*)out + (long)qrow * Dm, ldo,          \
-                           (const TT*)dout + (long)qrow * Dm, ldo, lse, (TT*)dqkv, T, H, qrow, seed, stream_id, thr, ks);                                 \
-    } while (0)
-    if (dtype == AMDS_F16) { if (p > 0.f) AMDS_ROW_BWD(f16, true, 0); else AMDS_ROW_BWD(f16, false, 1); }
-    else { if (p > 0.f) AMDS_ROW_BWD(bf16, true, 2); else AMDS_ROW_BWD(bf16, false, 3); }
-#undef AMDS_ROW_BWD
-    AMDS_LAUNCH_CHECK("attn_row_bwd_kernel");
-    return AMDS_OK;
+    const DropParams d(p);
+    auto launch = [&](auto t, auto drop) -> int {
+        typedef AMDS_TAG_T(t) TT;
+        constexpr bool DR = decltype(drop)::value;
+        AMDS_HIP(lds_opt_in<attn_row_bwd_kernel<TT, DR>>(140 * 1024));
+        hipLaunchKernelGGL((attn_row_bwd_kernel<TT, DR>), dim3(H, B), dim3(256), lds, st, (const TT*)qkv, (const TT*)out + (long)qrow * Dm, ldo,
+                           (const TT*)dout + (long)qrow * Dm, ldo, lse, (TT*)dqkv, T, H, qrow, seed, stream_id, d.thr, d.scale);
+        AMDS_LAUNCH_CHECK("attn_row_bwd_kernel");
+        return AMDS_OK;
+    };
+    int rc = AMDS_OK;                                                    // the dtype was checked above: the ladder cannot come back false
+    dispatch_16(dtype, &rc, [&](auto t) { return p > 0.f ? launch(t, std::true_type{}) : launch(t, std::false_type{}); });
+    return rc;
 }
 
 extern "C" int amds_attention_row_alibi_fwd_train(const void* qkv, const float* coords, const float* inv_running_mean, const float* bias_scale, void* out, void* u,
@@ -868,16 +867,15 @@ extern "C" int amds_attention_row_alibi_fwd_train(const void* qkv, const float* 
     if (B == 0) return AMDS_OK;
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = ((size_t)2 * ((T + 3) & ~3) + 2 * 16 * 64 + 8) * 4;
-    static bool attr[2] = {false, false};
-    if (dtype == AMDS_F16) {
-        if (!attr[0]) { AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_row_alibi_kernel<f16>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024)); attr[0] = true; }
-        hipLaunchKernelGGL((attn_row_alibi_kernel<f16>), dim3(H, B), dim3(256), lds, st, (const f16*)qkv, coords, inv_running_mean, bias_scale, (f16*)out, (f16*)u, (f16*)osm, lse, T, H, qrow);
-    } else {
-        if (!attr[1]) { AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_row_alibi_kernel<bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024)); attr[1] = true; }
-        hipLaunchKernelGGL((attn_row_alibi_kernel<bf16>), dim3(H, B), dim3(256), lds, st, (const bf16*)qkv, coords, inv_running_mean, bias_scale, (bf16*)out, (bf16*)u, (bf16*)osm, lse, T, H, qrow);
-    }
-    AMDS_LAUNCH_CHECK("attn_row_alibi_kernel");
-    return AMDS_OK;
+    int rc = AMDS_OK;                                                    // the dtype was checked above: the ladder cannot come back false
+    dispatch_16(dtype, &rc, [&](auto t) -> int {
+        typedef AMDS_TAG_T(t) TT;
+        AMDS_HIP(lds_opt_in<attn_row_alibi_kernel<TT>>(140 * 1024));
+        hipLaunchKernelGGL((attn_row_alibi_kernel<TT>), dim3(H, B), dim3(256), lds, st, (const TT*)qkv, coords, inv_running_mean, bias_scale, (TT*)out, (TT*)u, (TT*)osm, lse, T, H, qrow);
+        AMDS_LAUNCH_CHECK("attn_row_alibi_kernel");
+        return AMDS_OK;
+    });
+    return rc;
 }
 
 extern "C" int amds_attention_row_alibi_bwd_train(const void* qkv, const void* osm, const void* u, const void* dout, const float* lse, const float* coords,
@@ -889,18 +887,16 @@ extern "C" int amds_attention_row_alibi_bwd_train(const void* qkv, const void* o
     AMDS_REQUIRE(dtype == AMDS_F16 || dtype == AMDS_BF16, "amds_attention_row_alibi_bwd_train: bad dtype %d", dtype);
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = ((size_t)((T + 3) & ~3) + 16 * 64) * 4;
-    static bool attr[2] = {false, false};
-    if (dtype == AMDS_F16) {
-        if (!attr[0]) { AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_row_alibi_bwd_kernel<f16>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024)); attr[0] = true; }
-        hipLaunchKernelGGL((attn_row_alibi_bwd_kernel<f16>), dim3(H, B), dim3(256), lds, st, (const f16*)qkv, (const f16*)osm, (const f16*)u, (const f16*)dout, lse, coords, bias_scale,
-                           inv_running_mean, (f16*)dqkv, dbs, T, H, qrow);
-    } else {
-        if (!attr[1]) { AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_row_alibi_bwd_kernel<bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024)); attr[1] = true; }
-        hipLaunchKernelGGL((attn_row_alibi_bwd_kernel<bf16>), dim3(H, B), dim3(256), lds, st, (const bf16*)qkv, (const bf16*)osm, (const bf16*)u, (const bf16*)dout, lse, coords,
-                           bias_scale, inv_running_mean, (bf16*)dqkv, dbs, T, H, qrow);
-    }
-    AMDS_LAUNCH_CHECK("attn_row_alibi_bwd_kernel");
-    return AMDS_OK;
+    int rc = AMDS_OK;                                                    // the dtype was checked above: the ladder cannot come back false
+    dispatch_16(dtype, &rc, [&](auto t) -> int {
+        typedef AMDS_TAG_T(t) TT;
+        AMDS_HIP(lds_opt_in<attn_row_alibi_bwd_kernel<TT>>(140 * 1024));
+        hipLaunchKernelGGL((attn_row_alibi_bwd_kernel<TT>), dim3(H, B), dim3(256), lds, st, (const TT*)qkv, (const TT*)osm, (const TT*)u, (const TT*)dout, lse, coords, bias_scale,
+                           inv_running_mean, (TT*)dqkv, dbs, T, H, qrow);
+        AMDS_LAUNCH_CHECK("attn_row_alibi_bwd_kernel");
+        return AMDS_OK;
+    });
+    return rc;
 }
 
 extern "C" int amds_attention_alibi(const void* qkv, const float* coords, const float* head_scale, void* out, int B, int T,
@@ -908,14 +904,10 @@ extern "C" int amds_attention_alibi(const void* qkv, const float* coords, const 
     AMDS_REQUIRE(qkv && out && coords && head_scale, "amds_attention_alibi: null pointer");
     AMDS_REQUIRE(B >= 0 && T > 0 && H > 0 && H <= 65535 && B <= 65535 && FA_SPAN_OK(T, H), "amds_attention_alibi: bad shape B=%d T=%d H=%d", B, T, H);
     if (B == 0) return AMDS_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((T + 127) / 128, H, B), block(256);
-    ProfScope prof(PROF_ATTN, 6.0 * B * H * (double)T * T * 64, st);
-    if (dtype == AMDS_F16) hipLaunchKernelGGL((attn_flash_kernel<f16, true, bf16>), grid, block, 0, st, (const f16*)qkv, (bf16*)out, T, H, coords, head_scale, nullptr);
-    else if (dtype == AMDS_BF16) hipLaunchKernelGGL((attn_flash_kernel<bf16, true, bf16>), grid, block, 0, st, (const bf16*)qkv, (bf16*)out, T, H, coords, head_scale, nullptr);
-    else { set_error("amds_attention_alibi: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
-    AMDS_LAUNCH_CHECK("attn_flash_kernel<alibi>");
-    return AMDS_OK;
+    FlashOpt o;
+    o.coords = coords;
+    o.head_scale = head_scale;
+    return flash_launch<true>("amds_attention_alibi", "attn_flash_kernel<alibi>", qkv, out, B, T, H, dtype, o, (hipStream_t)stream);
 }
 
 // forward that also stores L[b][h][q] = log2(sum_k exp2(s_qk * log2(e)/8)) for amds_attention_bwd
@@ -923,47 +915,38 @@ extern "C" int amds_attention_fwd_lse(const void* qkv, void* out, float* lse, in
     AMDS_REQUIRE(qkv && out && lse, "amds_attention_fwd_lse: null pointer");
     AMDS_REQUIRE(B >= 0 && T > 0 && H > 0 && H <= 65535 && B <= 65535 && FA_SPAN_OK(T, H), "amds_attention_fwd_lse: bad shape B=%d T=%d H=%d", B, T, H);
     if (B == 0) return AMDS_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((T + 127) / 128, H, B), block(256);
-    ProfScope prof(PROF_ATTN, 4.0 * B * H * (double)T * T * 64, st);
-    if (dtype == AMDS_F16) hipLaunchKernelGGL((attn_flash_kernel<f16, false>), grid, block, 0, st, (const f16*)qkv, (f16*)out, T, H, nullptr, nullptr, lse);
-    else if (dtype == AMDS_BF16) hipLaunchKernelGGL((attn_flash_kernel<bf16, false>), grid, block, 0, st, (const bf16*)qkv, (bf16*)out, T, H, nullptr, nullptr, lse);
-    else { set_error("amds_attention_fwd_lse: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
-    AMDS_LAUNCH_CHECK("attn_flash_kernel<lse>");
-    return AMDS_OK;
+    FlashOpt o;
+    o.lse = lse;
+    return flash_launch<false>("amds_attention_fwd_lse", "attn_flash_kernel<lse>", qkv, out, B, T, H, dtype, o, (hipStream_t)stream);
 }
 
 // Training forward of the ALiBi attention (reference vision_tranformer.py:42-74 in train mode): head_scale = 1 / running_mean
 // (already updated by the caller, :24-29), out = softmax(q k^T / 8) v - bias_scale_h * U with U = sum_k (dist / running_mean) v.
-// Saves what the backward needs: L = log2-sum-exp per query, U and the softmax part Osm (both bf16).
+// Saves what the backward needs: L = log2-sum-exp per query, U and the softmax part Osm -- all three bf16 from the C entry, in the operand type itself
+// (out_as_in) from the dtype-taking form at AMDS_F16: the training step at float32_matmul_precision "high".
+static int alibi_fwd_train(const void* qkv, const float* coords, const float* inv_running_mean, const float* bias_scale, void* out, void* u, void* osm, float* lse,
+                           int B, int T, int H, int dtype, bool out_as_in, void* stream) {
+    const char* who = "amds_attention_alibi_fwd_train";
+    AMDS_REQUIRE(qkv && coords && inv_running_mean && bias_scale && out && u && osm && lse, "%s: null pointer", who);
+    AMDS_REQUIRE(B >= 0 && T > 0 && H > 0 && H <= 65535 && B <= 65535 && FA_SPAN_OK(T, H), "%s: bad shape B=%d T=%d H=%d", who, B, T, H);
+    if (B == 0) return AMDS_OK;
+    FlashOpt o;
+    o.coords = coords;
+    o.head_scale = inv_running_mean;
+    o.lse = lse;
+    o.bias_scale = bias_scale;
+    o.u = u;
+    o.osm = osm;
+    if (out_as_in) return flash_launch<true, false, false, false, true>(who, "attn_flash_kernel<alibi,train,f16>", qkv, out, B, T, H, dtype, o, (hipStream_t)stream);
+    return flash_launch<true>(who, "attn_flash_kernel<alibi,train>", qkv, out, B, T, H, dtype, o, (hipStream_t)stream);
+}
 extern "C" int amds_attention_alibi_fwd_train(const void* qkv, const float* coords, const float* inv_running_mean, const float* bias_scale,
                                               void* out_bf16, void* u_bf16, void* osm_bf16, float* lse, int B, int T, int H, int dtype, void* stream) {
-    AMDS_REQUIRE(qkv && coords && inv_running_mean && bias_scale && out_bf16 && u_bf16 && osm_bf16 && lse, "amds_attention_alibi_fwd_train: null pointer");
-    AMDS_REQUIRE(B >= 0 && T > 0 && H > 0 && H <= 65535 && B <= 65535 && FA_SPAN_OK(T, H), "amds_attention_alibi_fwd_train: bad shape B=%d T=%d H=%d", B, T, H);
-    if (B == 0) return AMDS_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((T + 127) / 128, H, B), block(256);
-    ProfScope prof(PROF_ATTN, 6.0 * B * H * (double)T * T * 64, st);
-    if (dtype == AMDS_F16) hipLaunchKernelGGL((attn_flash_kernel<f16, true, bf16>), grid, block, 0, st, (const f16*)qkv, (bf16*)out_bf16, T, H, coords, inv_running_mean, lse, bias_scale, (bf16*)u_bf16, (bf16*)osm_bf16);
-    else if (dtype == AMDS_BF16) hipLaunchKernelGGL((attn_flash_kernel<bf16, true, bf16>), grid, block, 0, st, (const bf16*)qkv, (bf16*)out_bf16, T, H, coords, inv_running_mean, lse, bias_scale, (bf16*)u_bf16, (bf16*)osm_bf16);
-    else { set_error("amds_attention_alibi_fwd_train: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
-    AMDS_LAUNCH_CHECK("attn_flash_kernel<alibi,train>");
-    return AMDS_OK;
+    return alibi_fwd_train(qkv, coords, inv_running_mean, bias_scale, out_bf16, u_bf16, osm_bf16, lse, B, T, H, dtype, false, stream);
 }
-
-// the same with out / U / Osm in the operand type itself (dtype = AMDS_F16: the training step at float32_matmul_precision "high"; AMDS_BF16 = the entry above)
 int amds::attention_alibi_fwd_train_dt(const void* qkv, const float* coords, const float* inv_running_mean, const float* bias_scale, void* out, void* u, void* osm,
                                        float* lse, int B, int T, int H, int dtype, void* stream) {
-    if (dtype != AMDS_F16) return amds_attention_alibi_fwd_train(qkv, coords, inv_running_mean, bias_scale, out, u, osm, lse, B, T, H, dtype, stream);
-    AMDS_REQUIRE(qkv && coords && inv_running_mean && bias_scale && out && u && osm && lse, "amds_attention_alibi_fwd_train: null pointer");
-    AMDS_REQUIRE(B >= 0 && T > 0 && H > 0 && H <= 65535 && B <= 65535 && FA_SPAN_OK(T, H), "amds_attention_alibi_fwd_train: bad shape B=%d T=%d H=%d", B, T, H);
-    if (B == 0) return AMDS_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((T + 127) / 128, H, B), block(256);
-    ProfScope prof(PROF_ATTN, 6.0 * B * H * (double)T * T * 64, st);
-    hipLaunchKernelGGL((attn_flash_kernel<f16, true, f16>), grid, block, 0, st, (const f16*)qkv, (f16*)out, T, H, coords, inv_running_mean, lse, bias_scale, (f16*)u, (f16*)osm);
-    AMDS_LAUNCH_CHECK("attn_flash_kernel<alibi,train,f16>");
-    return AMDS_OK;
+    return alibi_fwd_train(qkv, coords, inv_running_mean, bias_scale, out, u, osm, lse, B, T, H, dtype, dtype == AMDS_F16, stream);
 }
 
 // `mask != None` forward of the reference (vision_tranformer.py:355-381; pinned by the reference's tests/test_model.py:28-32): pad u8 [B][T]
@@ -972,14 +955,10 @@ extern "C" int amds_attention_masked(const void* qkv, const uint8_t* pad, void* 
     AMDS_REQUIRE(qkv && out && pad, "amds_attention_masked: null pointer");
     AMDS_REQUIRE(B >= 0 && T > 0 && H > 0 && H <= 65535 && B <= 65535 && FA_SPAN_OK(T, H) && mask_heads > 0 && mask_heads <= H, "amds_attention_masked: bad shape B=%d T=%d H=%d mask_heads=%d", B, T, H, mask_heads);
     if (B == 0) return AMDS_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((T + 127) / 128, H, B), block(256);
-    ProfScope prof(PROF_ATTN, 4.0 * B * H * (double)T * T * 64, st);
-    if (dtype == AMDS_F16) hipLaunchKernelGGL((attn_flash_kernel<f16, false, f16, true>), grid, block, 0, st, (const f16*)qkv, (f16*)out, T, H, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pad, 0, 0, 0, 1.f, mask_heads);
-    else if (dtype == AMDS_BF16) hipLaunchKernelGGL((attn_flash_kernel<bf16, false, bf16, true>), grid, block, 0, st, (const bf16*)qkv, (bf16*)out, T, H, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pad, 0, 0, 0, 1.f, mask_heads);
-    else { set_error("amds_attention_masked: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
-    AMDS_LAUNCH_CHECK("attn_flash_kernel<mask>");
-    return AMDS_OK;
+    FlashOpt o;
+    o.pad = pad;
+    o.mask_heads = mask_heads;
+    return flash_launch<false, true>("amds_attention_masked", "attn_flash_kernel<mask>", qkv, out, B, T, H, dtype, o, (hipStream_t)stream);
 }
 
 extern "C" int amds_attention_alibi_masked(const void* qkv, const float* coords, const float* head_scale, const uint8_t* pad, void* out, int B, int T,
@@ -987,14 +966,11 @@ extern "C" int amds_attention_alibi_masked(const void* qkv, const float* coords,
     AMDS_REQUIRE(qkv && out && coords && head_scale && pad, "amds_attention_alibi_masked: null pointer");
     AMDS_REQUIRE(B >= 0 && T > 0 && H > 0 && H <= 65535 && B <= 65535 && FA_SPAN_OK(T, H), "amds_attention_alibi_masked: bad shape B=%d T=%d H=%d", B, T, H);
     if (B == 0) return AMDS_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((T + 127) / 128, H, B), block(256);
-    ProfScope prof(PROF_ATTN, 6.0 * B * H * (double)T * T * 64, st);
-    if (dtype == AMDS_F16) hipLaunchKernelGGL((attn_flash_kernel<f16, true, bf16, true>), grid, block, 0, st, (const f16*)qkv, (bf16*)out, T, H, coords, head_scale, nullptr, nullptr, nullptr, nullptr, pad, 0, 0, 0, 1.f);
-    else if (dtype == AMDS_BF16) hipLaunchKernelGGL((attn_flash_kernel<bf16, true, bf16, true>), grid, block, 0, st, (const bf16*)qkv, (bf16*)out, T, H, coords, head_scale, nullptr, nullptr, nullptr, nullptr, pad, 0, 0, 0, 1.f);
-    else { set_error("amds_attention_alibi_masked: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
-    AMDS_LAUNCH_CHECK("attn_flash_kernel<alibi,mask>");
-    return AMDS_OK;
+    FlashOpt o;
+    o.coords = coords;
+    o.head_scale = head_scale;
+    o.pad = pad;
+    return flash_launch<true, true>("amds_attention_alibi_masked", "attn_flash_kernel<alibi,mask>", qkv, out, B, T, H, dtype, o, (hipStream_t)stream);
 }
 
 // Training forward of nn.MultiheadAttention with dropout p on the attention probabilities (vision_tranformer.py:191: the `dropout`
@@ -1005,16 +981,12 @@ extern "C" int amds_attention_fwd_train(const void* qkv, void* out, float* lse, 
     AMDS_REQUIRE(qkv && out && lse, "amds_attention_fwd_train: null pointer");
     AMDS_REQUIRE(B >= 0 && T > 0 && H > 0 && H <= 65535 && B <= 65535 && FA_SPAN_OK(T, H) && p > 0.f && p < 1.f, "amds_attention_fwd_train: bad arguments B=%d T=%d H=%d p=%f", B, T, H, p);
     if (B == 0) return AMDS_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((T + 127) / 128, H, B), block(256);
-    const uint32_t thr = drop_thr16(p);
-    const float ks = drop_scale(thr);
-    ProfScope prof(PROF_ATTN, 4.0 * B * H * (double)T * T * 64, st);
-    if (dtype == AMDS_F16) hipLaunchKernelGGL((attn_flash_kernel<f16, false, f16, false, true>), grid, block, 0, st, (const f16*)qkv, (f16*)out, T, H, nullptr, nullptr, lse, nullptr, nullptr, nullptr, nullptr, seed, stream_id, thr, ks);
-    else if (dtype == AMDS_BF16) hipLaunchKernelGGL((attn_flash_kernel<bf16, false, bf16, false, true>), grid, block, 0, st, (const bf16*)qkv, (bf16*)out, T, H, nullptr, nullptr, lse, nullptr, nullptr, nullptr, nullptr, seed, stream_id, thr, ks);
-    else { set_error("amds_attention_fwd_train: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
-    AMDS_LAUNCH_CHECK("attn_flash_kernel<drop>");
-    return AMDS_OK;
+    FlashOpt o;
+    o.lse = lse;
+    o.p = p;
+    o.seed = seed;
+    o.stream_id = stream_id;
+    return flash_launch<false, false, true>("amds_attention_fwd_train", "attn_flash_kernel<drop>", qkv, out, B, T, H, dtype, o, (hipStream_t)stream);
 }
 
 

@@ -14,7 +14,7 @@
 // stage c issues QK^T of chunk c + 1 and P V of chunk c - 1 (16 MFMAs) in the gaps of chunk c's softmax (16 slices the scheduler may not
 // move across).  Round 2: 775 -> 742 (odd query) -> 695 us (pipeline) per 1020-tile launch.
 // Arithmetic of the 256 even queries, LDS images and the no-shuffle MFMA operand layout are those of attention_vit.hip.
-#include "common.h"
+#include "launch.h"
 #include <type_traits>
 
 namespace amds {
@@ -447,12 +447,8 @@ __global__ void __launch_bounds__(512) attn_vit257_kernel(const T* __restrict__ 
 
 template <typename T>
 static int launch_attn257(const void* qkv, void* out, int B, int H, hipStream_t st) {
-    auto kern = attn_vit257_kernel<T>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, A7_LDS));
-        attr_set = true;
-    }
+    constexpr auto kern = attn_vit257_kernel<T>;
+    AMDS_HIP(lds_opt_in<kern>(A7_LDS));
     const int n_cus = device_cu_count();
     AMDS_REQUIRE(n_cus > 0, "attention: cannot read the device's multiprocessor count");
     const int n_items = B * H;

@@ -17,7 +17,7 @@
 // LDS: 2 x (272 x 128 + 64 x 576 + 128) + 16 + 2 x 4 x R x 272 B = 163 216 B at R = 9.
 // Results: same arithmetic as the one-shot kernel of attention_vit.hip up to the summation order of the softmax denominators (tests hold both to
 // the fp64 reference at the same bar).
-#include "common.h"
+#include "launch.h"
 #include <type_traits>
 
 namespace amds {
@@ -450,14 +450,10 @@ __global__ void __launch_bounds__(512) attn_vit26x_kernel(const T* __restrict__ 
 
 template <typename T, int R>
 static int launch_attn26x(const void* qkv, void* out, int B, int H, hipStream_t st) {
-    auto kern = attn_vit26x_kernel<T, R>;
+    constexpr auto kern = attn_vit26x_kernel<T, R>;
     constexpr int LDS = ax_lds(R);
     static_assert(LDS <= 160 * 1024, "LDS budget");
-    static bool attr_set = false;
-    if (!attr_set) {
-        AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr_set = true;
-    }
+    AMDS_HIP(lds_opt_in<kern>(LDS));
     const int n_cus = device_cu_count();
     AMDS_REQUIRE(n_cus > 0, "attention: cannot read the device's multiprocessor count");
     const int n_items = B * H;

@@ -210,14 +210,8 @@ static int launch_attn80(const void* qkv, void* out, int B, int Tn, int H, hipSt
         const char* e = getenv("AMDS_ATTN80_THREADS");            // 256 = the four-wave form (A/B)
         nth = (e && atoi(e) == 256) ? 256 : 512;
     }
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        AMDS_HIP(hipGetDevice(&dev));
-        AMDS_HIP(hipGetDeviceProperties(&p, dev));
-        cus = p.multiProcessorCount;
-    }
+    const int cus = device_cu_count();
+    AMDS_REQUIRE(cus > 0, "attention: cannot read the device's multiprocessor count");
     const int n_items = B * H;
     const dim3 grid(n_items < cus ? n_items : cus);
     switch (nkt) {

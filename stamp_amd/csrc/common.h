@@ -26,10 +26,10 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 // ---- error plumbing (host) -------------------------------------------------------------------
 void set_error(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
-#define AMDS_HIP(call)                                           \
-    do {                                                         \
-        hipError_t e__ = (call);                                 \
-        if (e__ != hipSuccess) return amds::hip_fail(e__, #call); \
+#define AMDS_HIP(...)                                                   \
+    do {                                                                \
+        hipError_t e__ = (__VA_ARGS__);                                 \
+        if (e__ != hipSuccess) return amds::hip_fail(e__, #__VA_ARGS__); \
     } while (0)
 #define AMDS_REQUIRE(cond, ...)              \
     do {                                     \
@@ -329,6 +329,7 @@ amds_ctx* ctx_of_current_device();
 int ctx_matmul_precision();      // of the current device's context (AMDS_MATMUL_HIGHEST without one)
 int ctx_mil_cls_tail();          // of the current device's context (the AMDS_MIL_CLS_TAIL environment default without one)
 int device_cu_count();           // multiprocessor count of the current device, cached per device
+constexpr int MAX_DEV = 64;      // devices per process that per-device state (contexts, CU counts, launch.h's LDS opt-ins) has room for
 struct ProfScope {
     hipStream_t st; amds_ctx* ctx = nullptr; int slot = -1;
     ProfScope(int kind, double work, hipStream_t s) : st(s) { if (g_prof_any.load(std::memory_order_relaxed) > 0) slot = prof_begin(kind, work, s, &ctx); }

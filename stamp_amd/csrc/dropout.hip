@@ -8,7 +8,7 @@
 //   amds_dropout_cast_bwd          dy16 = (16-bit) drop'(dx)       (gradient entering fc2's backward GEMMs)
 //   amds_dropout_mask / amds_attention_dropout_mask   the masks themselves as u8, for the parity tests
 #include <algorithm>
-#include "common.h"
+#include "launch.h"
 
 namespace amds {
 
@@ -230,14 +230,13 @@ int amds::gelu_dropout_fwd_rows_dt(const void* z, long ldz, void* u, long ldu, l
                                    void* stream) {
     AMDS_REQUIRE(z && u && rows >= 0 && cols > 0 && row_mul > 0 && p >= 0.f && p < 1.f && (dtype == AMDS_BF16 || dtype == AMDS_F16), "amds_gelu_dropout_fwd_rows: bad arguments");
     if (rows == 0) return AMDS_OK;
-    const uint32_t thr = p > 0.f ? drop_thr16(p) : 0;
+    const DropParams d(p);
     const int grid = (int)std::min<long>(4096, (rows * cols + 255) / 256);
-    if (dtype == AMDS_BF16)
-        hipLaunchKernelGGL((gelu_dropout_fwd_rows_kernel<bf16, bf16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)z, ldz, (bf16*)u, ldu, rows, cols, row_mul, seed,
-                           stream_id, thr, thr ? drop_scale(thr) : 1.0f);
-    else
-        hipLaunchKernelGGL((gelu_dropout_fwd_rows_kernel<f16, f16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f16*)z, ldz, (f16*)u, ldu, rows, cols, row_mul, seed,
-                           stream_id, thr, thr ? drop_scale(thr) : 1.0f);
+    dispatch_16(dtype, [&](auto t) {
+        typedef AMDS_TAG_T(t) T;
+        hipLaunchKernelGGL((gelu_dropout_fwd_rows_kernel<T, T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)z, ldz, (T*)u, ldu, rows, cols, row_mul, seed, stream_id,
+                           d.thr, d.scale);
+    });
     AMDS_LAUNCH_CHECK("gelu_dropout_fwd_rows_kernel");
     return AMDS_OK;
 }
@@ -249,14 +248,13 @@ int amds::gelu_dropout_bwd_rows_dt(const void* z, long ldz, const void* du, long
                                    uint64_t seed, uint32_t stream_id, void* stream) {
     AMDS_REQUIRE(z && du && dz && rows >= 0 && cols > 0 && row_mul > 0 && p >= 0.f && p < 1.f && (dtype == AMDS_BF16 || dtype == AMDS_F16), "amds_gelu_dropout_bwd_rows: bad arguments");
     if (rows == 0) return AMDS_OK;
-    const uint32_t thr = p > 0.f ? drop_thr16(p) : 0;
+    const DropParams d(p);
     const int grid = (int)std::min<long>(4096, (rows * cols + 255) / 256);
-    if (dtype == AMDS_BF16)
-        hipLaunchKernelGGL((gelu_dropout_bwd_rows_kernel<bf16, bf16, bf16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)z, ldz, (const bf16*)du, ldu, (bf16*)dz,
-                           lddz, rows, cols, row_mul, seed, stream_id, thr, thr ? drop_scale(thr) : 1.0f);
-    else
-        hipLaunchKernelGGL((gelu_dropout_bwd_rows_kernel<f16, f16, f16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f16*)z, ldz, (const f16*)du, ldu, (f16*)dz,
-                           lddz, rows, cols, row_mul, seed, stream_id, thr, thr ? drop_scale(thr) : 1.0f);
+    dispatch_16(dtype, [&](auto t) {
+        typedef AMDS_TAG_T(t) T;
+        hipLaunchKernelGGL((gelu_dropout_bwd_rows_kernel<T, T, T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)z, ldz, (const T*)du, ldu, (T*)dz, lddz, rows, cols,
+                           row_mul, seed, stream_id, d.thr, d.scale);
+    });
     AMDS_LAUNCH_CHECK("gelu_dropout_bwd_rows_kernel");
     return AMDS_OK;
 }
@@ -268,10 +266,9 @@ extern "C" int amds_dropout_add_rows(const float* y, long ldy, const float* x_in
                                      uint64_t seed, uint32_t stream_id, void* stream) {
     AMDS_REQUIRE(y && x_in && x_out && rows >= 0 && cols > 0 && row_mul > 0 && p >= 0.f && p < 1.f, "amds_dropout_add_rows: bad arguments");
     if (rows == 0) return AMDS_OK;
-    const uint32_t thr = p > 0.f ? drop_thr16(p) : 0;
+    const DropParams d(p);
     const int grid = (int)std::min<long>(4096, (rows * cols + 255) / 256);
-    hipLaunchKernelGGL(dropout_add_rows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, y, ldy, x_in, ldx, x_out, ldo, rows, cols, row_mul, seed, stream_id, thr,
-                       thr ? drop_scale(thr) : 1.0f);
+    hipLaunchKernelGGL(dropout_add_rows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, y, ldy, x_in, ldx, x_out, ldo, rows, cols, row_mul, seed, stream_id, d.thr, d.scale);
     AMDS_LAUNCH_CHECK("dropout_add_rows_kernel");
     return AMDS_OK;
 }
@@ -280,17 +277,13 @@ int amds::dropout_cast_bwd_rows_dt(const float* dx, long ldx, void* dy, long ldy
     AMDS_REQUIRE(dx && dy && rows >= 0 && cols > 0 && row_mul > 0 && p >= 0.f && p < 1.f && (dtype == AMDS_BF16 || dtype == AMDS_F16 || dtype == AMDS_F32),
                  "amds_dropout_cast_bwd_rows: bad arguments");
     if (rows == 0) return AMDS_OK;
-    const uint32_t thr = p > 0.f ? drop_thr16(p) : 0;
+    const DropParams d(p);
     const int grid = (int)std::min<long>(4096, (rows * cols + 255) / 256);
-    if (dtype == AMDS_BF16)
-        hipLaunchKernelGGL((dropout_cast_bwd_rows_kernel<bf16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dx, ldx, (bf16*)dy, ldy, rows, cols, row_mul, seed, stream_id, thr,
-                           thr ? drop_scale(thr) : 1.0f);
-    else if (dtype == AMDS_F32)
-        hipLaunchKernelGGL((dropout_cast_bwd_rows_kernel<float>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dx, ldx, (float*)dy, ldy, rows, cols, row_mul, seed, stream_id, thr,
-                           thr ? drop_scale(thr) : 1.0f);
-    else
-        hipLaunchKernelGGL((dropout_cast_bwd_rows_kernel<f16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dx, ldx, (f16*)dy, ldy, rows, cols, row_mul, seed, stream_id, thr,
-                           thr ? drop_scale(thr) : 1.0f);
+    dispatch_16_32(dtype, [&](auto t) {
+        typedef AMDS_TAG_T(t) TO;
+        hipLaunchKernelGGL((dropout_cast_bwd_rows_kernel<TO>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dx, ldx, (TO*)dy, ldy, rows, cols, row_mul, seed, stream_id, d.thr,
+                           d.scale);
+    });
     AMDS_LAUNCH_CHECK("dropout_cast_bwd_rows_kernel");
     return AMDS_OK;
 }
@@ -298,56 +291,58 @@ extern "C" int amds_dropout_cast_bwd_rows(const float* dx, long ldx, void* dy, l
                                           void* stream) {
     return dropout_cast_bwd_rows_dt(dx, ldx, dy, ldy, rows, cols, row_mul, AMDS_BF16, p, seed, stream_id, stream);
 }
-extern "C" float amds_dropout_keep_scale(float p) { return drop_scale(drop_thr16(p)); }
+extern "C" float amds_dropout_keep_scale(float p) { return DropParams(p).scale; }
 
+// z in any of the three types; u in z's type or fp32.  The 8-wide kernels exist for 16-bit z only.
 extern "C" int amds_gelu_dropout_fwd(const void* z, void* u, long n, int in_dtype, int out_dtype, float p, uint64_t seed, uint32_t stream_id, void* stream) {
     AMDS_REQUIRE(z && u && n >= 0 && DROP_ARGS_OK(p), "amds_gelu_dropout_fwd: bad arguments");
     if (n == 0) return AMDS_OK;
     hipStream_t st = (hipStream_t)stream;
-    const uint32_t thr = drop_thr16(p);
-    const float sc = drop_scale(thr);
+    const DropParams d(p);
     const bool v8 = n % 8 == 0 && al16(z) && al16(u);
-    if (in_dtype == AMDS_BF16 && out_dtype == AMDS_BF16 && v8) hipLaunchKernelGGL((gelu_dropout_fwd8_kernel<bf16, bf16>), dim3(grid1d_(n / 8)), dim3(256), 0, st, (const bf16*)z, (bf16*)u, n / 8, seed, stream_id, thr, sc);
-    else if (in_dtype == AMDS_BF16 && out_dtype == AMDS_F32 && v8) hipLaunchKernelGGL((gelu_dropout_fwd8_kernel<bf16, float>), dim3(grid1d_(n / 8)), dim3(256), 0, st, (const bf16*)z, (float*)u, n / 8, seed, stream_id, thr, sc);
-    else if (in_dtype == AMDS_BF16 && out_dtype == AMDS_BF16) hipLaunchKernelGGL((gelu_dropout_fwd_kernel<bf16, bf16>), dim3(grid1d_(n)), dim3(256), 0, st, (const bf16*)z, (bf16*)u, n, seed, stream_id, thr, sc);
-    else if (in_dtype == AMDS_BF16 && out_dtype == AMDS_F32) hipLaunchKernelGGL((gelu_dropout_fwd_kernel<bf16, float>), dim3(grid1d_(n)), dim3(256), 0, st, (const bf16*)z, (float*)u, n, seed, stream_id, thr, sc);
-    else if (in_dtype == AMDS_F16 && out_dtype == AMDS_F16 && v8) hipLaunchKernelGGL((gelu_dropout_fwd8_kernel<f16, f16>), dim3(grid1d_(n / 8)), dim3(256), 0, st, (const f16*)z, (f16*)u, n / 8, seed, stream_id, thr, sc);
-    else if (in_dtype == AMDS_F16 && out_dtype == AMDS_F32 && v8) hipLaunchKernelGGL((gelu_dropout_fwd8_kernel<f16, float>), dim3(grid1d_(n / 8)), dim3(256), 0, st, (const f16*)z, (float*)u, n / 8, seed, stream_id, thr, sc);
-    else if (in_dtype == AMDS_F16 && out_dtype == AMDS_F16) hipLaunchKernelGGL((gelu_dropout_fwd_kernel<f16, f16>), dim3(grid1d_(n)), dim3(256), 0, st, (const f16*)z, (f16*)u, n, seed, stream_id, thr, sc);
-    else if (in_dtype == AMDS_F16 && out_dtype == AMDS_F32) hipLaunchKernelGGL((gelu_dropout_fwd_kernel<f16, float>), dim3(grid1d_(n)), dim3(256), 0, st, (const f16*)z, (float*)u, n, seed, stream_id, thr, sc);
-    else if (in_dtype == AMDS_F32 && out_dtype == AMDS_F32) hipLaunchKernelGGL((gelu_dropout_fwd_kernel<float, float>), dim3(grid1d_(n)), dim3(256), 0, st, (const float*)z, (float*)u, n, seed, stream_id, thr, sc);
-    else { set_error("amds_gelu_dropout_fwd: unsupported dtype pair"); return AMDS_ERR_INVALID; }
+    bool ok = false;
+    dispatch_16_32(in_dtype, [&](auto tz) { dispatch_16_32(out_dtype, [&](auto to) {
+        typedef AMDS_TAG_T(tz) TZ;
+        typedef AMDS_TAG_T(to) TO;
+        if constexpr (std::is_same_v<TO, TZ> || std::is_same_v<TO, float>) {
+            ok = true;
+            if constexpr (!std::is_same_v<TZ, float>)
+                if (v8) {
+                    hipLaunchKernelGGL((gelu_dropout_fwd8_kernel<TZ, TO>), dim3(grid1d_(n / 8)), dim3(256), 0, st, (const TZ*)z, (TO*)u, n / 8, seed, stream_id, d.thr, d.scale);
+                    return;
+                }
+            hipLaunchKernelGGL((gelu_dropout_fwd_kernel<TZ, TO>), dim3(grid1d_(n)), dim3(256), 0, st, (const TZ*)z, (TO*)u, n, seed, stream_id, d.thr, d.scale);
+        }
+    }); });
+    if (!ok) { set_error("amds_gelu_dropout_fwd: unsupported dtype pair"); return AMDS_ERR_INVALID; }
     AMDS_LAUNCH_CHECK("gelu_dropout_fwd_kernel");
     return AMDS_OK;
 }
 
+// dz in z's type; du in that type or fp32.  The 8-wide kernels exist for 16-bit z only.
 extern "C" int amds_gelu_dropout_bwd(const void* z, const void* du, void* dz, long n, int z_dtype, int du_dtype, int dz_dtype, float p, uint64_t seed,
                                      uint32_t stream_id, void* stream) {
     AMDS_REQUIRE(z && du && dz && n >= 0 && DROP_ARGS_OK(p), "amds_gelu_dropout_bwd: bad arguments");
     if (n == 0) return AMDS_OK;
     hipStream_t st = (hipStream_t)stream;
-    const uint32_t thr = drop_thr16(p);
-    const float sc = drop_scale(thr);
+    const DropParams d(p);
     const bool v8 = n % 8 == 0 && al16(z) && al16(du) && al16(dz);
-    if (z_dtype == AMDS_BF16 && du_dtype == AMDS_BF16 && dz_dtype == AMDS_BF16 && v8)
-        hipLaunchKernelGGL((gelu_dropout_bwd8_kernel<bf16, bf16, bf16>), dim3(grid1d_(n / 8)), dim3(256), 0, st, (const bf16*)z, (const bf16*)du, (bf16*)dz, n / 8, seed, stream_id, thr, sc);
-    else if (z_dtype == AMDS_BF16 && du_dtype == AMDS_F32 && dz_dtype == AMDS_BF16 && v8)
-        hipLaunchKernelGGL((gelu_dropout_bwd8_kernel<bf16, float, bf16>), dim3(grid1d_(n / 8)), dim3(256), 0, st, (const bf16*)z, (const float*)du, (bf16*)dz, n / 8, seed, stream_id, thr, sc);
-    else if (z_dtype == AMDS_BF16 && du_dtype == AMDS_BF16 && dz_dtype == AMDS_BF16)
-        hipLaunchKernelGGL((gelu_dropout_bwd_kernel<bf16, bf16, bf16>), dim3(grid1d_(n)), dim3(256), 0, st, (const bf16*)z, (const bf16*)du, (bf16*)dz, n, seed, stream_id, thr, sc);
-    else if (z_dtype == AMDS_BF16 && du_dtype == AMDS_F32 && dz_dtype == AMDS_BF16)
-        hipLaunchKernelGGL((gelu_dropout_bwd_kernel<bf16, float, bf16>), dim3(grid1d_(n)), dim3(256), 0, st, (const bf16*)z, (const float*)du, (bf16*)dz, n, seed, stream_id, thr, sc);
-    else if (z_dtype == AMDS_F16 && du_dtype == AMDS_F16 && dz_dtype == AMDS_F16 && v8)
-        hipLaunchKernelGGL((gelu_dropout_bwd8_kernel<f16, f16, f16>), dim3(grid1d_(n / 8)), dim3(256), 0, st, (const f16*)z, (const f16*)du, (f16*)dz, n / 8, seed, stream_id, thr, sc);
-    else if (z_dtype == AMDS_F16 && du_dtype == AMDS_F32 && dz_dtype == AMDS_F16 && v8)
-        hipLaunchKernelGGL((gelu_dropout_bwd8_kernel<f16, float, f16>), dim3(grid1d_(n / 8)), dim3(256), 0, st, (const f16*)z, (const float*)du, (f16*)dz, n / 8, seed, stream_id, thr, sc);
-    else if (z_dtype == AMDS_F16 && du_dtype == AMDS_F16 && dz_dtype == AMDS_F16)
-        hipLaunchKernelGGL((gelu_dropout_bwd_kernel<f16, f16, f16>), dim3(grid1d_(n)), dim3(256), 0, st, (const f16*)z, (const f16*)du, (f16*)dz, n, seed, stream_id, thr, sc);
-    else if (z_dtype == AMDS_F16 && du_dtype == AMDS_F32 && dz_dtype == AMDS_F16)
-        hipLaunchKernelGGL((gelu_dropout_bwd_kernel<f16, float, f16>), dim3(grid1d_(n)), dim3(256), 0, st, (const f16*)z, (const float*)du, (f16*)dz, n, seed, stream_id, thr, sc);
-    else if (z_dtype == AMDS_F32 && du_dtype == AMDS_F32 && dz_dtype == AMDS_F32)
-        hipLaunchKernelGGL((gelu_dropout_bwd_kernel<float, float, float>), dim3(grid1d_(n)), dim3(256), 0, st, (const float*)z, (const float*)du, (float*)dz, n, seed, stream_id, thr, sc);
-    else { set_error("amds_gelu_dropout_bwd: unsupported dtype combination"); return AMDS_ERR_INVALID; }
+    bool ok = false;
+    if (dz_dtype == z_dtype) dispatch_16_32(z_dtype, [&](auto tz) { dispatch_16_32(du_dtype, [&](auto tg) {
+        typedef AMDS_TAG_T(tz) TZ;
+        typedef AMDS_TAG_T(tg) TG;
+        if constexpr (std::is_same_v<TG, TZ> || std::is_same_v<TG, float>) {
+            ok = true;
+            if constexpr (!std::is_same_v<TZ, float>)
+                if (v8) {
+                    hipLaunchKernelGGL((gelu_dropout_bwd8_kernel<TZ, TG, TZ>), dim3(grid1d_(n / 8)), dim3(256), 0, st, (const TZ*)z, (const TG*)du, (TZ*)dz, n / 8, seed, stream_id,
+                                       d.thr, d.scale);
+                    return;
+                }
+            hipLaunchKernelGGL((gelu_dropout_bwd_kernel<TZ, TG, TZ>), dim3(grid1d_(n)), dim3(256), 0, st, (const TZ*)z, (const TG*)du, (TZ*)dz, n, seed, stream_id, d.thr, d.scale);
+        }
+    }); });
+    if (!ok) { set_error("amds_gelu_dropout_bwd: unsupported dtype combination"); return AMDS_ERR_INVALID; }
     AMDS_LAUNCH_CHECK("gelu_dropout_bwd_kernel");
     return AMDS_OK;
 }
@@ -356,13 +351,13 @@ extern "C" int amds_dropout_add(const float* y, long ldy, const float* x_in, lon
                                 uint64_t seed, uint32_t stream_id, void* stream) {
     AMDS_REQUIRE(y && x_in && x_out && rows >= 0 && cols > 0 && ldy >= cols && ldx >= cols && ldo >= cols && DROP_ARGS_OK(p), "amds_dropout_add: bad arguments");
     if (rows == 0) return AMDS_OK;
-    const uint32_t thr = drop_thr16(p);
+    const DropParams d(p);
     if (cols % 8 == 0 && ldy % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && al16(y) && al16(x_in) && al16(x_out))
         hipLaunchKernelGGL(dropout_add8_kernel, dim3(grid1d_(rows * cols / 8)), dim3(256), 0, (hipStream_t)stream, y, ldy, x_in, ldx, x_out, ldo, rows, cols, seed,
-                           stream_id, thr, drop_scale(thr));
+                           stream_id, d.thr, d.scale);
     else
         hipLaunchKernelGGL(dropout_add_kernel, dim3(grid1d_(rows * cols)), dim3(256), 0, (hipStream_t)stream, y, ldy, x_in, ldx, x_out, ldo, rows, cols, seed,
-                           stream_id, thr, drop_scale(thr));
+                           stream_id, d.thr, d.scale);
     AMDS_LAUNCH_CHECK("dropout_add_kernel");
     return AMDS_OK;
 }
@@ -371,16 +366,19 @@ extern "C" int amds_dropout_cast_bwd(const float* dx, long ldx, void* dy, long l
                                      uint32_t stream_id, void* stream) {
     AMDS_REQUIRE(dx && dy && rows >= 0 && cols > 0 && ldx >= cols && ldy >= cols && DROP_ARGS_OK(p), "amds_dropout_cast_bwd: bad arguments");
     if (rows == 0) return AMDS_OK;
-    const uint32_t thr = drop_thr16(p);
+    const DropParams d(p);
     hipStream_t st = (hipStream_t)stream;
-    if (out_dtype == AMDS_BF16 && cols % 8 == 0 && ldx % 4 == 0 && ldy % 8 == 0 && al16(dx) && al16(dy))
-        hipLaunchKernelGGL((dropout_cast_bwd8_kernel<bf16>), dim3(grid1d_(rows * cols / 8)), dim3(256), 0, st, dx, ldx, (bf16*)dy, ldy, rows, cols, seed, stream_id, thr, drop_scale(thr));
-    else if (out_dtype == AMDS_BF16) hipLaunchKernelGGL((dropout_cast_bwd_kernel<bf16>), dim3(grid1d_(rows * cols)), dim3(256), 0, st, dx, ldx, (bf16*)dy, ldy, rows, cols, seed, stream_id, thr, drop_scale(thr));
-    else if (out_dtype == AMDS_F16 && cols % 8 == 0 && ldx % 4 == 0 && ldy % 8 == 0 && al16(dx) && al16(dy))
-        hipLaunchKernelGGL((dropout_cast_bwd8_kernel<f16>), dim3(grid1d_(rows * cols / 8)), dim3(256), 0, st, dx, ldx, (f16*)dy, ldy, rows, cols, seed, stream_id, thr, drop_scale(thr));
-    else if (out_dtype == AMDS_F16) hipLaunchKernelGGL((dropout_cast_bwd_kernel<f16>), dim3(grid1d_(rows * cols)), dim3(256), 0, st, dx, ldx, (f16*)dy, ldy, rows, cols, seed, stream_id, thr, drop_scale(thr));
-    else if (out_dtype == AMDS_F32) hipLaunchKernelGGL((dropout_cast_bwd_kernel<float>), dim3(grid1d_(rows * cols)), dim3(256), 0, st, dx, ldx, (float*)dy, ldy, rows, cols, seed, stream_id, thr, drop_scale(thr));
-    else { set_error("amds_dropout_cast_bwd: bad dtype"); return AMDS_ERR_INVALID; }
+    const bool v8 = cols % 8 == 0 && ldx % 4 == 0 && ldy % 8 == 0 && al16(dx) && al16(dy);
+    const bool ok = dispatch_16_32(out_dtype, [&](auto t) {
+        typedef AMDS_TAG_T(t) TO;
+        if constexpr (!std::is_same_v<TO, float>)                       // the 8-wide kernel packs 16-bit outputs
+            if (v8) {
+                hipLaunchKernelGGL((dropout_cast_bwd8_kernel<TO>), dim3(grid1d_(rows * cols / 8)), dim3(256), 0, st, dx, ldx, (TO*)dy, ldy, rows, cols, seed, stream_id, d.thr, d.scale);
+                return;
+            }
+        hipLaunchKernelGGL((dropout_cast_bwd_kernel<TO>), dim3(grid1d_(rows * cols)), dim3(256), 0, st, dx, ldx, (TO*)dy, ldy, rows, cols, seed, stream_id, d.thr, d.scale);
+    });
+    if (!ok) { set_error("amds_dropout_cast_bwd: bad dtype"); return AMDS_ERR_INVALID; }
     AMDS_LAUNCH_CHECK("dropout_cast_bwd_kernel");
     return AMDS_OK;
 }

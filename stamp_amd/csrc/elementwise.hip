@@ -1,7 +1,7 @@
 // elementwise.hip -- HBM-bound kernels of the tile-encoder path: LayerNorm, weight casts, the u8 tile
 // transform and the u8 -> patch-matrix (im2col) staging.  One wave per row / 16-byte accesses per lane;
 // none of these has inter-block reuse, so no XCD remap (guide T1: 0 % on LayerNorm).
-#include "common.h"
+#include "launch.h"
 
 namespace amds {
 
@@ -394,13 +394,10 @@ extern "C" int amds_layernorm(const float* x, long x_row_stride, const float* ga
     if (rows == 0) return AMDS_OK;
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof(PROF_LN, (double)rows * cols * (4 + (out_dtype == AMDS_F32 ? 4 : 2)), st);
-    switch (out_dtype) {
-        case AMDS_F16: return launch_ln<f16>(x, x_row_stride, gamma, beta, y, y_row_stride, rows, cols, eps, st);
-        case AMDS_BF16: return launch_ln<bf16>(x, x_row_stride, gamma, beta, y, y_row_stride, rows, cols, eps, st);
-        case AMDS_F32: return launch_ln<float>(x, x_row_stride, gamma, beta, y, y_row_stride, rows, cols, eps, st);
-    }
-    set_error("amds_layernorm: bad out_dtype %d", out_dtype);
-    return AMDS_ERR_INVALID;
+    int rc = AMDS_ERR_INVALID;
+    if (!dispatch_16_32(out_dtype, [&](auto t) { rc = launch_ln<AMDS_TAG_T(t)>(x, x_row_stride, gamma, beta, y, y_row_stride, rows, cols, eps, st); }))
+        set_error("amds_layernorm: bad out_dtype %d", out_dtype);
+    return rc;
 }
 
 extern "C" int amds_cast_pad(const float* src, int ld_src, void* dst, int ld_dst, int rows, int cols, int dtype,
@@ -411,13 +408,11 @@ extern "C" int amds_cast_pad(const float* src, int ld_src, void* dst, int ld_dst
     if (total == 0) return AMDS_OK;
     const int grid = (int)min((long)4096, (total + 255) / 256);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == AMDS_F16)
-        hipLaunchKernelGGL((cast_pad_kernel<f16>), dim3(grid), dim3(256), 0, st, src, ld_src, (f16*)dst, ld_dst, total, cols);
-    else if (dtype == AMDS_BF16)
-        hipLaunchKernelGGL((cast_pad_kernel<bf16>), dim3(grid), dim3(256), 0, st, src, ld_src, (bf16*)dst, ld_dst, total, cols);
-    else if (dtype == AMDS_F32)
-        hipLaunchKernelGGL((cast_pad_kernel<float>), dim3(grid), dim3(256), 0, st, src, ld_src, (float*)dst, ld_dst, total, cols);
-    else { set_error("amds_cast_pad: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
+    const bool ok = dispatch_16_32(dtype, [&](auto t) {
+        typedef AMDS_TAG_T(t) T;
+        hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(grid), dim3(256), 0, st, src, ld_src, (T*)dst, ld_dst, total, cols);
+    });
+    if (!ok) { set_error("amds_cast_pad: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
     AMDS_LAUNCH_CHECK("cast_pad_kernel");
     return AMDS_OK;
 }
@@ -468,11 +463,11 @@ extern "C" int amds_tile_im2col_u8_ex(const uint8_t* tiles, void* out, int B, in
     const size_t lds = (size_t)patch * img * 3;
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof(PROF_OTHER, (double)B * ((double)img * img * 3 + (double)g * g * kp * (lo_shift ? 4 : 2)), st);
-    if (dtype == AMDS_F16)
-        hipLaunchKernelGGL((im2col_u8_kernel<f16>), dim3(B * g), dim3(256), lds, st, tiles, (f16*)out, img, patch, kp, lo_scale);
-    else if (dtype == AMDS_BF16)
-        hipLaunchKernelGGL((im2col_u8_kernel<bf16>), dim3(B * g), dim3(256), lds, st, tiles, (bf16*)out, img, patch, kp, lo_scale);
-    else { set_error("amds_tile_im2col_u8: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
+    const bool ok = dispatch_16(dtype, [&](auto t) {
+        typedef AMDS_TAG_T(t) T;
+        hipLaunchKernelGGL((im2col_u8_kernel<T>), dim3(B * g), dim3(256), lds, st, tiles, (T*)out, img, patch, kp, lo_scale);
+    });
+    if (!ok) { set_error("amds_tile_im2col_u8: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
     AMDS_LAUNCH_CHECK("im2col_u8_kernel");
     return AMDS_OK;
 }
@@ -506,13 +501,11 @@ extern "C" int amds_ln_stats_cast(const float* x, long ldx, int M, int D, float 
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof(PROF_LN, (double)M * D * 6.0, st);
     const int grid = cdiv(M, 4);
-    if (dtype == AMDS_F16) {
-        if (D <= 1024) hipLaunchKernelGGL((ln_stats_cast_kernel<f16, 4>), dim3(grid), dim3(256), 0, st, x, ldx, (f16*)xh, ldxh, M, D, eps, rowstat);
-        else hipLaunchKernelGGL((ln_stats_cast_kernel<f16, 8>), dim3(grid), dim3(256), 0, st, x, ldx, (f16*)xh, ldxh, M, D, eps, rowstat);
-    } else {
-        if (D <= 1024) hipLaunchKernelGGL((ln_stats_cast_kernel<bf16, 4>), dim3(grid), dim3(256), 0, st, x, ldx, (bf16*)xh, ldxh, M, D, eps, rowstat);
-        else hipLaunchKernelGGL((ln_stats_cast_kernel<bf16, 8>), dim3(grid), dim3(256), 0, st, x, ldx, (bf16*)xh, ldxh, M, D, eps, rowstat);
-    }
+    dispatch_16(dtype, [&](auto t) {
+        typedef AMDS_TAG_T(t) T;
+        if (D <= 1024) hipLaunchKernelGGL((ln_stats_cast_kernel<T, 4>), dim3(grid), dim3(256), 0, st, x, ldx, (T*)xh, ldxh, M, D, eps, rowstat);
+        else hipLaunchKernelGGL((ln_stats_cast_kernel<T, 8>), dim3(grid), dim3(256), 0, st, x, ldx, (T*)xh, ldxh, M, D, eps, rowstat);
+    });
     AMDS_LAUNCH_CHECK("ln_stats_cast_kernel");
     return AMDS_OK;
 }
@@ -545,9 +538,11 @@ extern "C" int amds_quick_gelu_inplace(void* u, long ld, long rows, int cols, in
     if (rows == 0) return AMDS_OK;
     const long total = rows * (cols >> 3);
     const unsigned grid = (unsigned)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
-    if (dtype == AMDS_F16) hipLaunchKernelGGL((quick_gelu_inplace_kernel<f16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (f16*)u, ld, rows, cols);
-    else if (dtype == AMDS_BF16) hipLaunchKernelGGL((quick_gelu_inplace_kernel<bf16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (bf16*)u, ld, rows, cols);
-    else { set_error("amds_quick_gelu_inplace: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
+    const bool ok = dispatch_16(dtype, [&](auto t) {
+        typedef AMDS_TAG_T(t) T;
+        hipLaunchKernelGGL((quick_gelu_inplace_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (T*)u, ld, rows, cols);
+    });
+    if (!ok) { set_error("amds_quick_gelu_inplace: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
     AMDS_LAUNCH_CHECK("quick_gelu_inplace_kernel");
     return AMDS_OK;
 }
@@ -575,9 +570,10 @@ extern "C" int amds_check_finite(const void* x, long n, int dtype, int* count_de
     AMDS_HIP(hipMemsetAsync(count_dev, 0, sizeof(int), st));
     if (n > 0) {
         const int grid = (int)((n + 256 * 8 - 1) / (256 * 8) < 2048 ? (n + 256 * 8 - 1) / (256 * 8) : 2048);
-        if (dtype == AMDS_F16) hipLaunchKernelGGL(count_nonfinite_kernel<_Float16>, dim3(grid), dim3(256), 0, st, reinterpret_cast<const _Float16*>(x), n, count_dev);
-        else if (dtype == AMDS_BF16) hipLaunchKernelGGL(count_nonfinite_kernel<__bf16>, dim3(grid), dim3(256), 0, st, reinterpret_cast<const __bf16*>(x), n, count_dev);
-        else hipLaunchKernelGGL(count_nonfinite_kernel<float>, dim3(grid), dim3(256), 0, st, reinterpret_cast<const float*>(x), n, count_dev);
+        dispatch_16_32(dtype, [&](auto t) {
+            typedef AMDS_TAG_T(t) T;
+            hipLaunchKernelGGL(count_nonfinite_kernel<T>, dim3(grid), dim3(256), 0, st, reinterpret_cast<const T*>(x), n, count_dev);
+        });
         AMDS_LAUNCH_CHECK("count_nonfinite_kernel");
     }
     AMDS_HIP(hipMemcpyAsync(count_host, count_dev, sizeof(int), hipMemcpyDeviceToHost, st));

@@ -723,7 +723,7 @@ static int launch_gemm_4w16(const void* A, long lda, const void* W, long ldw, in
         return launch_gemm_4w64<T, EPI>(A, lda, W, ldw, M, N, K, ep, st);
     } else {
         constexpr int LDS = 2 * (256 + 256) * 128;
-        auto kern = gemm_4w16_kernel<T, EPI, P3, P0, SPREAD, PRL, PRS, TN>;
+        constexpr auto kern = gemm_4w16_kernel<T, EPI, P3, P0, SPREAD, PRL, PRS, TN>;
         EpiArgs epp = ep;
         if constexpr (PRL + PRS > 0) {      // probe scratch: one region per workgroup, never read by anything real
             static char* scratch = nullptr;
@@ -736,11 +736,7 @@ static int launch_gemm_4w16(const void* A, long lda, const void* W, long ldw, in
             }
             epp.pos = reinterpret_cast<const float*>(scratch);
         }
-        static bool attr_set = false;
-        if (!attr_set) {
-            AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-            attr_set = true;
-        }
+        AMDS_HIP(lds_opt_in<kern>(LDS));
         const int tiles_m = cdiv(M, 256), tiles_n = N / 256;
         hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n, ep.nbatch), dim3(256), LDS, st, reinterpret_cast<const T*>(A), lda,
                            reinterpret_cast<const T*>(W), ldw, M, N, K, epp, tiles_m, tiles_n);

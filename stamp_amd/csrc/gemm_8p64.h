@@ -203,12 +203,8 @@ template <typename T, int EPI>
 static int launch_gemm_8p64(const void* A, long lda, const void* W, long ldw, int M, int N, int K, const EpiArgs& ep,
                             hipStream_t st) {
     constexpr int LDS = 2 * (256 + 256) * 128;
-    auto kern = gemm_8p64_kernel<T, EPI>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr_set = true;
-    }
+    constexpr auto kern = gemm_8p64_kernel<T, EPI>;
+    AMDS_HIP(lds_opt_in<kern>(LDS));
     const int tiles_m = cdiv(M, 256), tiles_n = N / 256;
     hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n, ep.nbatch), dim3(512), LDS, st, reinterpret_cast<const T*>(A), lda,
                        reinterpret_cast<const T*>(W), ldw, M, N, K, ep, tiles_m, tiles_n);

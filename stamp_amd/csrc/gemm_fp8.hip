@@ -314,12 +314,8 @@ gemm_fp8_kernel(const uint8_t* __restrict__ A, long lda, const uint8_t* __restri
 template <int EPI>
 static int launch_fp8(const void* A, long lda, const void* W, long ldw, int M, int N, int K, const Fp8Epi& ep, hipStream_t st) {
     constexpr int LDS = 2 * (256 + 256) * 128;
-    auto kern = gemm_fp8_kernel<EPI>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr_set = true;
-    }
+    constexpr auto kern = gemm_fp8_kernel<EPI>;
+    AMDS_HIP(lds_opt_in<kern>(LDS));
     const int tiles_m = cdiv(M, 256), tiles_n = N / 256;
     ProfScope prof(PROF_GEMM_FP8, 2.0 * M * (double)N * K, st);
     hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(256), LDS, st, reinterpret_cast<const uint8_t*>(A), lda, reinterpret_cast<const uint8_t*>(W), ldw, M, N, K, ep,

@@ -21,7 +21,7 @@
 //     co-resident tiles of an XCD share A and W panels through its L2.
 #pragma once
 #include <type_traits>
-#include "common.h"
+#include "launch.h"
 
 namespace amds {
 
@@ -398,13 +398,8 @@ static int launch_gemm_cfg(const void* A, long lda, const void* W, long ldw, int
     constexpr int STAGE = (BM + BN) * 64 * 2;
     constexpr int EPI_LDS = BM * ((BN * 4 / 16) | 1) * 16;            // fp32 tile at its odd chunk pitch
     constexpr int LDS = 2 * STAGE > EPI_LDS ? 2 * STAGE : EPI_LDS;
-    auto kern = gemm_tn_kernel<T, BM, BN, WM, WN, EPI>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr_set = true;
-    }
+    constexpr auto kern = gemm_tn_kernel<T, BM, BN, WM, WN, EPI>;
+    AMDS_HIP(lds_opt_in<kern>(LDS));
     const int tiles_m = cdiv(M, BM), tiles_n = N / BN;
     hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(64 * WM * WN), LDS, st,
                        reinterpret_cast<const T*>(A), lda, reinterpret_cast<const T*>(W), ldw, M, N, K, ep,

@@ -562,12 +562,8 @@ static int launch_rs_f16(const void* A, long lda, const void* W, long ldw, int M
     constexpr int K = KS * 16;
     const int nfrag = N / 32, slices = rs_slices(nfrag, KS), nf = nfrag / slices;
     const size_t lds = (size_t)nf * KS * 1024 + (LNF ? 2 * K * 4 : 0);
-    auto kern = rowstream_f16out_kernel<T, KS, FM, EPI, LNF>;
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-        AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds = lds;
-    }
+    constexpr auto kern = rowstream_f16out_kernel<T, KS, FM, EPI, LNF>;
+    AMDS_HIP(lds_opt_in<kern>(73728 + (LNF ? 2 * K * 4 : 0)));           // the bound of `lds` over N (rs_slices)
     const int groups = cdiv(M, 32 * FM);
     int gx = cdiv(groups, RS_WAVES);
     const int cap = 256 / slices > 0 ? 256 / slices : 1;            // one resident workgroup per CU over all slices
@@ -583,12 +579,8 @@ static int launch_rs_f32(const void* A, long lda, const void* W, long ldw, int M
                          hipStream_t st) {
     const int slices = N / (32 * NF);
     const size_t lds = (size_t)NF * KS * 1024;
-    auto kern = rowstream_f32out_kernel<T, KS, FM, NF, EPI, PREFETCH>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
+    constexpr auto kern = rowstream_f32out_kernel<T, KS, FM, NF, EPI, PREFETCH>;
+    AMDS_HIP(lds_opt_in<kern>((int)lds));
     const int groups = cdiv(M, 32 * FM);
     int gx = cdiv(groups, RS_WAVES);
     const int cap = 256 / slices > 0 ? 256 / slices : 1;
@@ -659,31 +651,28 @@ extern "C" int amds_swin_mlp96(float* x, int M, const void* fc1_w, const float* 
     int gx = cdiv(groups, RS_WAVES);
     if (gx > 256) gx = 256;
     ProfScope prof(PROF_GEMM, 4.0 * M * 96.0 * 384.0, st);
-#define MLP96_LAUNCH(T)                                                                                                              \
-    do {                                                                                                                             \
-        static bool attr_set = false;                                                                                                \
-        if (!attr_set) {                                                                                                             \
-            AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(swin_mlp96_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            attr_set = true;                                                                                                         \
-        }                                                                                                                            \
-        hipLaunchKernelGGL((swin_mlp96_kernel<T>), dim3(gx), dim3(64 * RS_WAVES), lds, st, x, M, reinterpret_cast<const T*>(fc1_w), fc1_b, \
-                           reinterpret_cast<const T*>(fc2_w), fc2_b, ln_gamma, ln_beta, ln_eps, groups);                             \
-    } while (0)
-    if (dtype == AMDS_F16) MLP96_LAUNCH(f16);
-    else if (dtype == AMDS_BF16) MLP96_LAUNCH(bf16);
-    else { set_error("amds_swin_mlp96: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
-#undef MLP96_LAUNCH
-    AMDS_LAUNCH_CHECK("swin_mlp96_kernel");
-    return AMDS_OK;
+    int rc = AMDS_OK;
+    const bool ok = dispatch_16(dtype, &rc, [&](auto t) -> int {
+        typedef AMDS_TAG_T(t) T;
+        AMDS_HIP(lds_opt_in<swin_mlp96_kernel<T>>((int)lds));
+        hipLaunchKernelGGL((swin_mlp96_kernel<T>), dim3(gx), dim3(64 * RS_WAVES), lds, st, x, M, reinterpret_cast<const T*>(fc1_w), fc1_b,
+                           reinterpret_cast<const T*>(fc2_w), fc2_b, ln_gamma, ln_beta, ln_eps, groups);
+        AMDS_LAUNCH_CHECK("swin_mlp96_kernel");
+        return AMDS_OK;
+    });
+    if (!ok) { set_error("amds_swin_mlp96: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
+    return rc;
 }
 
 extern "C" int amds_swin_mlp192_pack(const void* fc1_w, const void* fc2_w, void* packed, int dtype, void* stream) {
     AMDS_REQUIRE(fc1_w && fc2_w && packed, "amds_swin_mlp192_pack: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const int n = 12 * 48 * 64;
-    if (dtype == AMDS_F16) hipLaunchKernelGGL((swin_mlp192_pack_kernel<f16>), dim3(cdiv(n, 256)), dim3(256), 0, st, (const f16*)fc1_w, (const f16*)fc2_w, (f16*)packed);
-    else if (dtype == AMDS_BF16) hipLaunchKernelGGL((swin_mlp192_pack_kernel<bf16>), dim3(cdiv(n, 256)), dim3(256), 0, st, (const bf16*)fc1_w, (const bf16*)fc2_w, (bf16*)packed);
-    else { set_error("amds_swin_mlp192_pack: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
+    const bool ok = dispatch_16(dtype, [&](auto t) {
+        typedef AMDS_TAG_T(t) T;
+        hipLaunchKernelGGL((swin_mlp192_pack_kernel<T>), dim3(cdiv(n, 256)), dim3(256), 0, st, (const T*)fc1_w, (const T*)fc2_w, (T*)packed);
+    });
+    if (!ok) { set_error("amds_swin_mlp192_pack: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
     AMDS_LAUNCH_CHECK("swin_mlp192_pack_kernel");
     return AMDS_OK;
 }
@@ -699,20 +688,15 @@ extern "C" int amds_swin_mlp192(float* x, int M, const void* packed_w, const flo
     const int nblocks = cdiv(M, 32 * MS_WAVES);
     const int gx = nblocks < 256 ? nblocks : 256;
     ProfScope prof(PROF_GEMM, 4.0 * M * 192.0 * 768.0, st);
-#define MLP192_LAUNCH(T)                                                                                                              \
-    do {                                                                                                                              \
-        static bool attr_set = false;                                                                                                 \
-        if (!attr_set) {                                                                                                              \
-            AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(swin_mlp192_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            attr_set = true;                                                                                                          \
-        }                                                                                                                             \
-        hipLaunchKernelGGL((swin_mlp192_kernel<T>), dim3(gx), dim3(64 * MS_WAVES), lds, st, x, M, reinterpret_cast<const char*>(packed_w), fc1_b, fc2_b, \
-                           ln_gamma, ln_beta, ln_eps, nblocks);                                                                       \
-    } while (0)
-    if (dtype == AMDS_F16) MLP192_LAUNCH(f16);
-    else if (dtype == AMDS_BF16) MLP192_LAUNCH(bf16);
-    else { set_error("amds_swin_mlp192: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
-#undef MLP192_LAUNCH
-    AMDS_LAUNCH_CHECK("swin_mlp192_kernel");
-    return AMDS_OK;
+    int rc = AMDS_OK;
+    const bool ok = dispatch_16(dtype, &rc, [&](auto t) -> int {
+        typedef AMDS_TAG_T(t) T;
+        AMDS_HIP(lds_opt_in<swin_mlp192_kernel<T>>((int)lds));
+        hipLaunchKernelGGL((swin_mlp192_kernel<T>), dim3(gx), dim3(64 * MS_WAVES), lds, st, x, M, reinterpret_cast<const char*>(packed_w), fc1_b, fc2_b,
+                           ln_gamma, ln_beta, ln_eps, nblocks);
+        AMDS_LAUNCH_CHECK("swin_mlp192_kernel");
+        return AMDS_OK;
+    });
+    if (!ok) { set_error("amds_swin_mlp192: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
+    return rc;
 }

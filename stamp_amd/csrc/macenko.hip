@@ -9,7 +9,7 @@
 //   pass 3  concentrations C = pinv * OD of ALL pixels -> two histograms -> 99th percentiles -> scale to the reference maxima
 //   pass 4  I' = Io * exp(-HERef * C'), floor, clip, written back into the LDS tile and stored with 16-byte rows
 // HBM traffic: 150 528 B in + 150 528 B out per tile (the algorithmic minimum); everything else is LDS / VALU.
-#include "common.h"
+#include "launch.h"
 
 namespace amds {
 
@@ -206,11 +206,7 @@ extern "C" int amds_macenko_normalize_u8(const uint8_t* tiles, uint8_t* out, flo
     const int npix = H * W;
     const size_t lds = (((size_t)npix * 3 + 15) & ~(size_t)15) + MK_HB * 4 + (16 * 10 + 32) * 4;
     AMDS_REQUIRE(lds <= 160 * 1024, "amds_macenko_normalize_u8: a %d x %d tile does not fit in LDS", H, W);
-    static bool attr_set = false;
-    if (!attr_set) {
-        AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(macenko_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
+    AMDS_HIP(lds_opt_in<macenko_kernel>(160 * 1024));
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof(PROF_OTHER, 2.0 * B * npix * 3, st);
     hipLaunchKernelGGL(macenko_kernel, dim3(B), dim3(MK_T), lds, st, tiles, out, fit_out, npix, Io, alpha, beta);

@@ -10,7 +10,7 @@
 //            h = LN2(x) | u = gelu(h W1^T + b1) (GEMM) | x += u W2^T + b2 (GEMM)
 //   merge  : gather 2x2 cells + LayerNorm(4C) (one kernel) | x' = . Wred^T (GEMM, fp32 out)
 //   head   : LayerNorm + mean over tokens (one kernel) -> fp16 (".half()" of the reference loop) and/or fp32
-#include "common.h"
+#include "launch.h"
 #include "rowstream.h"
 #include <stdlib.h>
 
@@ -739,23 +739,18 @@ extern "C" int amds_swin_attn96(float* x, const void* qkv_w, const float* qkv_b,
     int gx = (int)((nwin + 3) / 4);
     if (gx > 256) gx = 256;
     ProfScope prof(PROF_ATTN, nwin * (2.0 * 49 * 96 * 384 + 4.0 * 3 * 49 * 49 * 32), st);
-#define ATTN96_LAUNCH(T)                                                                                                              \
-    do {                                                                                                                              \
-        static bool attr_set = false;                                                                                                 \
-        if (!attr_set) {                                                                                                              \
-            AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(swin_attn96_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, SA_LDS)); \
-            attr_set = true;                                                                                                          \
-        }                                                                                                                             \
-        hipLaunchKernelGGL((swin_attn96_kernel<T>), dim3(gx), dim3(256), SA_LDS, st, x, reinterpret_cast<const T*>(qkv_w), qkv_b,     \
-                           reinterpret_cast<const T*>(proj_w), proj_b, ln_gamma, ln_beta, bias_lane,                                  \
-                           reinterpret_cast<const unsigned long long*>(mask_bits), grid, shift, ln_eps, scale_l2, (int)nwin);         \
-    } while (0)
-    if (dtype == AMDS_F16) ATTN96_LAUNCH(f16);
-    else if (dtype == AMDS_BF16) ATTN96_LAUNCH(bf16);
-    else { set_error("amds_swin_attn96: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
-#undef ATTN96_LAUNCH
-    AMDS_LAUNCH_CHECK("swin_attn96_kernel");
-    return AMDS_OK;
+    int rc = AMDS_OK;
+    const bool ok = dispatch_16(dtype, &rc, [&](auto t) -> int {
+        typedef AMDS_TAG_T(t) T;
+        AMDS_HIP(lds_opt_in<swin_attn96_kernel<T>>(SA_LDS));
+        hipLaunchKernelGGL((swin_attn96_kernel<T>), dim3(gx), dim3(256), SA_LDS, st, x, reinterpret_cast<const T*>(qkv_w), qkv_b,
+                           reinterpret_cast<const T*>(proj_w), proj_b, ln_gamma, ln_beta, bias_lane,
+                           reinterpret_cast<const unsigned long long*>(mask_bits), grid, shift, ln_eps, scale_l2, (int)nwin);
+        AMDS_LAUNCH_CHECK("swin_attn96_kernel");
+        return AMDS_OK;
+    });
+    if (!ok) { set_error("amds_swin_attn96: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
+    return rc;
 }
 
 extern "C" int amds_patch_merge_ln(const float* x, void* y, const float* gamma, const float* beta, int B, int grid, int dim,
@@ -766,16 +761,13 @@ extern "C" int amds_patch_merge_ln(const float* x, void* y, const float* gamma, 
     const int rows = B * (grid / 2) * (grid / 2);
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof(PROF_LN, (double)rows * 4 * dim * 6, st);
-#define MERGE_LAUNCH(T)                                                                                                   \
-    do {                                                                                                                  \
-        if (dim <= 128) hipLaunchKernelGGL((swin_merge_ln_kernel<T, 2>), dim3(cdiv(rows, 4)), dim3(256), 0, st, x, (T*)y, gamma, beta, grid, dim, rows, eps); \
-        else if (dim <= 192) hipLaunchKernelGGL((swin_merge_ln_kernel<T, 3>), dim3(cdiv(rows, 4)), dim3(256), 0, st, x, (T*)y, gamma, beta, grid, dim, rows, eps); \
-        else hipLaunchKernelGGL((swin_merge_ln_kernel<T, 6>), dim3(cdiv(rows, 4)), dim3(256), 0, st, x, (T*)y, gamma, beta, grid, dim, rows, eps); \
-    } while (0)
-    if (dtype == AMDS_F16) MERGE_LAUNCH(f16);
-    else if (dtype == AMDS_BF16) MERGE_LAUNCH(bf16);
-    else { set_error("amds_patch_merge_ln: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
-#undef MERGE_LAUNCH
+    const bool ok = dispatch_16(dtype, [&](auto t) {
+        typedef AMDS_TAG_T(t) T;
+        if (dim <= 128) hipLaunchKernelGGL((swin_merge_ln_kernel<T, 2>), dim3(cdiv(rows, 4)), dim3(256), 0, st, x, (T*)y, gamma, beta, grid, dim, rows, eps);
+        else if (dim <= 192) hipLaunchKernelGGL((swin_merge_ln_kernel<T, 3>), dim3(cdiv(rows, 4)), dim3(256), 0, st, x, (T*)y, gamma, beta, grid, dim, rows, eps);
+        else hipLaunchKernelGGL((swin_merge_ln_kernel<T, 6>), dim3(cdiv(rows, 4)), dim3(256), 0, st, x, (T*)y, gamma, beta, grid, dim, rows, eps);
+    });
+    if (!ok) { set_error("amds_patch_merge_ln: bad dtype %d", dtype); return AMDS_ERR_INVALID; }
     AMDS_LAUNCH_CHECK("swin_merge_ln_kernel");
     return AMDS_OK;
 }

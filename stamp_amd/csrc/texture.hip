@@ -10,7 +10,7 @@
 //           outside the image, double threshold (m > high: edge; low < m <= high: candidate), 8-connected hysteresis.
 //   The hysteresis fixed point (candidates connected to an edge) does not depend on visiting order, so the stack walk of
 //   the CPU code becomes an in-LDS relaxation that repeats until no pixel changes.
-#include "common.h"
+#include "launch.h"
 #include <algorithm>
 #include <stdlib.h>
 
@@ -394,21 +394,13 @@ extern "C" int amds_tile_edge_fraction_u8(const uint8_t* tiles, float* frac, uin
     AMDS_REQUIRE(tiles && frac, "amds_tile_edge_fraction_u8: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)2 * S * S;
-    static bool attr_set = false;
-    if (!attr_set) {
-        AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tile_canny_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TEX_MAX_S * TEX_MAX_S));
-        attr_set = true;
-    }
+    AMDS_HIP(lds_opt_in<tile_canny_kernel>(2 * TEX_MAX_S * TEX_MAX_S));
     ProfScope prof(PROF_OTHER, (double)B * S * S * 3, st);
     // four pixels per thread and step when the rows split into dwords (S = 224 does); AMDS_CANNY_QUAD=0: the byte-at-a-time kernel (A/B, and any other S)
     static const bool quad_on = !(getenv("AMDS_CANNY_QUAD") && atoi(getenv("AMDS_CANNY_QUAD")) == 0);
     const bool quad = quad_on && S % 4 == 0 && S >= 8 && ((uintptr_t)tiles & 3) == 0 && (edges == nullptr || ((uintptr_t)edges & 3) == 0) && (gray == nullptr || ((uintptr_t)gray & 3) == 0);
     if (quad) {
-        static bool attr_q = false;
-        if (!attr_q) {
-            AMDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tile_canny_quad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TEX_MAX_S * TEX_MAX_S));
-            attr_q = true;
-        }
+        AMDS_HIP(lds_opt_in<tile_canny_quad_kernel>(2 * TEX_MAX_S * TEX_MAX_S));
         hipLaunchKernelGGL(tile_canny_quad_kernel, dim3(B), dim3(256), lds, st, tiles, frac, edges, gray, S, low, high);
     } else {
         hipLaunchKernelGGL(tile_canny_kernel, dim3(B), dim3(256), lds, st, tiles, frac, edges, gray, S, low, high);

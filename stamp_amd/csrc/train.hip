@@ -13,7 +13,7 @@
 //   amds_loss_scale_init / amds_grad_unscale_check / amds_adamw_guarded / amds_loss_scale_update
 //                             dynamic loss scaling of fp16 training: a device-resident state, the gradients unscaled and their non-finite
 //                             values counted in one pass, an AdamW step that a non-finite count turns into a no-op, the scale's back-off / growth
-#include "common.h"
+#include "launch.h"
 
 namespace amds {
 
@@ -579,10 +579,11 @@ static int colsum_stage1(const void* x, long ld, float* part, int M, int N, int 
     const int vec_ok = (ld % 4 == 0) && (((uintptr_t)x % (4 * esz)) == 0);      // 4-element vector loads need aligned rows
     // (Round 5 tried the second stage inside the first launch -- the block that arrives last for its 64 columns adds the chunk partials: the
     //  agent-scope fence that makes the partials of the other XCDs' L2s visible costs ~100 us per launch on this 8-XCD part, 6x the launch it saves.)
-    if (in_dtype == AMDS_F32) hipLaunchKernelGGL((colsum_partial_kernel<float>), grid, dim3(256), 0, st, (const float*)x, ld, part, M, N, vec_ok, cs_rows);
-    else if (in_dtype == AMDS_BF16) hipLaunchKernelGGL((colsum_partial_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)x, ld, part, M, N, vec_ok, cs_rows);
-    else if (in_dtype == AMDS_F16) hipLaunchKernelGGL((colsum_partial_kernel<f16>), grid, dim3(256), 0, st, (const f16*)x, ld, part, M, N, vec_ok, cs_rows);
-    else { set_error("amds_colsum: bad dtype"); return AMDS_ERR_INVALID; }
+    const bool ok = dispatch_16_32(in_dtype, [&](auto t) {
+        typedef AMDS_TAG_T(t) T;
+        hipLaunchKernelGGL((colsum_partial_kernel<T>), grid, dim3(256), 0, st, (const T*)x, ld, part, M, N, vec_ok, cs_rows);
+    });
+    if (!ok) { set_error("amds_colsum: bad dtype"); return AMDS_ERR_INVALID; }
     AMDS_LAUNCH_CHECK("colsum_partial_kernel");
     return AMDS_OK;
 }
@@ -651,20 +652,17 @@ extern "C" int amds_layernorm_train_copy(const float* x, long x_row_stride, cons
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(cdiv(rows, 4)), block(256);
     // float4 slots per lane by row width (2 = 512 columns: the MIL heads): the same arithmetic in a quarter of the registers
-#define AMDS_LN_TRAIN(TO_, MV)                                                                                                                \
-    hipLaunchKernelGGL((ln_train_kernel<TO_, MV>), grid, block, 0, st, x, x_row_stride, gamma, beta, (TO_*)y, y_row_stride, mean, rstd, rows, cols, eps, x_copy, copy_row_stride, copy_cols)
-#define AMDS_LN_TRAIN_W(TO_)                                   \
-    do {                                                       \
-        if (cols <= 512) AMDS_LN_TRAIN(TO_, 2);                \
-        else if (cols <= 1024) AMDS_LN_TRAIN(TO_, 4);          \
-        else AMDS_LN_TRAIN(TO_, 8);                            \
-    } while (0)
-    if (out_dtype == AMDS_BF16) AMDS_LN_TRAIN_W(bf16);
-    else if (out_dtype == AMDS_F16) AMDS_LN_TRAIN_W(f16);
-    else if (out_dtype == AMDS_F32) AMDS_LN_TRAIN_W(float);
-    else { set_error("amds_layernorm_train: bad dtype"); return AMDS_ERR_INVALID; }
-#undef AMDS_LN_TRAIN_W
-#undef AMDS_LN_TRAIN
+    const bool ok = dispatch_16_32(out_dtype, [&](auto t) {
+        typedef AMDS_TAG_T(t) TO;
+        auto launch = [&](auto mv) {
+            hipLaunchKernelGGL((ln_train_kernel<TO, decltype(mv)::value>), grid, block, 0, st, x, x_row_stride, gamma, beta, (TO*)y, y_row_stride, mean, rstd, rows, cols, eps,
+                               x_copy, copy_row_stride, copy_cols);
+        };
+        if (cols <= 512) launch(std::integral_constant<int, 2>{});
+        else if (cols <= 1024) launch(std::integral_constant<int, 4>{});
+        else launch(std::integral_constant<int, 8>{});
+    });
+    if (!ok) { set_error("amds_layernorm_train: bad dtype"); return AMDS_ERR_INVALID; }
     AMDS_LAUNCH_CHECK("ln_train_kernel");
     return AMDS_OK;
 }
@@ -690,24 +688,20 @@ int amds::layernorm_bwd_partials_dt(const float* dy, long dy_stride, const float
     AMDS_REQUIRE(dy && x && mean && rstd && gamma && dx && dgamma_part && dbeta_part, "amds_layernorm_bwd: null pointer");
     AMDS_REQUIRE(dx16_dtype == AMDS_BF16 || dx16_dtype == AMDS_F16, "amds_layernorm_bwd: the 16-bit copy is bf16 or fp16");
     AMDS_REQUIRE(!dx_bf16 || (dx_bf16_stride >= cols && dx_bf16_stride % 4 == 0 && p >= 0.f && p < 1.f), "amds_layernorm_bwd_cast: bad 16-bit output / rate");
-    const uint32_t dthr = (dx_bf16 && p > 0.f) ? drop_thr16(p) : 0;
-    const float dscale = dthr ? drop_scale(dthr) : 1.0f;
+    const DropParams d(dx_bf16 ? p : 0.f);                              // (p is checked, and used, only with the 16-bit copy)
     AMDS_REQUIRE(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "amds_layernorm_bwd: bad shape");
     hipStream_t st = (hipStream_t)stream;
     const int nblk = cdiv(rows, 64);
-#define AMDS_LN_BWD(MV)                                                                                                                                \
-    do {                                                                                                                                               \
-        if (dx16_dtype == AMDS_F16)                                                                                                                    \
-            hipLaunchKernelGGL((ln_bwd_kernel<MV, f16>), dim3(nblk), dim3(256), (size_t)8 * cols * 4, st, dy, dy_stride, x, x_stride, mean, rstd, gamma, dx, \
-                               dx_stride, add_skip, dgamma_part, dbeta_part, rows, cols, (f16*)dx_bf16, dx_bf16_stride, seed, stream_id, dthr, dscale);  \
-        else                                                                                                                                           \
-            hipLaunchKernelGGL((ln_bwd_kernel<MV, bf16>), dim3(nblk), dim3(256), (size_t)8 * cols * 4, st, dy, dy_stride, x, x_stride, mean, rstd, gamma, dx, \
-                               dx_stride, add_skip, dgamma_part, dbeta_part, rows, cols, (bf16*)dx_bf16, dx_bf16_stride, seed, stream_id, dthr, dscale); \
-    } while (0)
-    if (cols <= 512) AMDS_LN_BWD(2);
-    else if (cols <= 1024) AMDS_LN_BWD(4);
-    else AMDS_LN_BWD(8);
-#undef AMDS_LN_BWD
+    dispatch_16(dx16_dtype, [&](auto t) {
+        typedef AMDS_TAG_T(t) T16;
+        auto launch = [&](auto mv) {
+            hipLaunchKernelGGL((ln_bwd_kernel<decltype(mv)::value, T16>), dim3(nblk), dim3(256), (size_t)8 * cols * 4, st, dy, dy_stride, x, x_stride, mean, rstd, gamma, dx,
+                               dx_stride, add_skip, dgamma_part, dbeta_part, rows, cols, (T16*)dx_bf16, dx_bf16_stride, seed, stream_id, d.thr, d.scale);
+        };
+        if (cols <= 512) launch(std::integral_constant<int, 2>{});
+        else if (cols <= 1024) launch(std::integral_constant<int, 4>{});
+        else launch(std::integral_constant<int, 8>{});
+    });
     AMDS_LAUNCH_CHECK("ln_bwd_kernel");
     return AMDS_OK;
 }
@@ -746,12 +740,16 @@ extern "C" int amds_gelu_fwd(const void* z, void* u, long n, int in_dtype, int o
     if ((in_dtype == AMDS_BF16 || in_dtype == AMDS_F16) && n % 8 == 0 && (((uintptr_t)z | (uintptr_t)u) & 15) == 0)
         return amds_gelu_dropout_fwd(z, u, n, in_dtype, out_dtype, 0.f, 0, 0, stream);
     hipStream_t st = (hipStream_t)stream;
-    if (in_dtype == AMDS_BF16 && out_dtype == AMDS_BF16) hipLaunchKernelGGL((gelu_fwd_kernel<bf16, bf16>), dim3(grid1d(n)), dim3(256), 0, st, (const bf16*)z, (bf16*)u, n);
-    else if (in_dtype == AMDS_BF16 && out_dtype == AMDS_F32) hipLaunchKernelGGL((gelu_fwd_kernel<bf16, float>), dim3(grid1d(n)), dim3(256), 0, st, (const bf16*)z, (float*)u, n);
-    else if (in_dtype == AMDS_F16 && out_dtype == AMDS_F16) hipLaunchKernelGGL((gelu_fwd_kernel<f16, f16>), dim3(grid1d(n)), dim3(256), 0, st, (const f16*)z, (f16*)u, n);
-    else if (in_dtype == AMDS_F16 && out_dtype == AMDS_F32) hipLaunchKernelGGL((gelu_fwd_kernel<f16, float>), dim3(grid1d(n)), dim3(256), 0, st, (const f16*)z, (float*)u, n);
-    else if (in_dtype == AMDS_F32 && out_dtype == AMDS_F32) hipLaunchKernelGGL((gelu_fwd_kernel<float, float>), dim3(grid1d(n)), dim3(256), 0, st, (const float*)z, (float*)u, n);
-    else { set_error("amds_gelu_fwd: unsupported dtype pair"); return AMDS_ERR_INVALID; }
+    bool ok = false;                                                    // u in z's type or fp32
+    dispatch_16_32(in_dtype, [&](auto tz) { dispatch_16_32(out_dtype, [&](auto to) {
+        typedef AMDS_TAG_T(tz) TZ;
+        typedef AMDS_TAG_T(to) TO;
+        if constexpr (std::is_same_v<TO, TZ> || std::is_same_v<TO, float>) {
+            ok = true;
+            hipLaunchKernelGGL((gelu_fwd_kernel<TZ, TO>), dim3(grid1d(n)), dim3(256), 0, st, (const TZ*)z, (TO*)u, n);
+        }
+    }); });
+    if (!ok) { set_error("amds_gelu_fwd: unsupported dtype pair"); return AMDS_ERR_INVALID; }
     AMDS_LAUNCH_CHECK("gelu_fwd_kernel");
     return AMDS_OK;
 }
@@ -763,17 +761,16 @@ extern "C" int amds_gelu_bwd(const void* z, const void* du, void* dz, long n, in
         (((uintptr_t)z | (uintptr_t)du | (uintptr_t)dz) & 15) == 0)
         return amds_gelu_dropout_bwd(z, du, dz, n, z_dtype, du_dtype, dz_dtype, 0.f, 0, 0, stream);
     hipStream_t st = (hipStream_t)stream;
-    if (z_dtype == AMDS_BF16 && du_dtype == AMDS_BF16 && dz_dtype == AMDS_BF16)
-        hipLaunchKernelGGL((gelu_bwd_kernel<bf16, bf16, bf16>), dim3(grid1d(n)), dim3(256), 0, st, (const bf16*)z, (const bf16*)du, (bf16*)dz, n);
-    else if (z_dtype == AMDS_BF16 && du_dtype == AMDS_F32 && dz_dtype == AMDS_BF16)
-        hipLaunchKernelGGL((gelu_bwd_kernel<bf16, float, bf16>), dim3(grid1d(n)), dim3(256), 0, st, (const bf16*)z, (const float*)du, (bf16*)dz, n);
-    else if (z_dtype == AMDS_F16 && du_dtype == AMDS_F16 && dz_dtype == AMDS_F16)
-        hipLaunchKernelGGL((gelu_bwd_kernel<f16, f16, f16>), dim3(grid1d(n)), dim3(256), 0, st, (const f16*)z, (const f16*)du, (f16*)dz, n);
-    else if (z_dtype == AMDS_F16 && du_dtype == AMDS_F32 && dz_dtype == AMDS_F16)
-        hipLaunchKernelGGL((gelu_bwd_kernel<f16, float, f16>), dim3(grid1d(n)), dim3(256), 0, st, (const f16*)z, (const float*)du, (f16*)dz, n);
-    else if (z_dtype == AMDS_F32 && du_dtype == AMDS_F32 && dz_dtype == AMDS_F32)
-        hipLaunchKernelGGL((gelu_bwd_kernel<float, float, float>), dim3(grid1d(n)), dim3(256), 0, st, (const float*)z, (const float*)du, (float*)dz, n);
-    else { set_error("amds_gelu_bwd: unsupported dtype combination"); return AMDS_ERR_INVALID; }
+    bool ok = false;                                                    // dz in z's type; du in that type or fp32
+    if (dz_dtype == z_dtype) dispatch_16_32(z_dtype, [&](auto tz) { dispatch_16_32(du_dtype, [&](auto tg) {
+        typedef AMDS_TAG_T(tz) TZ;
+        typedef AMDS_TAG_T(tg) TG;
+        if constexpr (std::is_same_v<TG, TZ> || std::is_same_v<TG, float>) {
+            ok = true;
+            hipLaunchKernelGGL((gelu_bwd_kernel<TZ, TG, TZ>), dim3(grid1d(n)), dim3(256), 0, st, (const TZ*)z, (const TG*)du, (TZ*)dz, n);
+        }
+    }); });
+    if (!ok) { set_error("amds_gelu_bwd: unsupported dtype combination"); return AMDS_ERR_INVALID; }
     AMDS_LAUNCH_CHECK("gelu_bwd_kernel");
     return AMDS_OK;
 }

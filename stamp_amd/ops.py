@@ -62,8 +62,8 @@ def sync_float32_matmul_precision() -> str:
     before deployment (`deploy.py:398`), so a drop-in run gets the bf16 x 3 products exactly where the reference asked torch for cheaper ones.  Called by every
     host entry point in front of `amds_bgemm_f32` (TransMIL / Nystrom, the MLP heads' training GEMMs)."""
     level = torch.get_float32_matmul_precision()
-    dev = torch.cuda.current_device() if torch.cuda.is_available() else 0
-    _lib.check(_lib.lib().amds_set_matmul_precision(_lib.ctx(dev), 0 if level == "highest" else 1), "set_matmul_precision")
+    cx = _lib.ctx_of(None) if torch.cuda.is_available() else _lib.ctx(0)
+    _lib.check(_lib.lib().amds_set_matmul_precision(cx, 0 if level == "highest" else 1), "set_matmul_precision")
     return level
 
 
@@ -228,7 +228,7 @@ def set_mil_cls_tail(on: bool, device: int | None = None) -> bool:
     """The class-row tail of the MIL `vit` head / TransMIL deploy forward, a setting of the library's context of `device` (default: the current one;
     `amds_set_mil_cls_tail(ctx, on)`; default on, AMDS_MIL_CLS_TAIL=0 turns the default off): returns the previous setting."""
     lib = _lib.lib()
-    cx = _lib.ctx(torch.cuda.current_device() if device is None else device)
+    cx = _lib.ctx_of(device)
     prev = bool(lib.amds_get_mil_cls_tail(cx))
     _lib.check(lib.amds_set_mil_cls_tail(cx, 1 if on else 0), "set_mil_cls_tail")
     return prev

@@ -187,7 +187,7 @@ def forward_train(get, bags: torch.Tensor, dims: tuple[int, int, int], *, traini
     bags = bags.contiguous()
     lib = _lib.lib()
     # resolved HERE so that the backward of this step reads the arena the way this forward wrote it, whatever the context says by then
-    cfg = _lib.TransMilCfg(Fd, Cd, Cc, 1 if lib.amds_get_mil_cls_tail(_lib.ctx(dev.index if dev.index is not None else torch.cuda.current_device())) else 0)
+    cfg = _lib.TransMilCfg(Fd, Cd, Cc, 1 if lib.amds_get_mil_cls_tail(_lib.ctx_of(dev)) else 0)
     w, keep = _c_weights(get, Cd)
     need = lib.amds_transmil_train_saved_bytes(C.byref(cfg), Bb, Tn)
     if need == 0:

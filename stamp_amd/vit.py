@@ -245,7 +245,7 @@ class HipViT(nn.Module):
         if self.device_.type != "cuda":
             raise RuntimeError("HipViT runs on the GPU only (no CPU fallback)")
         _lib.lib()  # fail early and loudly if the extension is missing
-        _lib.ctx(self.device_.index if self.device_.index is not None else torch.cuda.current_device())   # side stream of the ragged-tail schedule
+        _lib.ctx_of(self.device_)   # side stream of the ragged-tail schedule
         self._ws: torch.Tensor | None = None
         # LayerNorm folded into the qkv / fc1 GEMMs (include/amdstamp.h, amds_gemm_lnfold): default on where the shapes allow it
         # (every preset); AMDS_VIT_LNFOLD=0 or ln_fold=False packs the plain weights and runs the stand-alone LayerNorm kernels (A/B).
@@ -484,7 +484,7 @@ class HipViT(nn.Module):
             if self._ws is None or self._ws.numel() < need:
                 self._ws = torch.empty(need, dtype=torch.uint8, device=self.device_)
             self._ws_chunk = None           # (the two-stream schedule keeps two plans in the buffer; the range counters are not read back from it)
-            rc = _lib.lib().amds_vit_forward_overlapped(_lib.ctx(tiles.device.index or 0), C.byref(self._cfg_c), C.byref(self._w_c), tiles.data_ptr(), feats.data_ptr(),
+            rc = _lib.lib().amds_vit_forward_overlapped(_lib.ctx_of(tiles.device), C.byref(self._cfg_c), C.byref(self._w_c), tiles.data_ptr(), feats.data_ptr(),
                                                         B, chunk, self._ws.data_ptr(), self._ws.numel(),
                                                         torch.cuda.current_stream().cuda_stream)
             _lib.check(rc, "vit_forward_overlapped")

@@ -38,6 +38,23 @@ def test_ops_refuse_cpu_tensors():
         HipViT(PRESETS["test_tiny"], random_vit_state_dict(PRESETS["test_tiny"]), device="cpu")
 
 
+def test_ctx_of_resolves_an_indexless_device_to_the_current_device(monkeypatch):
+    """`_lib.ctx_of`: None and an index-less CUDA device mean torch's CURRENT device (a context on GPU 0 would carry another card's settings);
+    an explicit index -- torch.device or int -- is honoured; one context per device."""
+    from stamp_amd import _lib
+
+    created = []
+    monkeypatch.setattr(_lib, "_ctx", {})
+    monkeypatch.setattr(_lib.lib(), "amds_create", lambda device: created.append(device) or 1000 + device)
+    monkeypatch.setattr(torch.cuda, "current_device", lambda: 3)
+    assert _lib.ctx_of(torch.device("cuda")) == 1003
+    assert _lib.ctx_of(None) == 1003
+    assert _lib.ctx_of(torch.device("cuda:1")) == 1001
+    assert _lib.ctx_of(torch.device("cuda", 0)) == 1000
+    assert _lib.ctx_of(2) == 1002
+    assert created == [3, 1, 0, 2]
+
+
 def test_product_never_imports_oracle():
     for p in (ROOT / "stamp_amd").rglob("*.py"):
         src = p.read_text()

@@ -265,6 +265,115 @@ def test_attention_row_alibi_train_forms(gpu, dt, B, T, H):
     assert rel(r["dbs"].sum(0), bsd.grad) < 1.6e-2
 
 
+_BIG_T = 16384          # row kernels: LDS (T + 1032) * 4 = 69 664 bytes, ALiBi row forward (2 T + 2056) * 4 = 139 296: past the 64 KB a kernel gets without an opt-in
+_big_mask_row = {}
+
+
+def _big_mask_row0(gpu, p, seed, sid):
+    """Row 0 of the [1, 1, T, T] attention dropout mask at _BIG_T (the whole tensor is written on the device, 268 MB of u8; one row comes back), once per rate."""
+    if p not in _big_mask_row:
+        m = torch.empty(1, 1, _BIG_T, _BIG_T, dtype=torch.uint8, device=gpu)
+        _lib.check(_lib.lib().amds_attention_dropout_mask(_p(m), 1, 1, _BIG_T, p, seed, sid, _st()), "mask")
+        _big_mask_row[p] = m[0, 0, 0].cpu().double() * _lib.lib().amds_dropout_keep_scale(p)
+        del m
+    return _big_mask_row[p]
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_attention_row_forms_past_64k_of_lds(gpu, dt):
+    """The one-query kernels at B = 1, H = 1, T = 16384, where their dynamic LDS request passes 64 KB and the launch depends on the per-device opt-in:
+    amds_attention_row_varlen with one bag of 16 383 tiles bit-equal to amds_attention_row on the same rows; amds_attention_row_fwd_train / _bwd_train at p = 0 and
+    0.25; amds_attention_row_alibi_fwd_train / _bwd_train.  Reference: fp64 autograd of the ONE row, softmax(q_0 K^T / 8) times the regenerated mask row, then @ V
+    (the full T x T product would be 2 GB of doubles).  Bars of the small-shape tests above: 4 ulp forward row, 8 ulp dqkv; ALiBi 8e-3 / 1.6e-2 relative L2."""
+    lib, T, seed, sid = _lib.lib(), _BIG_T, 99, 11
+    D, code = 64, ops.act_code(dt)
+    qkv0, g = _qkv(1, T, 1, dt, 16384 + 7, scale=1.0)
+    dout_row = torch.randn(D, generator=g).to(dt)
+
+    # ---- ragged form == fixed-pitch form, bit for bit
+    offs0 = torch.tensor([0, T - 1], dtype=torch.int32)
+    need = lib.amds_attention_varlen_workspace_bytes(1, T - 1)
+
+    def call_varlen(pattern):
+        b = Bufs(gpu, pattern)
+        qkv, offs, ws = b.inp(qkv0, name="qkv"), b.inp(offs0, name="offsets"), b.out((need,), torch.uint8, name="ws")
+        q = b.inp(qkv0[:1, :D], D + 8, "q")
+        o_var, o_row = b.out((1, D), dt, D + 8, name="out varlen"), b.out((1, D), dt, D + 8, name="out row")
+        _lib.check(lib.amds_attention_row_varlen(_p(q), D + 8, _p(qkv), _p(offs), _p(o_var), D + 8, 1, T - 1, T - 1, 1, code, _p(ws), need, _st()), "row_varlen")
+        _lib.check(lib.amds_attention_row(_p(q), D + 8, _p(qkv), _p(o_row), D + 8, 1, T, 1, code, _st()), "row")
+        return b.result(varlen=o_var, row=o_row)
+
+    r = G.run_contract(call_varlen)
+    assert torch.equal(r["varlen"], r["row"])
+    print(f"big-LDS row forms {dt}:", end=" ")
+
+    def row_ref(mult):
+        x = qkv0.double().requires_grad_(True)
+        w = torch.softmax(x[:1, :D] @ x[:, D:2 * D].T / 8.0, -1)
+        o = ((w if mult is None else w * mult) @ x[:, 2 * D:]).reshape(D)
+        o.backward(dout_row.double())
+        return o.detach(), x.grad
+
+    o0, _ = row_ref(None)
+    err = (r["row"].double().cpu().reshape(D) - o0).abs().max().item()
+    print(f"row fwd {err / _eps(dt):.3f} ulp", end="; ")
+    assert err < 4 * _eps(dt) * max(1.0, o0.abs().max().item())
+
+    # ---- training forms, without and with dropout
+    for p in (0.0, 0.25):
+        o, dref = row_ref(_big_mask_row0(gpu, p, seed, sid) if p > 0 else None)
+
+        def call_train(pattern):
+            b = Bufs(gpu, pattern)
+            qkv, dout = b.inp(qkv0, name="qkv"), b.out((T, D), dt, name="dout")
+            dout[0] = dout_row.to(gpu)                                                   # only the query row of dout is read: the rest stays poisoned
+            out, lse, dqkv = b.out((T, D), dt, name="out"), b.out((1, 1, T), torch.float32, name="lse"), b.out((T, 3 * D), dt, name="dqkv")
+            _lib.check(lib.amds_attention_row_fwd_train(_p(qkv), _p(out), _p(lse), 1, T, 1, 0, code, p, seed, sid, _st()), "row_fwd_train")
+            _lib.check(lib.amds_attention_row_bwd_train(_p(qkv), _p(out), _p(dout), _p(lse), _p(dqkv), 1, T, 1, 0, code, p, seed, sid, _st()), "row_bwd_train")
+            return b.result(out_row=out[0], lse_row=lse[:, :, 0], dqkv=dqkv)
+
+        rt = {k_: v.double().cpu() for k_, v in G.run_contract(call_train).items()}
+        ef, eb = (rt["out_row"] - o).abs().max().item(), (rt["dqkv"] - dref).abs().max().item()
+        print(f"p={p}: fwd {ef / _eps(dt):.3f} ulp, dqkv {eb / (_eps(dt) * max(1.0, dref.abs().max().item())):.3f} ulp", end="; ")
+        assert ef < 4 * _eps(dt) * max(1.0, o.abs().max().item())
+        assert eb < 8 * _eps(dt) * max(1.0, dref.abs().max().item())
+
+    # ---- ALiBi row forms (the class token at the origin)
+    qa0, g = _qkv(1, T, 1, dt, 16384 + 11, scale=0.8)
+    coords0 = torch.rand(T, 2, generator=g) * 4000.0
+    coords0[0] = 0.0
+    bs0, rm = torch.rand(1, generator=g) * 0.5 + 0.1, torch.rand(1, generator=g) * 500.0 + 1800.0
+    da_row = (torch.randn(D, generator=g) * 0.5).to(dt)
+    x = qa0.double().requires_grad_(True)
+    bsd = bs0.double().clone().requires_grad_(True)
+    w = torch.softmax(x[:1, :D] @ x[:, D:2 * D].T / 8.0, -1) - (coords0.double().norm(dim=-1)[None, :] / rm.double()) * bsd
+    ref = (w @ x[:, 2 * D:]).reshape(D)
+    ref.backward(da_row.double())
+
+    def call_alibi(pattern):
+        b = Bufs(gpu, pattern)
+        qkv, coords = b.inp(qa0, name="qkv"), b.inp(coords0, name="coords")
+        inv_rm, bs = b.inp(1.0 / rm, name="inv_rm"), b.inp(bs0, name="bias_scale")
+        dout = b.out((T, D), dt, name="dout")
+        dout[0] = da_row.to(gpu)
+        out, u, osm = (b.out((T, D), dt, name=n) for n in ("out", "u", "osm"))
+        lse, dqkv, dbs = b.out((1, 1, T), torch.float32, name="lse"), b.out((T, 3 * D), dt, name="dqkv"), b.out((1, 1), torch.float32, name="dbs")
+        _lib.check(lib.amds_attention_row_alibi_fwd_train(_p(qkv), _p(coords), _p(inv_rm), _p(bs), _p(out), _p(u), _p(osm), _p(lse), 1, T, 1, 0, code, _st()), "fwd")
+        _lib.check(lib.amds_attention_row_alibi_bwd_train(_p(qkv), _p(osm), _p(u), _p(dout), _p(lse), _p(coords), _p(bs), _p(inv_rm), _p(dqkv), _p(dbs), 1, T, 1, 0, code,
+                                                          _st()), "bwd")
+        return b.result(out_row=out[0], u_row=u[0], osm_row=osm[0], lse_row=lse[:, :, 0], dqkv=dqkv, dbs=dbs)
+
+    ra = {k_: v.double().cpu() for k_, v in G.run_contract(call_alibi).items()}
+    rel = lambda a, c: ((a - c).norm() / (c.norm() + 1e-30)).item()  # noqa: E731
+    d3, g3 = ra["dqkv"].reshape(T, 3, D), x.grad.reshape(T, 3, D)
+    rels = [rel(ra["out_row"], ref.detach())] + [rel(d3[:, i], g3[:, i]) for i in range(3)] + [rel(ra["dbs"].sum(0), bsd.grad)]
+    print("alibi rel L2 out / dq / dk / dv / dbs " + " ".join(f"{v:.2e}" for v in rels))
+    assert rels[0] < 8e-3
+    for i in range(3):
+        assert rels[1 + i] < 8e-3, i
+    assert rels[4] < 1.6e-2
+
+
 @pytest.mark.parametrize("dt", DTYPES)
 def test_attention_masked(gpu, dt):
     """amds_attention_masked at (3, 129, 4), mask_heads 3 (one zero-padded head): blocked(q, k) = (pad[q] & pad[k]) | (q > 0 & k == 0) with the pad row of bag

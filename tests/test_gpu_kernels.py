@@ -239,7 +239,7 @@ def test_attention_streaming_any_length(gpu, dt, B, T, H):
 
 
 @pytest.mark.parametrize("dt", DTYPES)
-@pytest.mark.parametrize("B,T,H", [(3, 1025, 8), (2, 212, 4), (1, 1, 1), (5, 63, 2), (2, 5000, 3)])
+@pytest.mark.parametrize("B,T,H", [(3, 1025, 8), (2, 212, 4), (1, 1, 1), (5, 63, 2), (2, 5000, 3), (1, 16384, 1)])
 def test_attention_row_is_the_class_tokens_row_of_the_full_attention(gpu, dt, B, T, H):
     """amds_attention_row: ONE query per (bag, head) against all keys / values of the packed qkv -- the class token's attention in the last block of the MIL `vit`
     head, whose other rows nothing reads (vision_tranformer.py: the head takes x[:, 0]).  Against fp64 softmax(q k^T / 8) v on the same 16-bit inputs (its weights
@@ -252,9 +252,11 @@ def test_attention_row_is_the_class_tokens_row_of_the_full_attention(gpu, dt, B,
     qq, k, v = qkv.double().reshape(B, T, 3, H, 64).permute(2, 0, 3, 1, 4)
     ref = (torch.softmax(qq[:, :, :1] @ k.transpose(-1, -2) / 8.0, -1) @ v).reshape(B, D)
     tol = 2 * _eps(dt) * max(1.0, ref.abs().max().item())
-    assert (out.double() - ref).abs().max().item() < tol
     full = ops.attention(qkv, B, T, H).view(B, T, D)[:, 0]
-    assert (out.double() - full.double()).abs().max().item() < 4 * _eps(dt) * max(1.0, ref.abs().max().item())
+    e_ref, e_full = (out.double() - ref).abs().max().item(), (out.double() - full.double()).abs().max().item()
+    print(f"attention_row {dt} B={B} T={T} H={H}: {e_ref / (tol / 2):.3f} ulp vs fp64 (bar 2), {e_full / (tol / 2):.3f} ulp vs the streaming kernel (bar 4)")
+    assert e_ref < tol
+    assert e_full < 4 * _eps(dt) * max(1.0, ref.abs().max().item())
     assert torch.equal(out, ops.attention_row(q, qkv, B, T, H))
 
 
