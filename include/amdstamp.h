@@ -671,6 +671,57 @@ int amds_ticon_tile_forward(const amds_ticon_weights* w_host, const void* emb, i
 /* ws: contents on entry are ignored (the call initialises every byte it reads);
  *     nothing outside [ws, ws + amds_ticon_tile_workspace_bytes) is written. */
 
+/* SLIDE mode: the same `EncoderDecoder.forward` (:543-562, :504-506) on all tiles of a slide with their coordinates -- what the model is for: every tile
+ * attends to the other tiles of its slide under a distance bias inside the softmax (`Attention.forward` :183-215).
+ *   x = LayerNorm(fc2(silu(fc1(emb))))                                          input_proj_<key>   :94-98
+ *   depth x [ x += g1 * proj(attn(LN(x)));  x += g2 * fc2(silu(x1) * x2) ]      :329-343, :262, :73-76
+ *   out = enc_norm(x)                                                           :506
+ * Residual stream fp32; every Linear an MFMA GEMM on cfg.dtype operands (amds_gemm), the MLP through AMDS_EPI_SWIGLU, LayerScale + add through
+ * AMDS_EPI_RESIDUAL, the attention amds_attention_distbias.  Padded sizes: Fp / Dp = in_dim / dim rounded up to 256, Ha = heads rounded up to 4, Da = 64 Ha,
+ * Hp = hidden / 2 rounded up to 128; padding rows, columns and heads are zero (amds_cast_pad).  16-bit matrices are [N][K] row-major in cfg.dtype. */
+
+/* out[b*T + q][h*64..] = softmax_k(q . k / 8 - slopes[h] * |c_q - c_k|_2) v over the T tokens of slide b: qkv [B*T][3*H*64] 16-bit as for amds_attention,
+ * coords fp32 [B][T][2], slopes fp32 [H], out 16-bit [B*T][H*64] in the operand type.  Distances in fp32 from the coordinates, nothing T x T is stored.
+ * head_dim < 64 as in the MIL heads: zero-padded heads, q rows scaled by sqrt(64 / head_dim).  Shapes as amds_attention. */
+int amds_attention_distbias(const void* qkv, const float* coords, const float* slopes, void* out, int B, int T, int H, int dtype, void* stream);
+
+typedef struct {
+    int in_dim;     /* width of the tile encoder's features (input_proj_<key>.fc1.in_features) */
+    int dim;        /* embed_dim (head_dim = dim / heads <= 64, dim % 4 == 0, dim <= 8192) */
+    int heads;
+    int hidden;     /* Mlp.fc1.out_features = int(dim * 16 / 3) (:58-66), even */
+    int depth;      /* encoder blocks */
+    int dtype;      /* MFMA operand type of the 16-bit weights below: AMDS_F16 or AMDS_BF16 */
+} amds_ticon_slide_cfg;
+typedef struct {
+    const float* ln1_w; const float* ln1_b;        /* [dim]                residual1.norm                                                      */
+    const void* in_w;   const float* in_b;         /* [3 Da][Dp], [3 Da]   residual1.fn.q_proj | k_proj | v_proj, head h at rows 64h..64h+63;
+                                                    *                      head_dim < 64: q rows scaled by sqrt(64 / head_dim)                 */
+    const void* proj_w; const float* proj_b;       /* [Dp][Da], [Dp]       residual1.fn.proj                                                   */
+    const float* g1;                               /* [Dp]                 residual1.gamma (LayerScale), or NULL = 1                           */
+    const float* ln2_w; const float* ln2_b;        /* [dim]                residual2.norm                                                      */
+    const void* fc1_w;  const float* fc1_b;        /* [2 Hp][Dp], [2 Hp]   residual2.fn.fc1: the x1 and the x2 rows each zero padded to Hp,
+                                                    *                      then interleaved by amds_pack_swiglu_rows(H = Hp)                   */
+    const void* fc2_w;  const float* fc2_b;        /* [Dp][Hp], [Dp]       residual2.fn.fc2                                                    */
+    const float* g2;                               /* [Dp]                 residual2.gamma, or NULL = 1                                        */
+} amds_ticon_slide_block;
+typedef struct {
+    const void* in_fc1_w; const float* in_fc1_b;   /* [Dp][Fp], [Dp]       input_proj_<key>.fc1                                                */
+    const void* in_fc2_w; const float* in_fc2_b;   /* [Dp][Dp], [Dp]       input_proj_<key>.fc2                                                */
+    const float* in_norm_w; const float* in_norm_b;/* [dim]                input_proj_<key>.norm                                               */
+    const float* slopes;                           /* [Ha]                 get_slopes(heads) :102-119, zero padded                             */
+    const amds_ticon_slide_block* blocks_host;     /* HOST array of cfg.depth entries (encoder.blocks)                                         */
+    const float* norm_w; const float* norm_b;      /* [dim]                enc_norm                                                            */
+} amds_ticon_slide_weights;
+size_t amds_ticon_slide_workspace_bytes(const amds_ticon_slide_cfg* cfg_host, int n_slides, int n_tiles);
+/* emb: [n_slides][n_tiles][in_dim] AMDS_F32 / AMDS_F16; coords: fp32 [n_slides][n_tiles][2] in the unit the model was trained on; out:
+ * [n_slides][n_tiles][dim] in out_dtype (AMDS_F32 or AMDS_F16).  Every slide of a call has n_tiles tiles; a slide's rows do not depend on the other
+ * slides of the call.  n_tiles * 3 * Ha * 128 < 2^31.  Launches only, on `stream`; ws 256-byte aligned. */
+int amds_ticon_slide_forward(const amds_ticon_slide_cfg* cfg_host, const amds_ticon_slide_weights* w_host, const void* emb, int emb_dtype,
+                             const float* coords, void* out, int out_dtype, int n_slides, int n_tiles, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_ticon_slide_workspace_bytes) is written. */
+
 /* ------------------------------------------------------------------------------------------------
  * Gated-attention pooling (CHIEF slide encoder; reference
  * src/stamp/encoding/encoder/chief.py:74-89 CHIEFModel.forward, :255-275 Attn_Net_Gated)

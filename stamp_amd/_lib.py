@@ -184,6 +184,19 @@ _vp, _i, _l, _f, _sz = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
 _u64, _u32 = C.c_uint64, C.c_uint32
 
 # name -> (restype, argtypes); must list every symbol include/amdstamp.h declares
+class TiconSlideCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("in_dim", "dim", "heads", "hidden", "depth", "dtype")]
+
+
+class TiconSlideBlock(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("ln1_w", "ln1_b", "in_w", "in_b", "proj_w", "proj_b", "g1", "ln2_w", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "g2")]
+
+
+class TiconSlideWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("in_fc1_w", "in_fc1_b", "in_fc2_w", "in_fc2_b", "in_norm_w", "in_norm_b", "slopes")] + \
+               [("blocks_host", C.POINTER(TiconSlideBlock)), ("norm_w", C.c_void_p), ("norm_b", C.c_void_p)]
+
+
 PROTOTYPES = {
     "amds_version": (_i, []),
     "amds_last_error": (C.c_char_p, []),
@@ -271,6 +284,9 @@ PROTOTYPES = {
     "amds_barspoon_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "amds_ticon_tile_workspace_bytes": (_sz, [_vp, _i]),
     "amds_ticon_tile_forward": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _sz, _vp]),
+    "amds_attention_distbias": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "amds_ticon_slide_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "amds_ticon_slide_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     "amds_tile_resize_crop_workspace_bytes": (_sz, [_i, _i, _i]),
     "amds_tile_resize_crop_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _sz, _vp]),
     "amds_proj_head_l2norm_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -54,7 +54,12 @@ __device__ __forceinline__ int attn_swz(int row) { return (((row >> 1) & 1) << 2
 // (bag, 128-query block) work items built once per call from the bag offsets (varlen_plan_kernel): blockIdx.x indexes `vwork`, item = {first token row of
 // the bag, its token count Tn, q block, -}; Tn = 0 marks the slack at the end of the list (the host sizes the grid by a bound, not by the device-side sum).
 // Everything else is the fixed-pitch kernel: the same arithmetic per (bag, head, query) whatever the bag's neighbours.
-template <typename T, bool ALIBI, typename TO = T, bool MASK = false, bool DROP = false, bool VARLEN = false>
+//
+// DBIAS (inference; no ALIBI / MASK / DROP / VARLEN): the distance bias INSIDE the softmax, TICON's `Attention` (src/stamp/preprocessing/extractor/ticon.py:183-215,
+// :152-154):  out = softmax(q k^T / 8 - slope_h * |c_q - c_k|) v,  slope_h = head_scale[h] (get_slopes :102-119).  Key coordinates are staged like the ALiBi
+// variant's, the query's stay in registers, distances are fp32 and the logit is formed in the log2 domain before the running maximum (the bias moves the maximum).
+// Keys past the sequence get -inf AFTER the bias: their zero V rows would not make a finite weight harmless to the normaliser.
+template <typename T, bool ALIBI, typename TO = T, bool MASK = false, bool DROP = false, bool VARLEN = false, bool DBIAS = false>
 __global__ void __launch_bounds__(256, 2) attn_flash_kernel(const T* __restrict__ qkv, TO* __restrict__ out, int Tn, int H,
                                                             const float* __restrict__ coords, const float* __restrict__ head_scale,
                                                             float* __restrict__ lse_out, const float* __restrict__ out_scale = nullptr,
@@ -63,6 +68,8 @@ __global__ void __launch_bounds__(256, 2) attn_flash_kernel(const T* __restrict_
                                                             uint32_t thr16 = 0, float keep_scale = 1.f, int mask_heads = 0,
                                                             const int4* __restrict__ vwork = nullptr) {
     static_assert(!(VARLEN && (MASK || DROP)), "the ragged form is the inference forward only");
+    static_assert(!(DBIAS && (ALIBI || MASK || DROP || VARLEN)), "the pre-softmax distance bias is a plain inference forward");
+    constexpr bool COORDS = ALIBI || DBIAS;                              // token coordinates are staged with the K / V tiles
     typedef typename Act<T>::vec8 vec8;
     constexpr int F2_STAGE = 2 * FA_K_BYTES + FA_C_BYTES;                // K rows | V rows | key coordinates (ALiBi)
     __shared__ __attribute__((aligned(16))) char smem[2 * F2_STAGE + (MASK ? 2 * FA_KT : 0)];
@@ -89,8 +96,8 @@ __global__ void __launch_bounds__(256, 2) attn_flash_kernel(const T* __restrict_
     // ALiBi: the tile's 128 coordinate dwords by waves 0 and 1.  Only the padding flags (bytes at an odd stride) still travel through a register.
     const __amdgpu_buffer_rsrc_t rsrc_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base + Dm), 0, (int)((((long)Tn - 1) * ld + 64) * 2), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsrc_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base + 2 * Dm), 0, (int)((((long)Tn - 1) * ld + 64) * 2), 0x00020000);
-    const float* cbase = ALIBI ? coords + row0 * 2 : nullptr;
-    const __amdgpu_buffer_rsrc_t rsrc_c = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ALIBI ? cbase : head_scale), 0, ALIBI ? Tn * 8 : 0, 0x00020000);
+    const float* cbase = COORDS ? coords + row0 * 2 : nullptr;
+    const __amdgpu_buffer_rsrc_t rsrc_c = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(COORDS ? cbase : head_scale), 0, COORDS ? Tn * 8 : 0, 0x00020000);
     uint8_t mreg = 0;
     const uint8_t* prow = nullptr;
     if constexpr (MASK) prow = pad + (long)(ALIBI ? b : (int)(((long)b * mask_heads + min(h, mask_heads - 1)) % gridDim.z)) * Tn;
@@ -103,7 +110,7 @@ __global__ void __launch_bounds__(256, 2) attn_flash_kernel(const T* __restrict_
             bufl16(rsrc_k, sK + (wave + 4 * pc) * 1024, vo, (j * FA_KT + 32 * pc) * (int)ld * 2);
             bufl16(rsrc_v, sK + FA_K_BYTES + (wave + 4 * pc) * 1024, vo, (j * FA_KT + 32 * pc) * (int)ld * 2);
         }
-        if constexpr (ALIBI) {
+        if constexpr (COORDS) {
             if (wave < 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_c, (lptr_t)(sK + 2 * FA_K_BYTES + wave * 256), 4, lane * 4, j * FA_KT * 8 + wave * 256, 0, 0);
         }
         if constexpr (MASK) {
@@ -131,7 +138,8 @@ __global__ void __launch_bounds__(256, 2) attn_flash_kernel(const T* __restrict_
         for (int r = 0; r < 16; ++r) { o[dt][r] = 0.f; o2[dt][r] = 0.f; }
     float mrun = -INFINITY, l = 0.f;
     float xq = 0.f, yq = 0.f, sh = 0.f;
-    if constexpr (ALIBI) { xq = cbase[(long)qc * 2]; yq = cbase[(long)qc * 2 + 1]; sh = head_scale[h]; }
+    if constexpr (COORDS) { xq = cbase[(long)qc * 2]; yq = cbase[(long)qc * 2 + 1]; sh = head_scale[h]; }
+    if constexpr (DBIAS) sh *= 1.44269504088896340736f;                  // the bias joins the scores in the log2 domain
     const float sc = 0.125f * 1.44269504088896340736f;
     const int swz = attn_swz(l31);
     // transpose reads of the V image (attention_train.hip): lane i of 16-lane group g hands in (key row (i >> 2) of the 4, 8-byte piece i & 3 of its 32 bytes)
@@ -180,6 +188,17 @@ __global__ void __launch_bounds__(256, 2) attn_flash_kernel(const T* __restrict_
         }
         const int key0 = j * FA_KT;
         const bool ragged = key0 + FA_KT > Tn;
+        if constexpr (DBIAS) {               // s <- log2(e) * (s / 8 - slope_h * dist): from here on the scores are final logits in the log2 domain
+            const float* sC = reinterpret_cast<const float*>(sV + FA_K_BYTES);
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int kl = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    const float dx = xq - sC[kl * 2], dy = yq - sC[kl * 2 + 1];
+                    s[t][r] = fmaf(s[t][r], sc, -sh * dist_sqrt(fmaf(dx, dx, dy * dy)));
+                }
+        }
         if (ragged) {
 #pragma unroll
             for (int t = 0; t < 2; ++t)
@@ -209,7 +228,7 @@ __global__ void __launch_bounds__(256, 2) attn_flash_kernel(const T* __restrict_
 #pragma unroll
             for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[t][r]);
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        float mnew = fmaxf(mrun, mx * sc);
+        float mnew = fmaxf(mrun, DBIAS ? mx : mx * sc);
         float msafe = mnew;
         if constexpr (MASK) msafe = (mnew == -INFINITY) ? 0.f : mnew;       // a query whose keys so far are all blocked
         const float alpha = __builtin_amdgcn_exp2f(mrun - msafe);
@@ -220,7 +239,7 @@ __global__ void __launch_bounds__(256, 2) attn_flash_kernel(const T* __restrict_
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float p = __builtin_amdgcn_exp2f(fmaf(s[t][r], sc, -mnew));
+                const float p = __builtin_amdgcn_exp2f(DBIAS ? s[t][r] - mnew : fmaf(s[t][r], sc, -mnew));
                 s[t][r] = p;
                 ls += p;
             }
@@ -748,7 +767,7 @@ struct FlashOpt {
 
 // One launch of the streaming kernel: grid, profiler scope and the dtype ladder.  The variant is the entry's (template flags), the operand type the call's;
 // OUT_AS_IN = false: bf16 out / U / Osm whatever the operands (the ALiBi forms, see the kernel comment).  `who` names the entry in the dtype message.
-template <bool ALIBI, bool MASK = false, bool DROP = false, bool VARLEN = false, bool OUT_AS_IN = !ALIBI>
+template <bool ALIBI, bool MASK = false, bool DROP = false, bool VARLEN = false, bool OUT_AS_IN = !ALIBI, bool DBIAS = false>
 static int flash_launch(const char* who, const char* kname, const void* qkv, void* out, int B, int T, int H, int dtype, const FlashOpt& o, hipStream_t st) {
     const dim3 grid(VARLEN ? o.n_work : (unsigned)((T + 127) / 128), H, B), block(256);
     std::optional<ProfScope> prof;          // (the ragged forms are timed by their callers)
@@ -757,7 +776,7 @@ static int flash_launch(const char* who, const char* kname, const void* qkv, voi
     const bool ok = dispatch_16(dtype, [&](auto t) {
         typedef AMDS_TAG_T(t) TI;
         typedef std::conditional_t<OUT_AS_IN, TI, bf16> TO;
-        hipLaunchKernelGGL((attn_flash_kernel<TI, ALIBI, TO, MASK, DROP, VARLEN>), grid, block, 0, st, (const TI*)qkv, (TO*)out, T, H, o.coords, o.head_scale, o.lse,
+        hipLaunchKernelGGL((attn_flash_kernel<TI, ALIBI, TO, MASK, DROP, VARLEN, DBIAS>), grid, block, 0, st, (const TI*)qkv, (TO*)out, T, H, o.coords, o.head_scale, o.lse,
                            o.bias_scale, (TO*)o.u, (TO*)o.osm, o.pad, o.seed, o.stream_id, d.thr, d.scale, o.mask_heads, o.vwork);
     });
     if (!ok) { set_error("%s: bad dtype %d", who, dtype); return AMDS_ERR_INVALID; }
@@ -908,6 +927,17 @@ extern "C" int amds_attention_alibi(const void* qkv, const float* coords, const 
     o.coords = coords;
     o.head_scale = head_scale;
     return flash_launch<true>("amds_attention_alibi", "attn_flash_kernel<alibi>", qkv, out, B, T, H, dtype, o, (hipStream_t)stream);
+}
+
+// TICON's attention (kernel comment, DBIAS): the distance bias before the softmax; out in the operand type
+extern "C" int amds_attention_distbias(const void* qkv, const float* coords, const float* slopes, void* out, int B, int T, int H, int dtype, void* stream) {
+    AMDS_REQUIRE(qkv && out && coords && slopes, "amds_attention_distbias: null pointer");
+    AMDS_REQUIRE(B >= 0 && T > 0 && H > 0 && H <= 65535 && B <= 65535 && FA_SPAN_OK(T, H), "amds_attention_distbias: bad shape B=%d T=%d H=%d", B, T, H);
+    if (B == 0) return AMDS_OK;
+    FlashOpt o;
+    o.coords = coords;
+    o.head_scale = slopes;
+    return flash_launch<false, false, false, false, true, true>("amds_attention_distbias", "attn_flash_kernel<distbias>", qkv, out, B, T, H, dtype, o, (hipStream_t)stream);
 }
 
 // forward that also stores L[b][h][q] = log2(sum_k exp2(s_qk * log2(e)/8)) for amds_attention_bwd

@@ -257,6 +257,112 @@ def golden_ticon() -> None:
     save("ticon.npz", **out)
 
 
+def golden_ticon_slide() -> None:
+    """TICON in SLIDE mode: the reference's own `EncoderDecoder` (classes executed as in `golden_ticon`) on whole slides -- all tiles of a slide as one
+    sequence with their coordinates, so that `Attention.forward`'s distance bias (ticon.py:201-212) and the q / k projections carry arithmetic.
+    Two models: (a) dim 192, 3 heads (head_dim 64, a non-power-of-two head count), depth 2; (b) dim 96, 6 heads (head_dim 16), depth 3 (the geometry
+    of ticon.npz).  Per model: B = 2 slides of 150 tiles on distinct cells of a 20 x 20 grid through both input projections; one un-batched slide of
+    70 tiles with non-integer coordinates (grid x 37.5); one tile alone at (0, 0).  Kept below the largest fixture of the repository: 2-d weights as
+    their bf16 bit patterns (`wb:` keys, exact: they were rounded to bf16), embeddings as fp16 (exact likewise), `out64` -- the float64 run -- with the
+    last 20 mantissa bits cleared (2^-33 relative), the fp32 run `out` as its distance in fp32 ulps from float32(out64) (`outulp`, exact); `wb:` and
+    `out64` arrays as byte planes (uint8 [itemsize, ...], little endian) in LZMA zips, which numpy.load reads like any .npz; one main file and
+    four parts (ticon_slide.npz, .out64.npz, .b.npz, .a0.npz, .a1.npz), each below 1 MiB.
+    tests/chains/ticon_slide.py (`load_fixture`) undoes all of it."""
+    import math
+    from collections.abc import Callable, Mapping
+    from functools import partial
+    from typing import Any
+
+    import torch.nn as nn
+
+    glb = {"nn": nn, "torch": torch, "math": math, "Tensor": torch.Tensor, "Float": sys.modules["jaxtyping"].Float, "Callable": Callable, "Mapping": Mapping,
+           "Any": Any, "partial": partial}
+    exec_defs(REF / "preprocessing" / "extractor" / "ticon.py",
+              {"LayerScale", "Mlp", "ProjectionMlp", "get_slopes", "scaled_dot_product_attention_custom", "Attention", "NaiveResidual", "EfficientResidual", "Block",
+               "Transformer", "EncoderDecoder", "_init_weights"}, glb)
+    out: dict = {}
+    for h in (3, 6, 24):
+        out[f"slopes_{h}"] = torch.Tensor(glb["get_slopes"](h)).numpy()
+    gen = torch.Generator().manual_seed(78)
+
+    def planes(a: np.ndarray) -> np.ndarray:
+        return np.ascontiguousarray(np.moveaxis(a.view(np.uint8).reshape(a.shape + (a.itemsize,)), -1, 0))
+
+    def grid_coords(n: int, scale: float) -> torch.Tensor:
+        cells = torch.randperm(400, generator=gen)[:n]
+        return torch.stack([cells // 20, cells % 20], dim=1).float() * scale
+
+    models = (("a", 192, 3, 2, (("hoptimus1", 128), ("conchv15", 80))), ("b", 96, 6, 3, (("conchv15", 48), ("hoptimus1", 128))))
+    for tag, dim, heads, depth, keys in models:
+        torch.manual_seed(79 + heads)
+        cfg = dict(transformers_kwargs={"embed_dim": dim, "drop_path_rate": 0.0, "block_kwargs": {"attn_kwargs": {"num_heads": heads}}},
+                   encoder_kwargs={"depth": depth}, decoder_kwargs={"depth": 1}, in_dims=[d for _, d in keys], tile_encoder_keys=[k for k, _ in keys],
+                   num_decoders=1, decoder_out_dims=[d for _, d in keys])
+        model = glb["EncoderDecoder"](**cfg).init_weights().eval()
+        with torch.no_grad():
+            for n, p in model.named_parameters():                   # as golden_ticon: every parameter matters, every weight is a bf16 number
+                if p.dim() == 1:
+                    p.add_(0.1 * torch.randn_like(p))
+                p.copy_(p.bfloat16().float())
+        out[f"{tag}_hparams"] = np.array([dim, heads, depth])
+        out[f"{tag}_keys"] = np.array([k for k, _ in keys])
+        cases = [(f"b2_{k}", k, d, 2, 150, 1.0) for k, d in keys] + [("n70", keys[0][0], keys[0][1], 0, 70, 37.5), ("n1", keys[0][0], keys[0][1], 0, 1, 0.0)]
+        for name, key, d_in, B, N, scale in cases:
+            nb = max(B, 1)
+            emb = torch.randn(nb, N, d_in, generator=gen).half()
+            coords = torch.stack([grid_coords(N, scale) for _ in range(nb)])
+            with torch.no_grad():
+                y = model(x=emb.float(), relative_coords=coords, tile_encoder_key=key)
+                y64 = model.double()(x=emb.double(), relative_coords=coords.double(), tile_encoder_key=key)
+                model.float()
+            y64 = (y64.numpy().view(np.int64) & ~np.int64((1 << 20) - 1)).view(np.float64)
+            order = lambda f: np.where(f.view(np.int32) >= 0, f.view(np.int32).astype(np.int64), -(f.view(np.int32).astype(np.int64) & 0x7FFFFFFF))  # noqa: E731
+            ulp = order(y.numpy()) - order(y64.astype(np.float32))          # monotonic in the value, so small where the two runs are close
+            assert np.abs(ulp).max() < 2 ** 31
+            sq = (lambda a: a[0]) if B == 0 else (lambda a: a)
+            c = f"{tag}_{name}"
+            out[f"{c}_key"] = np.array(key)
+            out[f"{c}_emb"], out[f"{c}_coords"] = sq(emb.numpy()), sq(coords.numpy())
+            out[f"{c}_out64"], out[f"{c}_outulp"] = planes(sq(y64)), sq(ulp.astype(np.int32))
+        for k, v in model.state_dict().items():
+            if ".decoder_" in k or "output_proj" in k or "mask_dict" in k:
+                continue
+            v = v.detach().cpu()
+            if v.dim() == 2:
+                assert torch.equal(v.bfloat16().float(), v)
+                out[f"{tag}_wb:{k}"] = planes(v.bfloat16().view(torch.int16).numpy().view(np.uint16))
+            else:
+                out[f"{tag}_w:{k}"] = v.numpy().copy()
+    # No file of the repository may exceed 1 MiB and the weights alone are 1.8 MB, so the fixture is a main file and four parts, all read as one:
+    # the cases in ticon_slide.npz, their float64 outputs in .out64, model b's weights in .b, model a's in .a0 (input projections, block 0) and .a1
+    import zipfile
+
+    def part(k: str) -> str:
+        if k.endswith("_out64"):
+            return ".out64"
+        if k.startswith("b_w"):
+            return ".b"
+        if k.startswith("a_w"):
+            return ".a1" if ("encoder.blocks.1." in k or "enc_norm" in k) else ".a0"
+        return ""
+
+    for old in OUT.glob("ticon_slide*.npz"):
+        old.unlink()
+    total = 0
+    for suffix in ("", ".out64", ".b", ".a0", ".a1"):
+        name = f"ticon_slide{suffix}.npz"
+        with zipfile.ZipFile(OUT / name, "w", compression=zipfile.ZIP_LZMA) as z:
+            for k, v in out.items():
+                if part(k) == suffix:
+                    with z.open(k + ".npy", "w") as f:
+                        np.lib.format.write_array(f, np.asanyarray(v), allow_pickle=False)
+        size = (OUT / name).stat().st_size
+        total += size
+        print(f"wrote {name}: {size/1024:.1f} KiB")
+        assert size <= 1 << 20, (name, size)
+    assert total <= max(f.stat().st_size for f in OUT.iterdir() if not f.name.startswith("ticon_slide")), total
+
+
 def golden_keep_head() -> None:
     """KEEP's image head: the reference's own `KEEPImageModel.encode_image` (keep.py:25-50) with the timm trunk replaced by the identity (timm is not
     in this image; the trunk is pinned elsewhere) -- pins visual_head + the L2 normalisation."""
@@ -1138,6 +1244,7 @@ def main() -> None:
     golden_eagle()
     golden_barspoon()
     golden_ticon()
+    golden_ticon_slide()
     golden_keep_head()
     golden_plip()
     golden_dinov2_hf()
