@@ -155,7 +155,11 @@ int amds_swin_mlp192(float* x, int M, const void* packed_w, const float* fc1_b, 
  * bit-identical results; 12 / 13 sum the bias first and 32 products per MFMA: they differ from the others in the last bits.
  * -2 = -1 plus: when M is not a multiple of 256 and dropping the last, partial row tile (<= 128 rows) saves a whole wave of workgroups on
  * kernel 12, those rows run through kernel 0 as a second launch (the MIL training step: M = bags x 1025).  Rows of that tile then differ
- * in the last bits from what kernel 12 would give, so paths that promise identical rows across batch compositions use -1. */
+ * in the last bits from what kernel 12 would give, so paths that promise identical rows across batch compositions use -1.
+ * 14 = kernel 12 with the one-phase form of its 16-bit-output epilogues (BIAS / BIAS_GELU / BIAS_RELU: the whole tile's values staged in LDS behind a
+ * workgroup barrier, then stored) instead of the streamed one (each wave drains its quadrant block row by block row, stores in flight under the
+ * value arithmetic): same bits as 12, kept for A/B.  AMDS_GEMM_EPI_STREAM=0 in the environment (read at every call, like AMDS_VIT_PLANES) turns
+ * kernels 12 / 13 back to the one-phase form wherever they run -- amds_gemm, amds_gemm_ex, amds_gemm_batched, amds_gemm_lnfold, the encoders. */
 int amds_gemm_ex(int cfg, const void* A, long lda, const void* W, long ldw, int M, int N, int K,
                  int dtype, int epi, void* out, long ldo, const float* bias, const float* scale,
                  const float* pos, int np, int T, int P, float acc_scale, void* stream);

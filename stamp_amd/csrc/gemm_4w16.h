@@ -45,7 +45,10 @@ __device__ __forceinline__ f32x4 agpr_read(const f32x4& a) {
 // loads and PRS 16-byte stores per lane against a scratch region (ep.pos), spread behind the MFMAs of the third unit, and the K loop waits for
 // its operands with a COUNTED vmcnt so that this traffic stays in flight -- i.e. an epilogue's worth of HBM traffic perfectly overlapped with
 // the matrix pipe, on top of the unchanged real epilogue.  T(probe) - T(id 12) = what overlapped epilogue bytes would still cost.
-template <typename T, int EPI, int P3 = 6, int P0 = 6, bool SPREAD = true, int PRL = 0, int PRS = 0, bool TN = false>
+// STREAM (16-bit-output epilogues only; kernel id 14 = id 12 with STREAM = false, AMDS_GEMM_EPI_STREAM=0 for ids 12 / 13): the epilogue is streamed
+// block row by block row through wave-private LDS slabs instead of staged as a whole tile behind a workgroup barrier (see the epilogue).
+// TN stays the LAST template argument: tools/check_tn_isa.py finds the token-major kernel by the end of its mangled name.
+template <typename T, int EPI, int P3 = 6, int P0 = 6, bool SPREAD = true, int PRL = 0, int PRS = 0, bool STREAM = false, bool TN = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 gemm_4w16_kernel(const T* __restrict__ A, long lda, const T* __restrict__ W, long ldw, int M, int N, int K,
                  EpiArgs ep, int tiles_m, int tiles_n) {
@@ -615,6 +618,82 @@ gemm_4w16_kernel(const T* __restrict__ A, long lda, const T* __restrict__ W, lon
             return;
         }
     }
+    if constexpr (F16OUT && STREAM) {
+        // Streamed 16-bit epilogue.  The one-phase form below runs the value math of the whole tile, one workgroup barrier, then all the stores:
+        // with one wave per SIMD nothing covers either phase.  Here every wave drains its own 128 x 128 quadrant in eight steps of one 16-row
+        // block row: 32 values per lane through the value transform (same operations in the same order: same bits), 8 ds_write_b64 into a
+        // wave-private slab of 16 rows x 256 B, 4 ds_read_b128 back (16 lanes = one row's 256 B), 4 buffer_store_dwordx4.  The read-back of
+        // step s is issued right behind its writes and consumed behind the value math of step s + 1, so the LDS round trip is covered and
+        // stores are in flight for the whole epilogue.  No workgroup barrier: a slab (two per wave, 32 KB of the idle stages) is touched by its
+        // wave only, and the LDS executes one wave's instructions in order.
+        // Slab image: the 16-byte chunk c of row r sits at chunk c ^ ((r >> 1) & 7), and the two 8-byte halves of a chunk are swapped in odd rows.
+        //   writes (ds_write_b64: groups of 16 contiguous lanes = rows 0..15 of one kb, banks of 128 B): 8 chunk positions x 2 halves = 16 slots;
+        //   reads  (ds_read_b128: groups of 16 lanes = 8 chunks each of rows r and r + 2, banks of 256 B): the chunk sets {0-3, 12-15} and {4-11}
+        //          of the two rows stay disjoint, their XOR terms differ in bit 0 only.  Conflict-free both ways.
+        // Rows past M lie beyond num_records of the output descriptor and their stores are dropped (all of the offset is in the VGPR).
+        EpiArgs epv = ep;                           // what the value transform still has to apply
+        if (bias_in_acc || lnf) epv.bias = nullptr;
+        EpiCols<FJ> cols;                           // [j]: columns n0 + wn*128 + 16 j + 4 kb
+        epi_cols_load<EPI>(epv, cols, [&](int j) { return n0 + wn * 128 + j * 16 + 4 * kb; });
+        const int rows_o = min(BM, M - m0);
+        const __amdgpu_buffer_rsrc_t rsrc_s = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<T*>(ep.out) + (long)m0 * ep.ldo + n0, 0,
+                                                                                (int)((((long)rows_o - 1) * ep.ldo + BN) * 2), 0x00020000);
+        char* slab = smem + wave * 8192;
+        const int wr_base = l15 * 256 + (((kb & 1) ^ (l15 & 1)) << 3);
+        const int wr_x = (kb >> 1) ^ ((l15 >> 1) & 7);
+        const int rd_base = kb * 512 + ((l15 ^ kb) << 4);             // read-back lane: chunk l15 of rows 2 kb + {0, 1, 8, 9}
+        const int ldo2 = (int)ep.ldo * 2;
+        const int st_base = (wm * 128 + 2 * kb) * ldo2 + (wn * 128 + l15 * 8) * 2;
+        auto run = [&](auto mode_c) {
+            constexpr int MODE = decltype(mode_c)::value;            // 0: the general transform, 1: FAST, 2: LayerNorm-folded consumer
+            u32x4 rd[4];
+#pragma unroll
+            for (int s = 0; s <= FI; ++s) {
+                if (s < FI) {
+                    char* wp = slab + (s & 1) * 4096 + wr_base;
+#pragma unroll
+                    for (int j = 0; j < FJ; j += 2) {
+                        f32x4 v0 = agpr_read(acc[s][j]), v1 = agpr_read(acc[s][j + 1]);
+                        if constexpr (MODE == 2) {
+                            if constexpr (LNC) {
+                                v0 = v0 * rs[s][0] + (cs[j] * rs[s][1] + cb[j]);
+                                v1 = v1 * rs[s][0] + (cs[j + 1] * rs[s][1] + cb[j + 1]);
+                                epi_value_pair<EPI, true, true>(epv, cb[j], cb[j], cb[j + 1], cb[j + 1], v0, v1);      // activation only
+                            }
+                        } else {
+                            epi_value_pair<EPI, MODE == 1, true>(epv, cols.bias[j], cols.scale[j], cols.bias[j + 1], cols.scale[j + 1], v0, v1);
+                        }
+                        const vec4 o0 = Act<T>::from_f32x4(v0), o1 = Act<T>::from_f32x4(v1);
+                        *reinterpret_cast<vec4*>(wp + (((2 * j) ^ wr_x) << 4)) = o0;
+                        *reinterpret_cast<vec4*>(wp + (((2 * j + 2) ^ wr_x) << 4)) = o1;
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                if (s > 0) {                        // block row s - 1, read back before this step's value math
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        const u32x4 v = (t & 1) ? u32x4{rd[t][2], rd[t][3], rd[t][0], rd[t][1]} : rd[t];      // odd row: halves stored swapped
+                        const int rowoff = ((s - 1) * 16 + (t & 1) + 8 * (t >> 1)) * ldo2;
+                        __builtin_amdgcn_raw_buffer_store_b128(v, rsrc_s, st_base + rowoff, 0, 0);
+                    }
+                }
+                if (s < FI) {
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // (no code: the lanes of a wave exchange data through the slab)
+                    __builtin_amdgcn_wave_barrier();
+                    const char* rp = slab + (s & 1) * 4096;
+#pragma unroll
+                    for (int t = 0; t < 4; ++t)
+                        rd[t] = *reinterpret_cast<const u32x4*>(rp + (rd_base ^ ((t >> 1) << 6)) + (t & 1) * 256 + (t >> 1) * 2048);
+                    __builtin_amdgcn_wave_barrier();
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        };
+        if (LNC && lnf) run(std::integral_constant<int, 2>{});
+        else if (bias_in_acc || (ep.bias == nullptr && ep.acc_scale == 1.0f)) run(std::integral_constant<int, 1>{});
+        else run(std::integral_constant<int, 0>{});
+        return;
+    }
     constexpr int NPASS = F16OUT ? 1 : 2;
     constexpr int JP = FJ / NPASS;                 // column blocks per pass
 #pragma unroll
@@ -716,14 +795,19 @@ gemm_4w16_kernel(const T* __restrict__ A, long lda, const T* __restrict__ W, lon
     }
 }
 
-template <typename T, int EPI, bool SPREAD = true, int P3 = 6, int P0 = 6, int PRL = 0, int PRS = 0, bool TN = false>
+template <typename T, int EPI, bool SPREAD = true, int P3 = 6, int P0 = 6, int PRL = 0, int PRS = 0, bool STREAM = false, bool TN = false>
 static int launch_gemm_4w16(const void* A, long lda, const void* W, long ldw, int M, int N, int K, const EpiArgs& ep,
                             hipStream_t st) {
     if constexpr (!epi_is_staged<EPI>() && EPI != AMDS_EPI_SWIGLU) {
         return launch_gemm_4w64<T, EPI>(A, lda, W, ldw, M, N, K, ep, st);
     } else {
         constexpr int LDS = 2 * (256 + 256) * 128;
-        constexpr auto kern = gemm_4w16_kernel<T, EPI, P3, P0, SPREAD, PRL, PRS, TN>;
+        // (only the 16-bit-output epilogues have a streamed form: every other epilogue has one instantiation)
+        constexpr bool STR = STREAM && (EPI == AMDS_EPI_BIAS || EPI == AMDS_EPI_BIAS_GELU || EPI == AMDS_EPI_BIAS_RELU);
+        if constexpr (STR) {                // the streamed epilogue addresses a tile's 256 output rows with 32-bit byte offsets; the one-phase form has no such limit
+            if (ep.ldo * 512 >= (1L << 31)) return launch_gemm_4w16<T, EPI, SPREAD, P3, P0, PRL, PRS, false, TN>(A, lda, W, ldw, M, N, K, ep, st);
+        }
+        constexpr auto kern = gemm_4w16_kernel<T, EPI, P3, P0, SPREAD, PRL, PRS, STR, TN>;
         EpiArgs epp = ep;
         if constexpr (PRL + PRS > 0) {      // probe scratch: one region per workgroup, never read by anything real
             static char* scratch = nullptr;

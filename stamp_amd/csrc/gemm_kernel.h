@@ -20,6 +20,7 @@
 //     range of tiles, walked in groups of GROUP_M row-tiles x all column-tiles so that the ~64
 //     co-resident tiles of an XCD share A and W panels through its L2.
 #pragma once
+#include <stdlib.h>
 #include <type_traits>
 #include "launch.h"
 
@@ -414,15 +415,23 @@ static int launch_gemm_8p64(const void* A, long lda, const void* W, long ldw, in
 template <typename T, int EPI>
 static int launch_gemm_4w64(const void* A, long lda, const void* W, long ldw, int M, int N, int K, const EpiArgs& ep,
                             hipStream_t st);   // gemm_4w64.h
-template <typename T, int EPI, bool SPREAD, int P3, int P0, int PRL, int PRS, bool TN>
+template <typename T, int EPI, bool SPREAD, int P3, int P0, int PRL, int PRS, bool STREAM, bool TN>
 static int launch_gemm_4w16(const void* A, long lda, const void* W, long ldw, int M, int N, int K, const EpiArgs& ep,
                             hipStream_t st);   // gemm_4w16.h
+
+// AMDS_GEMM_EPI_STREAM=0: the one-phase 16-bit epilogue of gemm_4w16.h instead of the streamed one (A/B; read at every call)
+static inline bool gemm_epi_stream() {
+    const char* e = getenv("AMDS_GEMM_EPI_STREAM");
+    return !(e && *e && atoi(e) == 0);
+}
 
 // kernel ids (amds_gemm_ex): 0 = 128x128 tile, one barrier per K step (small problems, any N % 128 == 0)
 //   1 = 128x96 tile, four waves stacked along M (N % 96 == 0: the Swin widths 96/192/288/576 that 128 does not divide)
 //  12 = 256x256x64 four waves, 128x128 wave tiles on v_mfma 16x16x32, AGPR accumulators (gemm_4w16.h): PRODUCTION for every
 //       epilogue but PATCH whenever N % 256 == 0 and the grid fills the chip; 13 = the same kernel with tile kt+2 requested
 //       from mid-tile kt on (two barriers per K tile, gemm_4w16.h SCHED 2; A/B)
+//       14 = id 12 with the one-phase 16-bit epilogue (the whole tile staged behind a workgroup barrier, then stored) that ids 12 / 13 had before
+//       theirs was streamed; AMDS_GEMM_EPI_STREAM=0, read at every call, turns 12 / 13 back to it as well (A/B)
 //   8 = 256x256x64 eight-wave staggered two-group pipeline (gemm_8p64.h): the PATCH epilogue, batched fallback
 //  10 = the four-wave structure on v_mfma 32x32x16 (gemm_4w64.h): the one A/B sibling kept
 // (the BK = 32 predecessors 3 / 7 and the ping-pong experiment 9 of round 1 were removed; their measurements stay in profiles/r01_*)
@@ -431,20 +440,27 @@ static int launch_gemm(int cfg, const void* A, long lda, const void* W, long ldw
                        const EpiArgs& ep, hipStream_t st) {
     if (cfg == 10 && N % 256 == 0 && ep.nbatch == 1) return launch_gemm_4w64<T, EPI>(A, lda, W, ldw, M, N, K, ep, st);
     if (cfg == 10) cfg = 8;
-    if (cfg == 12 && N % 256 == 0) return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 0, false>(A, lda, W, ldw, M, N, K, ep, st);
-    if (cfg == 13 && N % 256 == 0) return launch_gemm_4w16<T, EPI, true, -2, 0, 0, 0, false>(A, lda, W, ldw, M, N, K, ep, st);
+    if ((cfg == 12 || cfg == 13 || cfg == 14) && N % 256 == 0) {
+        const bool stream = cfg != 14 && gemm_epi_stream();
+        if (cfg == 13) {
+            if (stream) return launch_gemm_4w16<T, EPI, true, -2, 0, 0, 0, true, false>(A, lda, W, ldw, M, N, K, ep, st);
+            return launch_gemm_4w16<T, EPI, true, -2, 0, 0, 0, false, false>(A, lda, W, ldw, M, N, K, ep, st);
+        }
+        if (stream) return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 0, true, false>(A, lda, W, ldw, M, N, K, ep, st);
+        return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 0, false, false>(A, lda, W, ldw, M, N, K, ep, st);
+    }
 #ifdef AMDS_GEMM_PROBE      // overlap probe of round 4 (gemm_4w16.h PRL / PRS; make PROBE=1): K-loop traffic of (0, 2) / (1, 1) / (4, 4) loads, stores per lane and K tile
     if constexpr (EPI == AMDS_EPI_BIAS || EPI == AMDS_EPI_BIAS_GELU || EPI == AMDS_EPI_RESIDUAL) {
-        if (cfg == 21 && N % 256 == 0) return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 2, false>(A, lda, W, ldw, M, N, K, ep, st);
-        if (cfg == 22 && N % 256 == 0) return launch_gemm_4w16<T, EPI, true, 6, 6, 1, 1, false>(A, lda, W, ldw, M, N, K, ep, st);
-        if (cfg == 23 && N % 256 == 0) return launch_gemm_4w16<T, EPI, true, 6, 6, 4, 4, false>(A, lda, W, ldw, M, N, K, ep, st);
+        if (cfg == 21 && N % 256 == 0) return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 2, false, false>(A, lda, W, ldw, M, N, K, ep, st);
+        if (cfg == 22 && N % 256 == 0) return launch_gemm_4w16<T, EPI, true, 6, 6, 1, 1, false, false>(A, lda, W, ldw, M, N, K, ep, st);
+        if (cfg == 23 && N % 256 == 0) return launch_gemm_4w16<T, EPI, true, 6, 6, 4, 4, false, false>(A, lda, W, ldw, M, N, K, ep, st);
     }
 #endif
     if constexpr (EPI == AMDS_EPI_BIAS_F32) {      // 15 = the token-major (TN) form of id 12: weight gradients straight from dY / X (gemm_4w16.h)
-        if (cfg == 15 && N % 256 == 0 && M % 256 == 0) return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 0, true>(A, lda, W, ldw, M, N, K, ep, st);
+        if (cfg == 15 && N % 256 == 0 && M % 256 == 0) return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 0, false, true>(A, lda, W, ldw, M, N, K, ep, st);
     }
     if (cfg == 15) { set_error("amds_gemm: kernel 15 (token-major operands) takes the BIAS_F32 epilogue and M, N multiples of 256"); return AMDS_ERR_INVALID; }
-    if (cfg == 12 || cfg == 13) cfg = 8;
+    if (cfg == 12 || cfg == 13 || cfg == 14) cfg = 8;
 
     if (cfg == 8 && N % 256 == 0) return launch_gemm_8p64<T, EPI>(A, lda, W, ldw, M, N, K, ep, st);
     if (cfg == 8) cfg = 0;

@@ -1,5 +1,6 @@
 """A/B of the production GEMM's LDS-DMA schedules (kernel ids 12 / 13) on the four ViT-L shapes at one 1020-tile chunk, sustained:
-every candidate is warmed for ~0.4 s, then 40 launches are timed between two events; two rounds.  python tools/gemm_sched_ab.py"""
+every candidate is warmed for ~0.4 s, then 40 launches are timed between two events; two rounds.  python tools/gemm_sched_ab.py
+[M [ids]], e.g. `262140 12,14` for the streamed against the one-phase 16-bit epilogue."""
 import sys
 from pathlib import Path
 
