@@ -1041,6 +1041,93 @@ int amds_barspoon_forward(const amds_barspoon_cfg* cfg_host, const amds_barspoon
 /* ws: contents on entry are ignored (the call initialises every byte it reads);
  *     nothing outside [ws, ws + amds_barspoon_workspace_bytes) is written. */
 
+/* ---- the TRAINING step of the barspoon head, forward and backward as one call each -----------------------------------------------------------------------
+ * Reference: the train-mode forward of barspoon.py:164-205 -- torch's pre-norm containers with their documented `norm_first=True` dropout sites live
+ * (dropout = 0.1: the reference passes none, barspoon.py:118-162) -- and loss.backward() through it (`LitMilClassificationMixin.step`, barspoon.py:263-321).
+ *   projector            x = relu(W f + b) + PE                                                    (no dropout)                  :171-186
+ *   encoder layer l      x += drop(SA(LN1(x)));  x += drop(W2 drop(relu(W1 LN2(x))))               (dropout on SA's probabilities)  :188
+ *   decoder layer l      t += drop(SA(LN1(t)));  t += drop(MHA(LN2(t), x_enc));  t += drop(W2 drop(relu(W1 LN3(t))))                :190-193
+ *   heads                one Linear per target                                                                                      :196-203
+ * cfg.dtype = AMDS_BF16 or AMDS_F16: the type of every 16-bit tensor of the tile side (operands, saved activations, 16-bit gradients); fp32 accumulation,
+ * residual stream and its gradient.  The class-token side is exact fp32 in both directions whatever amds_set_matmul_precision says.
+ * One rate p for every site; masks are counter-based functions of (seed, stream id, element), regenerated by the backward, never stored.  p = 0, seed = 0 is
+ * eval arithmetic with saved activations.  Stream ids and element indices (Ha = enc_heads rounded up to 4; Dp / FFp = dim / ff rounded up to 256;
+ * M = n_bags * n_tiles; M2 = n_bags * n_targets), each readable with amds_dropout_mask (flat) or amds_attention_dropout_mask_rows (attention):
+ *   encoder layer l, id 10 l + 1   SA probabilities         rows (b Ha + h) n_tiles + q, cols n_tiles       (= amds_attention_dropout_mask(B, Ha, n_tiles))
+ *                    id 10 l + 2   relu -> dropout          flat r FFp + c over [M][FFp]
+ *                    id 10 l + 3   feed-forward output      flat r Dp + c over [M][Dp]
+ *                    id 10 l + 4   SA output                flat r Dp + c over [M][Dp]
+ *   decoder layer l, id 5000 + 10 l + 1   SA probabilities  rows (b dec_heads + h) n_targets + i, cols n_targets
+ *                    id 5000 + 10 l + 2   SA output         flat r dim + c over [M2][dim]
+ *                    id 5000 + 10 l + 3   MHA probabilities rows (b dec_heads + h) n_targets + j, cols n_tiles
+ *                    id 5000 + 10 l + 4   MHA output        flat r dim + c over [M2][dim]
+ *                    id 5000 + 10 l + 5   relu -> dropout   flat r ff + c over [M2][ff]
+ *                    id 5000 + 10 l + 6   feed-forward output  flat r dim + c over [M2][dim] */
+typedef struct {
+    float p;            /* every dropout site (torch's default 0.1 for both containers) */
+    uint64_t seed;
+} amds_barspoon_dropout;
+/* The deploy weights plus what the backward's input-gradient GEMMs read: enc_layers_host[l].{in,out,fc1,fc2}_wt (amds_mil_vit_layer's training fields) must be
+ * set, and ca_kv_wt_host[l] = decoder layer l's ca_kv_w transposed and padded, 16-bit [Dp][KVp], KVp = 2 Db rounded up to 256 (columns >= 2 Db zero). */
+typedef struct {
+    amds_barspoon_weights w;
+    const void* const* ca_kv_wt_host;                   /* HOST array of cfg.dec_layers device pointers */
+} amds_barspoon_train_weights;
+/* fp32 gradient buffers.  Encoder layers and the projector in the padded layout of their weights; decoder layers in the reference's shapes, except
+ * ca_kv_w [KVp][Dp] / ca_kv_b [KVp] (rows >= 2 Db receive zeros). */
+typedef struct {
+    float* ln1_w; float* ln1_b;
+    float* sa_in_w; float* sa_in_b;
+    float* sa_out_w; float* sa_out_b;
+    float* ln2_w; float* ln2_b;
+    float* ca_q_w; float* ca_q_b;
+    float* ca_kv_w; float* ca_kv_b;
+    float* ca_out_w; float* ca_out_b;
+    float* ln3_w; float* ln3_b;
+    float* fc1_w; float* fc1_b;
+    float* fc2_w; float* fc2_b;
+} amds_barspoon_dec_layer_grads;
+typedef struct {
+    float* proj_w; float* proj_b;                                   /* [Dp][Fp], [Dp] */
+    const amds_mil_vit_layer_grads* enc_layers_host;                /* HOST array of cfg.enc_layers entries (bias_scale unused) */
+    float* class_tokens;                                            /* [n_targets][dim] */
+    const amds_barspoon_dec_layer_grads* dec_layers_host;           /* HOST array of cfg.dec_layers entries */
+    float* const* head_w_host; float* const* head_b_host;           /* HOST arrays of n_targets device pointers: [n_out_t][dim], [n_out_t] */
+} amds_barspoon_grads;
+/* `saved`: the activations the backward reads (written by the forward, read-only afterwards: several backwards may follow one forward); `ws`: scratch of the
+ * backward.  Both 256-byte aligned; 0 bytes on a bad configuration (amds_last_error). */
+size_t amds_barspoon_train_saved_bytes(const amds_barspoon_cfg* cfg_host, int n_bags, int n_tiles);
+size_t amds_barspoon_train_workspace_bytes(const amds_barspoon_cfg* cfg_host, int n_bags, int n_tiles, int split_k);
+/* bags / positions / logits as amds_barspoon_forward.  Launches only, on `stream`. */
+int amds_barspoon_train_forward(const amds_barspoon_cfg* cfg_host, const amds_barspoon_train_weights* w_host, const void* bags, int bags_dtype,
+                                const float* positions, const amds_barspoon_dropout* drop_host, float* logits, int n_bags, int n_tiles, void* saved,
+                                size_t saved_bytes, void* stream);
+/* dlogits: fp32 [n_bags][sum_t n_out_t].  Every parameter gradient (no gradient w.r.t. bags or positions).  The gradient of the encoder's output is the sum over
+ * the decoder layers of the gradient through that layer's K | V projection, accumulated in fp32 before the encoder's backward starts.  Reductions over tiles
+ * (weight gradients in `split_k` partials, column sums, dq of the cross-attention) are summed in a fixed order: deterministic, no float atomics.
+ * dec_layers = 0: the encoder's and the projector's gradients are exact zeros. */
+int amds_barspoon_train_backward(const amds_barspoon_cfg* cfg_host, const amds_barspoon_train_weights* w_host, const float* dlogits,
+                                 const amds_barspoon_dropout* drop_host, int n_bags, int n_tiles, const void* saved, size_t saved_bytes,
+                                 const amds_barspoon_grads* grads_host, int split_k, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_barspoon_train_workspace_bytes) is written. */
+
+/* The cross-attention of that step on its own (nn.MultiheadAttention of the decoder layers with the tile tokens as memory, barspoon.py:190-193):
+ * a few fp32 queries against T 16-bit keys / values.  q, out, dout, dq: fp32 [B][nt][H hd]; kv: 16-bit [B*T][2 Db], Db = 64 H, K of head h at columns
+ * 64 h.., V at Db + 64 h.. (channels >= hd zero); lse fp32 [B][H][nt], log2 domain, of the undropped softmax; hd <= 64.
+ *   fwd: out = drop(softmax(q k^T / sqrt(hd))) v; mask = amds_attention_dropout_mask_rows(rows = B H nt, cols = T).  One wave per (bag, target, head).
+ *   bwd: dq and dkv [B*T][ld_dkv] in `dtype` (ld_dkv >= 2 Db; columns >= 2 Db are not written).  One workgroup per (bag, head, 256-key chunk) handles ALL nt
+ *        queries: each key / value row is read once (16-byte loads), each dkv row written once, no per-key cross-lane reduction; dq is summed from the
+ *        per-chunk partials in chunk order. */
+int amds_cross_attention_fwd_train(const float* q, const void* kv, float* out, float* lse, int B, int T, int nt, int H, int hd, int dtype, float p,
+                                   uint64_t seed, uint32_t stream_id, void* stream);
+size_t amds_cross_attention_bwd_workspace_bytes(int B, int T, int nt, int H);
+int amds_cross_attention_bwd_train(const float* q, const void* kv, const float* out, const float* dout, const float* lse, float* dq, void* dkv, long ld_dkv,
+                                   int B, int T, int nt, int H, int hd, int dtype, float p, uint64_t seed, uint32_t stream_id, void* ws, size_t ws_bytes,
+                                   void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_cross_attention_bwd_workspace_bytes) is written. */
+
 /* ------------------------------------------------------------------------------------------------
  * TransMIL building blocks (reference src/stamp/modeling/models/trans_mil.py), fp32 throughout
  * ---------------------------------------------------------------------------------------------- */
@@ -1370,6 +1457,20 @@ int amds_dropout_add_rows(const float* y, long ldy, const float* x_in, long ldx,
 int amds_dropout_cast_bwd_rows(const float* dx, long ldx, void* dy, long ldy, long rows, int cols, long row_mul, float p, uint64_t seed, uint32_t stream_id, void* stream);
 int amds_dropout_mask(uint8_t* mask, long n, float p, uint64_t seed, uint32_t stream_id, void* stream);
 int amds_attention_dropout_mask(uint8_t* mask, int B, int H, int T, float p, uint64_t seed, uint32_t stream_id, void* stream);
+/* `Linear -> ReLU -> Dropout` on a stored pre-activation, the pair the barspoon head's feed-forward blocks need (torch's
+ * nn.TransformerEncoderLayer / nn.TransformerDecoderLayer with activation=relu, instantiated by reference src/stamp/modeling/models/barspoon.py:118-162):
+ *   amds_relu_dropout_fwd   u = drop(max(z, 0))           amds_relu_dropout_bwd   dz = z > 0 ? drop'(du) : 0
+ * Same masks, element index and dtype rules as the GELU pair (u in z's type or fp32; dz in z's type, du in that type or fp32); p = 0: plain ReLU. */
+int amds_relu_dropout_fwd(const void* z, void* u, long n, int in_dtype, int out_dtype, float p, uint64_t seed, uint32_t stream_id, void* stream);
+int amds_relu_dropout_bwd(const void* z, const void* du, void* dz, long n, int z_dtype, int du_dtype, int dz_dtype, float p, uint64_t seed,
+                          uint32_t stream_id, void* stream);
+/* Dropout on fp32 attention probabilities that are held as a matrix, [rows][cols] contiguous (the decoder self-attention among barspoon's class tokens,
+ * barspoon.py:190-193): y[r][k] = keep(r, k) ? x[r][k] * keep_scale : 0, y may be x; applied to a gradient with the same arguments it is its own backward.
+ * The keep bit of (r, k) is the attention kernels': row key of row r, element pair k >> 1 (amds_attention_dropout_mask is the case rows = B H T, cols = T).
+ * amds_attention_dropout_mask_rows writes those bits (u8 0/1, [rows][cols]) for tests -- also the mask of amds_cross_attention_fwd_train
+ * (rows = B H n_targets in (b, h, target) order, cols = n_tiles). */
+int amds_attention_dropout_rows(const float* x, float* y, long rows, int cols, float p, uint64_t seed, uint32_t stream_id, void* stream);
+int amds_attention_dropout_mask_rows(uint8_t* mask, long rows, int cols, float p, uint64_t seed, uint32_t stream_id, void* stream);
 /* rowsum[b*T + q] = sum_k |coords[b,q] - coords[b,k]|: the batch statistic `_RunningMeanScaler` needs (mean of torch.cdist). */
 int amds_cdist_rowsum(const float* coords, float* rowsum, int B, int T, void* stream);
 /* fp16 -> bf16 (features are fp16 on disk; the training path feeds bf16 MFMA operands). */

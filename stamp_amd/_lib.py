@@ -146,6 +146,23 @@ class BarspoonWeights(C.Structure):
                 ("n_out_host", C.POINTER(C.c_int)), ("pe_div", C.c_void_p)]
 
 
+class BarspoonDropout(C.Structure):
+    _fields_ = [("p", C.c_float), ("seed", C.c_uint64)]
+
+
+class BarspoonTrainWeights(C.Structure):
+    _fields_ = [("w", BarspoonWeights), ("ca_kv_wt_host", C.POINTER(C.c_void_p))]
+
+
+class BarspoonDecLayerGrads(C.Structure):
+    _fields_ = BarspoonDecLayer._fields_
+
+
+class BarspoonGrads(C.Structure):
+    _fields_ = [("proj_w", C.c_void_p), ("proj_b", C.c_void_p), ("enc_layers_host", C.POINTER(MilVitLayerGrads)), ("class_tokens", C.c_void_p),
+                ("dec_layers_host", C.POINTER(BarspoonDecLayerGrads)), ("head_w_host", C.POINTER(C.c_void_p)), ("head_b_host", C.POINTER(C.c_void_p))]
+
+
 class TiconBlock(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("ln1_w", "ln1_b", "v_w", "v_b", "proj_w", "proj_b", "ln2_w", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")]
 
@@ -282,6 +299,13 @@ PROTOTYPES = {
     "amds_attention_row_varlen": (_i, [_vp, _l, _vp, _vp, _vp, _l, _i, _l, _i, _i, _i, _vp, _sz, _vp]),
     "amds_barspoon_workspace_bytes": (_sz, [_vp, _i, _i]),
     "amds_barspoon_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "amds_barspoon_train_saved_bytes": (_sz, [_vp, _i, _i]),
+    "amds_barspoon_train_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "amds_barspoon_train_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "amds_barspoon_train_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _i, _vp, _sz, _vp]),
+    "amds_cross_attention_fwd_train": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _u64, _u32, _vp]),
+    "amds_cross_attention_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "amds_cross_attention_bwd_train": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _f, _u64, _u32, _vp, _sz, _vp]),
     "amds_ticon_tile_workspace_bytes": (_sz, [_vp, _i]),
     "amds_ticon_tile_forward": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _sz, _vp]),
     "amds_attention_distbias": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -374,6 +398,10 @@ PROTOTYPES = {
     "amds_dropout_cast_bwd": (_i, [_vp, _l, _vp, _l, _l, _i, _i, _f, _u64, _u32, _vp]),
     "amds_dropout_mask": (_i, [_vp, _l, _f, _u64, _u32, _vp]),
     "amds_attention_dropout_mask": (_i, [_vp, _i, _i, _i, _f, _u64, _u32, _vp]),
+    "amds_relu_dropout_fwd": (_i, [_vp, _vp, _l, _i, _i, _f, _u64, _u32, _vp]),
+    "amds_relu_dropout_bwd": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _f, _u64, _u32, _vp]),
+    "amds_attention_dropout_rows": (_i, [_vp, _vp, _l, _i, _f, _u64, _u32, _vp]),
+    "amds_attention_dropout_mask_rows": (_i, [_vp, _l, _i, _f, _u64, _u32, _vp]),
     "amds_convert_f16_bf16": (_i, [_vp, _vp, _l, _vp]),
     "amds_adamw": (_i, [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _vp]),
     "amds_loss_scale_init": (_i, [_vp, _f, _i, _f, _f, _f, _f, _vp]),

@@ -87,6 +87,81 @@ __global__ void __launch_bounds__(256) gelu_dropout_bwd8_kernel(const TZ* __rest
         reinterpret_cast<vo*>(dz)[v] = o;
     }
 }
+// ---- ReLU + Dropout (the barspoon head's `Linear -> ReLU -> Dropout` sites; same masks, same index rule as the GELU pair above) ----
+template <typename TI, typename TO>
+__global__ void relu_dropout_fwd_kernel(const TI* __restrict__ z, TO* __restrict__ u, long n, uint64_t seed, uint32_t stream, uint32_t thr, float scale) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) {
+        const float x = (float)z[i];
+        u[i] = (TO)((x > 0.f && drop_keep_flat(seed, stream, i, thr)) ? x * scale : 0.f);
+    }
+}
+template <typename TZ, typename TG, typename TO>
+__global__ void relu_dropout_bwd_kernel(const TZ* __restrict__ z, const TG* __restrict__ du, TO* __restrict__ dz, long n, uint64_t seed,
+                                        uint32_t stream, uint32_t thr, float scale) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) dz[i] = (TO)(((float)z[i] > 0.f && drop_keep_flat(seed, stream, i, thr)) ? (float)du[i] * scale : 0.f);
+}
+template <typename TI, typename TO>
+__global__ void __launch_bounds__(256) relu_dropout_fwd8_kernel(const TI* __restrict__ z, TO* __restrict__ u, long n8, uint64_t seed, uint32_t stream, uint32_t thr, float scale) {
+    typedef typename Vec8<TI>::type vi;
+    typedef typename Vec8<TO>::type vo;
+    long v = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (; v < n8; v += stride) {
+        const vi a = reinterpret_cast<const vi*>(z)[v];
+        bool keep[8];
+        drop_keep8(seed, stream, v * 8, thr, keep);
+        vo o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float x = (float)a[e];
+            o[e] = (TO)((x > 0.f && keep[e]) ? x * scale : 0.f);
+        }
+        reinterpret_cast<vo*>(u)[v] = o;
+    }
+}
+template <typename TZ, typename TG, typename TO>
+__global__ void __launch_bounds__(256) relu_dropout_bwd8_kernel(const TZ* __restrict__ z, const TG* __restrict__ du, TO* __restrict__ dz, long n8, uint64_t seed,
+                                                                uint32_t stream, uint32_t thr, float scale) {
+    typedef typename Vec8<TZ>::type vz;
+    typedef typename Vec8<TG>::type vg;
+    typedef typename Vec8<TO>::type vo;
+    long v = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (; v < n8; v += stride) {
+        const vz a = reinterpret_cast<const vz*>(z)[v];
+        const vg g = reinterpret_cast<const vg*>(du)[v];
+        bool keep[8];
+        drop_keep8(seed, stream, v * 8, thr, keep);
+        vo o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (TO)(((float)a[e] > 0.f && keep[e]) ? (float)g[e] * scale : 0.f);
+        reinterpret_cast<vo*>(dz)[v] = o;
+    }
+}
+// fp32 attention probabilities [rows][cols] times their keep mask and scale (row key = row, pair = k >> 1: the rule of attn_dropout_mask_kernel)
+__global__ void __launch_bounds__(256) attn_dropout_rows_kernel(const float* __restrict__ x, float* __restrict__ y, long rows, int cols, uint64_t seed, uint32_t stream,
+                                                                uint32_t thr, float scale) {
+    const long n = rows * cols;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / cols;
+        const int k = (int)(i - r * cols);
+        const uint32_t key = drop_rowkey(seed, stream, (uint64_t)r);
+        y[i] = drop_keep(drop_pair_bits(key, (uint32_t)k >> 1), k & 1, thr) ? x[i] * scale : 0.f;
+    }
+}
+__global__ void __launch_bounds__(256) attn_dropout_mask_rows_kernel(uint8_t* __restrict__ m, long rows, int cols, uint64_t seed, uint32_t stream, uint32_t thr) {
+    const long n = rows * cols;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / cols;
+        const int k = (int)(i - r * cols);
+        const uint32_t key = drop_rowkey(seed, stream, (uint64_t)r);
+        m[i] = drop_keep(drop_pair_bits(key, (uint32_t)k >> 1), k & 1, thr) ? 1 : 0;
+    }
+}
 template <typename TO>
 __global__ void __launch_bounds__(256) dropout_cast_bwd8_kernel(const float* __restrict__ dx, long ldx, TO* __restrict__ dy, long ldy, long rows, int cols, uint64_t seed,
                                                                 uint32_t stream, uint32_t thr, float scale) {
@@ -344,6 +419,77 @@ extern "C" int amds_gelu_dropout_bwd(const void* z, const void* du, void* dz, lo
     }); });
     if (!ok) { set_error("amds_gelu_dropout_bwd: unsupported dtype combination"); return AMDS_ERR_INVALID; }
     AMDS_LAUNCH_CHECK("gelu_dropout_bwd_kernel");
+    return AMDS_OK;
+}
+
+// ReLU + Dropout on a stored pre-activation: the dtype rules of the GELU pair (u in z's type or fp32; dz in z's type, du in that type or fp32)
+extern "C" int amds_relu_dropout_fwd(const void* z, void* u, long n, int in_dtype, int out_dtype, float p, uint64_t seed, uint32_t stream_id, void* stream) {
+    AMDS_REQUIRE(z && u && n >= 0 && DROP_ARGS_OK(p), "amds_relu_dropout_fwd: bad arguments");
+    if (n == 0) return AMDS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const DropParams d(p);
+    const bool v8 = n % 8 == 0 && al16(z) && al16(u);
+    bool ok = false;
+    dispatch_16_32(in_dtype, [&](auto tz) { dispatch_16_32(out_dtype, [&](auto to) {
+        typedef AMDS_TAG_T(tz) TZ;
+        typedef AMDS_TAG_T(to) TO;
+        if constexpr (std::is_same_v<TO, TZ> || std::is_same_v<TO, float>) {
+            ok = true;
+            if constexpr (!std::is_same_v<TZ, float>)
+                if (v8) {
+                    hipLaunchKernelGGL((relu_dropout_fwd8_kernel<TZ, TO>), dim3(grid1d_(n / 8)), dim3(256), 0, st, (const TZ*)z, (TO*)u, n / 8, seed, stream_id, d.thr, d.scale);
+                    return;
+                }
+            hipLaunchKernelGGL((relu_dropout_fwd_kernel<TZ, TO>), dim3(grid1d_(n)), dim3(256), 0, st, (const TZ*)z, (TO*)u, n, seed, stream_id, d.thr, d.scale);
+        }
+    }); });
+    if (!ok) { set_error("amds_relu_dropout_fwd: unsupported dtype pair"); return AMDS_ERR_INVALID; }
+    AMDS_LAUNCH_CHECK("relu_dropout_fwd_kernel");
+    return AMDS_OK;
+}
+
+extern "C" int amds_relu_dropout_bwd(const void* z, const void* du, void* dz, long n, int z_dtype, int du_dtype, int dz_dtype, float p, uint64_t seed,
+                                     uint32_t stream_id, void* stream) {
+    AMDS_REQUIRE(z && du && dz && n >= 0 && DROP_ARGS_OK(p), "amds_relu_dropout_bwd: bad arguments");
+    if (n == 0) return AMDS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const DropParams d(p);
+    const bool v8 = n % 8 == 0 && al16(z) && al16(du) && al16(dz);
+    bool ok = false;
+    if (dz_dtype == z_dtype) dispatch_16_32(z_dtype, [&](auto tz) { dispatch_16_32(du_dtype, [&](auto tg) {
+        typedef AMDS_TAG_T(tz) TZ;
+        typedef AMDS_TAG_T(tg) TG;
+        if constexpr (std::is_same_v<TG, TZ> || std::is_same_v<TG, float>) {
+            ok = true;
+            if constexpr (!std::is_same_v<TZ, float>)
+                if (v8) {
+                    hipLaunchKernelGGL((relu_dropout_bwd8_kernel<TZ, TG, TZ>), dim3(grid1d_(n / 8)), dim3(256), 0, st, (const TZ*)z, (const TG*)du, (TZ*)dz, n / 8, seed, stream_id,
+                                       d.thr, d.scale);
+                    return;
+                }
+            hipLaunchKernelGGL((relu_dropout_bwd_kernel<TZ, TG, TZ>), dim3(grid1d_(n)), dim3(256), 0, st, (const TZ*)z, (const TG*)du, (TZ*)dz, n, seed, stream_id, d.thr, d.scale);
+        }
+    }); });
+    if (!ok) { set_error("amds_relu_dropout_bwd: unsupported dtype combination"); return AMDS_ERR_INVALID; }
+    AMDS_LAUNCH_CHECK("relu_dropout_bwd_kernel");
+    return AMDS_OK;
+}
+
+// y = drop(x) on fp32 attention probabilities [rows][cols] (y may be x); the same call with the same arguments on a gradient is the backward
+extern "C" int amds_attention_dropout_rows(const float* x, float* y, long rows, int cols, float p, uint64_t seed, uint32_t stream_id, void* stream) {
+    AMDS_REQUIRE(x && y && rows >= 0 && cols > 0 && DROP_ARGS_OK(p), "amds_attention_dropout_rows: bad arguments");
+    if (rows == 0) return AMDS_OK;
+    const DropParams d(p);
+    hipLaunchKernelGGL(attn_dropout_rows_kernel, dim3(grid1d_(rows * cols)), dim3(256), 0, (hipStream_t)stream, x, y, rows, cols, seed, stream_id, d.thr, d.scale);
+    AMDS_LAUNCH_CHECK("attn_dropout_rows_kernel");
+    return AMDS_OK;
+}
+
+extern "C" int amds_attention_dropout_mask_rows(uint8_t* mask, long rows, int cols, float p, uint64_t seed, uint32_t stream_id, void* stream) {
+    AMDS_REQUIRE(mask && rows >= 0 && cols > 0 && DROP_ARGS_OK(p), "amds_attention_dropout_mask_rows: bad arguments");
+    if (rows == 0) return AMDS_OK;
+    hipLaunchKernelGGL(attn_dropout_mask_rows_kernel, dim3(grid1d_(rows * cols)), dim3(256), 0, (hipStream_t)stream, mask, rows, cols, seed, stream_id, drop_thr16(p));
+    AMDS_LAUNCH_CHECK("attn_dropout_mask_rows_kernel");
     return AMDS_OK;
 }
 

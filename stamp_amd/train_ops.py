@@ -276,3 +276,33 @@ def wgrad_tn(dy: torch.Tensor, x: torch.Tensor, split_k: int = 32) -> torch.Tens
     part = torch.empty(split_k, N, K, dtype=torch.float32, device=dy.device)
     _lib.check(_lib.lib().amds_wgrad_tn(_p(dy), dy.stride(0), _p(x), x.stride(0), tokens, N, K, split_k, act_code(dy.dtype), _p(part), _stream()), "wgrad_tn")
     return colsum(part.view(split_k, N * K)).view(N, K)
+
+
+def attention_dropout_mask_rows(rows: int, cols: int, p: float, seed: int, stream_id: int, device) -> torch.Tensor:
+    """The keep mask (u8 [rows, cols]) of attention probabilities held as a matrix, and of the training cross-attention (rows = B H n_targets) -- for tests."""
+    m = torch.empty(rows, cols, dtype=torch.uint8, device=device)
+    _lib.check(_lib.lib().amds_attention_dropout_mask_rows(_p(m), rows, cols, float(p), int(seed), int(stream_id), _stream()), "attention_dropout_mask_rows")
+    return m
+
+
+def cross_attention_fwd_train(q: torch.Tensor, kv: torch.Tensor, B: int, T: int, nt: int, H: int, hd: int, p: float = 0.0, seed: int = 0, stream_id: int = 0):
+    """q fp32 [B, nt, H hd], kv 16-bit [B T, 128 H] -> (out fp32 [B, nt, H hd], lse fp32 [B, H, nt], log2 domain)."""
+    _dev(q, kv)
+    out = torch.empty(B, nt, H * hd, dtype=torch.float32, device=q.device)
+    lse = torch.empty(B, H, nt, dtype=torch.float32, device=q.device)
+    _lib.check(_lib.lib().amds_cross_attention_fwd_train(_p(q), _p(kv), _p(out), _p(lse), B, T, nt, H, hd, act_code(kv.dtype), float(p), int(seed), int(stream_id),
+                                                         _stream()), "cross_attention_fwd_train")
+    return out, lse
+
+
+def cross_attention_bwd_train(q: torch.Tensor, kv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, B: int, T: int, nt: int, H: int, hd: int,
+                              p: float = 0.0, seed: int = 0, stream_id: int = 0):
+    """-> (dq fp32 [B, nt, H hd], dkv [B T, 128 H] in kv's type)."""
+    _dev(q, kv, out, dout, lse)
+    dq = torch.empty_like(q)
+    dkv = torch.empty_like(kv)
+    need = _lib.lib().amds_cross_attention_bwd_workspace_bytes(B, T, nt, H)
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
+    _lib.check(_lib.lib().amds_cross_attention_bwd_train(_p(q), _p(kv), _p(out), _p(dout), _p(lse), _p(dq), _p(dkv), kv.shape[1], B, T, nt, H, hd, act_code(kv.dtype),
+                                                         float(p), int(seed), int(stream_id), _p(ws), ws.numel(), _stream()), "cross_attention_bwd_train")
+    return dq, dkv
