@@ -127,43 +127,9 @@ class EncDecTransformer(nn.Module):
         key = (str(dev), tuple((t.data_ptr(), t._version) for t in tensors.values()))
         if self._pack_key == key:
             return self._packed
-        g = lambda n: tensors[n].detach().to(dev, torch.float32).contiguous()  # noqa: E731
-        D, Hd, FF = self.d_model, self.num_decoder_heads, self.dim_feedforward
-        dims = VitDims(F=self.d_features, D=D, H=self.num_encoder_heads, FF=FF, C=1, L=self.num_encoder_layers, alibi=False)
-        vit_get = self._enc_get(g, dev)
-
-        pk = PackedVit(dims, vit_get, torch.float16, train=False)
-        pk.c_structs()
-        enc_layers = pk._c[2]
-        keep = [pk]
-
-        def T(t):
-            keep.append(t)
-            return t.data_ptr()
-
-        Dp = dims.Dp
-        dec = (_lib.BarspoonDecLayer * max(self.num_decoder_layers, 1))()
-        for l in range(self.num_decoder_layers):
-            p = f"transformer_decoder.layers.{l}."
-            w, b = g(p + "multihead_attn.in_proj_weight"), g(p + "multihead_attn.in_proj_bias")
-            kvw, kvb = pad_kv_w(w[D:], Hd, D, Dp), pad_kv_b(b[D:], Hd, D)
-            dec[l] = _lib.BarspoonDecLayer(T(g(p + "norm1.weight")), T(g(p + "norm1.bias")), T(g(p + "self_attn.in_proj_weight")), T(g(p + "self_attn.in_proj_bias")),
-                                           T(g(p + "self_attn.out_proj.weight")), T(g(p + "self_attn.out_proj.bias")), T(g(p + "norm2.weight")), T(g(p + "norm2.bias")),
-                                           T(w[:D].contiguous()), T(b[:D].contiguous()), T(ops.cast_pad(kvw, Dp, torch.float16)), T(kvb),
-                                           T(g(p + "multihead_attn.out_proj.weight")), T(g(p + "multihead_attn.out_proj.bias")), T(g(p + "norm3.weight")),
-                                           T(g(p + "norm3.bias")), T(g(p + "linear1.weight")), T(g(p + "linear1.bias")), T(g(p + "linear2.weight")), T(g(p + "linear2.bias")))
-        labels = [sanitize(t) for t in self.target_labels]
-        nt = len(labels)
-        hw, hb, no = (C.c_void_p * nt)(), (C.c_void_p * nt)(), (C.c_int * nt)()
-        for j, t in enumerate(labels):
-            hw[j], hb[j], no[j] = T(g(f"heads.{t}.weight")), T(g(f"heads.{t}.bias")), self.heads[t].out_features
-        ct = torch.stack([g(f"class_tokens.{t}") for t in labels]).contiguous()
-        pe = (100_000 ** (torch.arange(D // 4, dtype=torch.float32) / D)).to(dev).contiguous()              # :176-178, in torch's own fp32 arithmetic
-        wc = _lib.BarspoonWeights(pk.w["proj_w"].data_ptr(), pk.m["proj_b"].data_ptr(), enc_layers, T(ct), dec, hw, hb, no, T(pe))
-        cfg = _lib.BarspoonCfg(self.d_features, D, self.num_encoder_heads, Hd, FF, self.num_encoder_layers, self.num_decoder_layers, nt,
-                               int(bool(self.positional_encoding)), _lib.F16)
-        self._packed, self._pack_key = (cfg, wc, keep, dec, hw, hb, no, sum(no)), key
-        return self._packed
+        pack = _Pack(self, lambda n: tensors[n].detach().to(dev, torch.float32), torch.float16, dev, train=False)
+        self._packed, self._pack_key = pack, key
+        return pack
 
     def forward(self, tile_tokens: torch.Tensor, tile_positions: torch.Tensor) -> dict[str, torch.Tensor]:
         if not tile_tokens.is_cuda:
@@ -180,7 +146,8 @@ class EncDecTransformer(nn.Module):
         x = tile_tokens if tile_tokens.dtype in ops._DT else tile_tokens.float()
         x = x.contiguous()
         pos = tile_positions.to(dev, torch.float32).contiguous() if tile_positions is not None else None
-        cfg, wc, _keep, _dec, _hw, _hb, no, total = self._pack(dev)
+        pack = self._pack(dev)
+        cfg, wc, no, total = pack.cfg, pack.wc, pack.no, pack.total_out
         lib = _lib.lib()
         need = lib.amds_barspoon_workspace_bytes(C.byref(cfg), Bb, T)
         if need == 0:
@@ -236,16 +203,18 @@ class EncDecTransformer(nn.Module):
 
 
 # ---- the training step's functional core: pack, forward, backward (each ONE library call) -----------------------------------------------------
-class TrainPack:
-    """Device operands of one training step: the encoder in the MIL `vit` head's padded training pack (16-bit W and W^T), the decoder's fp32 tensors, each
-    decoder layer's K | V projection padded, cast and transposed, and the C structs over them.  `get(name)` -> fp32 device tensor of a parameter."""
+class _Pack:
+    """Device operands of one packing and the C structs over them (amds_barspoon_cfg, amds_barspoon_weights and what they point to): the encoder in the MIL
+    `vit` head's padded pack, the decoder's fp32 tensors, each decoder layer's K | V projection padded and cast.  `train` (a training step): the encoder's
+    pack carries W^T too, the K | V rows are padded to KVp and their transposed copies go into amds_barspoon_train_weights; without it (the deploy forward,
+    `EncDecTransformer._pack`) `wc` is the plain amds_barspoon_weights.  `get(name)` -> fp32 device tensor of a parameter."""
 
-    def __init__(self, model: EncDecTransformer, get, act: torch.dtype, dev) -> None:
-        self.model, self.act, self.dev = model, act, dev
+    def __init__(self, model: EncDecTransformer, get, act: torch.dtype, dev, *, train: bool) -> None:
+        self.act, self.dev = act, dev
         D, Hd, FF = model.d_model, model.num_decoder_heads, model.dim_feedforward
         self.dims = VitDims(F=model.d_features, D=D, H=model.num_encoder_heads, FF=FF, C=1, L=model.num_encoder_layers, alibi=False)
         g = lambda n: get(n).contiguous()  # noqa: E731
-        self.pk = PackedVit(self.dims, model._enc_get(g, dev), act, train=True)
+        self.pk = PackedVit(self.dims, model._enc_get(g, dev), act, train=train)
         self.pk.c_structs()
         enc_layers = self.pk._c[2]
         self.keep: list = []
@@ -255,19 +224,23 @@ class TrainPack:
             return t.data_ptr()
 
         Dp = self.dims.Dp
-        self.KVp = _up(2 * 64 * Hd, 256)
         Ld = model.num_decoder_layers
         self.dec = (_lib.BarspoonDecLayer * max(Ld, 1))()
-        self.kvt = (C.c_void_p * max(Ld, 1))()
+        if train:
+            self.KVp = _up(2 * 64 * Hd, 256)
+            self.kvt = (C.c_void_p * max(Ld, 1))()
         for l in range(Ld):
             p = f"transformer_decoder.layers.{l}."
             w, b = g(p + "multihead_attn.in_proj_weight"), g(p + "multihead_attn.in_proj_bias")
             kvw, kvb = pad_kv_w(w[D:], Hd, D, Dp), pad_kv_b(b[D:], Hd, D)
-            kv16 = ops.cast_pad(F.pad(kvw, (0, 0, 0, self.KVp - kvw.shape[0])).contiguous(), Dp, act)        # [KVp][Dp], rows >= 2 Db zero
+            if train:
+                kvw = F.pad(kvw, (0, 0, 0, self.KVp - kvw.shape[0])).contiguous()                            # [KVp][Dp], rows >= 2 Db zero
+            kv16 = ops.cast_pad(kvw, Dp, act)
             fields = {k: T(g(p + n)) for k, n in _DEC_FP32}
             fields.update(ca_q_w=T(w[:D].contiguous()), ca_q_b=T(b[:D].contiguous()), ca_kv_w=T(kv16), ca_kv_b=T(kvb))
             self.dec[l] = _lib.BarspoonDecLayer(**fields)
-            self.kvt[l] = T(kv16.t().contiguous())                                                           # [Dp][KVp]
+            if train:
+                self.kvt[l] = T(kv16.t().contiguous())                                                       # [Dp][KVp]
         labels = [sanitize(t) for t in model.target_labels]
         nt = len(labels)
         self.hw, self.hb, self.no = (C.c_void_p * nt)(), (C.c_void_p * nt)(), (C.c_int * nt)()
@@ -277,9 +250,17 @@ class TrainPack:
         ct = torch.stack([g(f"class_tokens.{t}") for t in labels]).contiguous()
         pe = (100_000 ** (torch.arange(D // 4, dtype=torch.float32) / D)).to(dev).contiguous()              # :176-178, in torch's own fp32 arithmetic
         base = _lib.BarspoonWeights(self.pk.w["proj_w"].data_ptr(), self.pk.m["proj_b"].data_ptr(), enc_layers, T(ct), self.dec, self.hw, self.hb, self.no, T(pe))
-        self.wc = _lib.BarspoonTrainWeights(base, self.kvt)
+        self.wc = _lib.BarspoonTrainWeights(base, self.kvt) if train else base
         self.cfg = _lib.BarspoonCfg(model.d_features, D, model.num_encoder_heads, Hd, FF, model.num_encoder_layers, Ld, nt, int(bool(model.positional_encoding)),
                                     ops.act_code(act))
+
+
+class TrainPack(_Pack):
+    """The pack of one training step (16-bit W and W^T of the encoder, K | V projections padded, cast and transposed)."""
+
+    def __init__(self, model: EncDecTransformer, get, act: torch.dtype, dev) -> None:
+        super().__init__(model, get, act, dev, train=True)
+        self.model = model
 
 
 def train_forward(pack: TrainPack, tile_tokens: torch.Tensor, tile_positions: torch.Tensor | None, *, p: float, seed: int):

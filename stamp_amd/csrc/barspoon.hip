@@ -11,16 +11,13 @@
 // 256, heads to 64 channels); the class-token side (n_targets rows per bag) runs in exact fp32 (amds_bgemm_f32).  The cross-attention is
 // its own kernel: one fp32 query row per (bag, target, head) streamed over the bag's 16-bit keys / values with an online softmax.
 #include <algorithm>
-#include "common.h"
+#include "barspoon_common.h"
 
 namespace amds {
 namespace {
 
-inline int up(int n, int m) { return (n + m - 1) / m * m; }
-inline size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
-
-struct BsPlan {
-    int Fp, Dp, FFp, Ha, Da, Hb, Db, hd_e, hd_d, nt, n_out_total;
+struct BsPlan : PadDims {
+    int Hb, Db, hd_e, hd_d, nt, n_out_total;
     size_t a, x, h, qkv, att, u, kv, tok, th, tqkv, tsc, to, tq, tu, total;
 };
 
@@ -34,41 +31,28 @@ int bs_plan(const amds_barspoon_cfg* c, int Bb, int T, BsPlan* p) {
     AMDS_REQUIRE(c->n_targets <= 1024, "amds_barspoon: %d targets", c->n_targets);
     AMDS_REQUIRE(c->dtype == AMDS_F16 || c->dtype == AMDS_BF16, "amds_barspoon: operand dtype must be f16 or bf16");
     AMDS_REQUIRE(Bb >= 0 && T > 0, "amds_barspoon: bad shape bags=%d tiles=%d", Bb, T);
-    p->Fp = up(c->n_feats, 256); p->Dp = up(c->dim, 256); p->FFp = up(c->ff, 256);
-    p->Ha = up(c->enc_heads, 4); p->Da = 64 * p->Ha;                 // encoder self-attention: padded heads (amds_attention wants H % 4 == 0)
+    static_cast<PadDims&>(*p) = pad_dims(c->n_feats, c->dim, c->ff, c->enc_heads);      // encoder self-attention: padded heads
     p->Hb = c->dec_heads; p->Db = 64 * p->Hb;                        // cross-attention K / V: decoder heads padded to 64 channels
     p->hd_e = c->dim / c->enc_heads; p->hd_d = c->dim / c->dec_heads;
     p->nt = c->n_targets;
     const size_t M = (size_t)Bb * T, M2 = (size_t)Bb * p->nt, D = c->dim;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-    p->a = take(M * p->Fp * 2);
-    p->x = take(M * p->Dp * 4);
-    p->h = take(M * p->Dp * 2);
-    p->qkv = take(M * 3 * p->Da * 2);
-    p->att = take(M * p->Da * 2);
-    p->u = take(M * p->FFp * 2);
-    p->kv = take(M * 2 * p->Db * 2);
-    p->tok = take(M2 * D * 4);
-    p->th = take(M2 * D * 4);
-    p->tqkv = take(M2 * 3 * D * 4);
-    p->tsc = take((size_t)Bb * p->Hb * p->nt * p->nt * 4);
-    p->to = take(M2 * D * 4);
-    p->tq = take(M2 * D * 4);
-    p->tu = take(M2 * (size_t)c->ff * 4);
-    p->total = off;
+    Arena ar;
+    p->a = ar.take(M * p->Fp * 2);
+    p->x = ar.take(M * p->Dp * 4);
+    p->h = ar.take(M * p->Dp * 2);
+    p->qkv = ar.take(M * 3 * p->Da * 2);
+    p->att = ar.take(M * p->Da * 2);
+    p->u = ar.take(M * p->FFp * 2);
+    p->kv = ar.take(M * 2 * p->Db * 2);
+    p->tok = ar.take(M2 * D * 4);
+    p->th = ar.take(M2 * D * 4);
+    p->tqkv = ar.take(M2 * 3 * D * 4);
+    p->tsc = ar.take((size_t)Bb * p->Hb * p->nt * p->nt * 4);
+    p->to = ar.take(M2 * D * 4);
+    p->tq = ar.take(M2 * D * 4);
+    p->tu = ar.take(M2 * (size_t)c->ff * 4);
+    p->total = ar.off;
     return AMDS_OK;
-}
-
-template <typename TI, typename TO>
-__global__ void __launch_bounds__(256) bs_stage_kernel(const TI* __restrict__ src, long ld_src, TO* __restrict__ dst, int Fp, long total, int F) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (; i < total; i += stride) {
-        const long r = i / Fp;
-        const int c = (int)(i - r * Fp);
-        dst[i] = c < F ? (TO)(float)src[r * ld_src + c] : (TO)0.f;
-    }
 }
 
 // x[r][c] += PE(pos[r])[c] for c < D:  [ sin(px / f_i) | sin(py / f_i) | cos(px / f_i) | cos(py / f_i) ],  i < D / 4,  f_i = pe_div[i] (:173-186)
@@ -156,18 +140,21 @@ __global__ void __launch_bounds__(256) cross_attention_kernel(const float* __res
     }
 }
 
-#define RC(call)                          \
-    do {                                  \
-        int rc__ = (call);                \
-        if (rc__ != AMDS_OK) return rc__; \
-    } while (0)
+}  // namespace
 
-inline int bg(const float* A, int lda, long sAo, long sAi, const float* B, int ldb, long sBo, long sBi, int tflags, float* Cm, int ldc, long sCo, long sCi,
-              int outer, int inner, int M, int N, int K, float alpha, const float* bias, int accumulate, void* st) {
-    return bgemm_f32_exact(A, lda, sAo, sAi, B, ldb, sBo, sBi, tflags, Cm, ldc, sCo, sCi, outer, inner, M, N, K, alpha, 0.0f, bias, accumulate, st);
+int pos_encoding_add(float* x, int Dp, int D, const float* pos, const float* pe_div, long rows, hipStream_t st) {
+    const long total = rows * D;
+    hipLaunchKernelGGL(pos_encoding_add_kernel, dim3((unsigned)std::min<long>(8192, (total + 255) / 256)), dim3(256), 0, st, x, Dp, D, pos, pe_div, rows);
+    AMDS_LAUNCH_CHECK("pos_encoding_add_kernel");
+    return AMDS_OK;
 }
 
-}  // namespace
+int broadcast_rows(const float* src, float* dst, long per_bag, long total, hipStream_t st) {
+    hipLaunchKernelGGL(broadcast_rows_kernel, dim3((unsigned)std::min<long>(4096, (total + 255) / 256)), dim3(256), 0, st, src, dst, per_bag, total);
+    AMDS_LAUNCH_CHECK("broadcast_rows_kernel");
+    return AMDS_OK;
+}
+
 }  // namespace amds
 
 using namespace amds;
@@ -206,31 +193,17 @@ extern "C" int amds_barspoon_forward(const amds_barspoon_cfg* cfg_host, const am
     // ---- projector: Linear + ReLU (:171), positional encodings (:173-186)
     const void* a = bags;
     if (!(bags_dtype == dt && c.n_feats == p.Fp)) {
-        const long total = M * p.Fp;
-        const int grid = (int)std::min<long>(8192, (total + 255) / 256);
-#define STAGE(TI, TO) hipLaunchKernelGGL((bs_stage_kernel<TI, TO>), dim3(grid), dim3(256), 0, st, (const TI*)bags, (long)c.n_feats, (TO*)(base + p.a), p.Fp, total, c.n_feats)
-        if (dt == AMDS_F16) {
-            if (bags_dtype == AMDS_F32) STAGE(float, f16); else if (bags_dtype == AMDS_F16) STAGE(f16, f16); else STAGE(bf16, f16);
-        } else {
-            if (bags_dtype == AMDS_F32) STAGE(float, bf16); else if (bags_dtype == AMDS_F16) STAGE(f16, bf16); else STAGE(bf16, bf16);
-        }
-#undef STAGE
-        AMDS_LAUNCH_CHECK("bs_stage_kernel");
+        RC(stage_rows_dt(bags, bags_dtype, c.n_feats, base + p.a, dt, p.Fp, M, c.n_feats, stream));
         a = base + p.a;
     }
     RC(amds_gemm(a, p.Fp, w.proj_w, p.Fp, (int)M, Dp, p.Fp, dt, AMDS_EPI_BIAS_RELU_F32, x, Dp, w.proj_b, nullptr, nullptr, 0, 0, 0, 1.0f, stream));
-    if (c.positional_encoding) {
-        const long total = M * D;
-        hipLaunchKernelGGL(pos_encoding_add_kernel, dim3((unsigned)std::min<long>(8192, (total + 255) / 256)), dim3(256), 0, st, x, Dp, D, positions, w.pe_div, M);
-        AMDS_LAUNCH_CHECK("pos_encoding_add_kernel");
-    }
+    if (c.positional_encoding) RC(pos_encoding_add(x, Dp, D, positions, w.pe_div, M, st));
     if (Dp != D) AMDS_HIP(hipMemsetAsync(h, 0, (size_t)M * Dp * 2, st));      // LayerNorm writes the first D columns only
 
     // ---- encoder (:188): pre-norm layers on the 16-bit MFMA path, the MIL `vit` head's layer with ReLU
     for (int l = 0; l < c.enc_layers; ++l) {
         const amds_mil_vit_layer& L = w.enc_layers_host[l];
-        AMDS_REQUIRE(L.ln1_w && L.ln1_b && L.in_w && L.in_b && L.out_w && L.out_b && L.ln2_w && L.ln2_b && L.fc1_w && L.fc1_b && L.fc2_w && L.fc2_b,
-                     "amds_barspoon_forward: incomplete weights of encoder layer %d", l);
+        AMDS_REQUIRE(enc_layer_complete(L), "amds_barspoon_forward: incomplete weights of encoder layer %d", l);
         RC(amds_layernorm(x, Dp, L.ln1_w, L.ln1_b, h, Dp, (int)M, D, 1e-5f, dt, stream));
         RC(amds_gemm(h, Dp, L.in_w, Dp, (int)M, 3 * p.Da, Dp, dt, AMDS_EPI_BIAS, qkv, 3 * p.Da, L.in_b, nullptr, nullptr, 0, 0, 0, 1.0f, stream));
         RC(amds_attention(qkv, att, Bb, T, p.Ha, dt, stream));
@@ -246,11 +219,7 @@ extern "C" int amds_barspoon_forward(const amds_barspoon_cfg* cfg_host, const am
     float *tok = reinterpret_cast<float*>(base + p.tok), *th = reinterpret_cast<float*>(base + p.th), *tqkv = reinterpret_cast<float*>(base + p.tqkv);
     float *tsc = reinterpret_cast<float*>(base + p.tsc), *to = reinterpret_cast<float*>(base + p.to), *tq = reinterpret_cast<float*>(base + p.tq);
     float* tu = reinterpret_cast<float*>(base + p.tu);
-    {
-        const long total = M2 * D;
-        hipLaunchKernelGGL(broadcast_rows_kernel, dim3((unsigned)std::min<long>(4096, (total + 255) / 256)), dim3(256), 0, st, w.class_tokens, tok, (long)nt * D, total);
-        AMDS_LAUNCH_CHECK("broadcast_rows_kernel");
-    }
+    RC(broadcast_rows(w.class_tokens, tok, (long)nt * D, M2 * D, st));
     const float sa_scale = (float)(1.0 / sqrt((double)hd));
     for (int l = 0; l < c.dec_layers; ++l) {
         const amds_barspoon_dec_layer& L = w.dec_layers_host[l];

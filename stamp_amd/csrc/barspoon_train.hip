@@ -10,13 +10,10 @@
 // reduction over tiles runs through fixed-order partials (no float atomics), nothing is allocated and the host never waits for the device.
 #include <algorithm>
 #include <vector>
-#include "launch.h"
+#include "barspoon_common.h"
 
 namespace amds {
 namespace {
-
-inline int up(int n, int m) { return (n + m - 1) / m * m; }
-inline size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
 
 constexpr int CA_KEYS = 256;       // keys per workgroup of the cross-attention backward (one per lane)
 constexpr int CA_JB = 16;          // queries per pass of that kernel (the LDS tile of dS)
@@ -217,51 +214,9 @@ __global__ void __launch_bounds__(256) cross_attn_dq_reduce_kernel(const float* 
     }
 }
 
-// bags in any of the three types -> 16-bit operand rows of pitch Fp, padding columns zero
-template <typename TI, typename TO>
-__global__ void __launch_bounds__(256) bt_stage_kernel(const TI* __restrict__ src, long ld_src, TO* __restrict__ dst, int Fp, long total, int F) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (; i < total; i += stride) {
-        const long r = i / Fp;
-        const int c = (int)(i - r * Fp);
-        dst[i] = c < F ? (TO)(float)src[r * ld_src + c] : (TO)0.f;
-    }
-}
-
-// x[r][c] += PE(pos[r])[c] for c < D:  [ sin(px / f_i) | sin(py / f_i) | cos(px / f_i) | cos(py / f_i) ],  i < D / 4,  f_i = pe_div[i] (:173-186)
-__global__ void __launch_bounds__(256) bt_pos_encoding_add_kernel(float* __restrict__ x, int Dp, int D, const float* __restrict__ pos, const float* __restrict__ pe_div,
-                                                                long rows) {
-    const int q = D / 4;
-    const long total = rows * D;
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (; i < total; i += stride) {
-        const long r = i / D;
-        const int c = (int)(i - r * D);
-        const int blk = c / q, f = c - blk * q;                // blk: 0 sin x, 1 sin y, 2 cos x, 3 cos y
-        const float a = pos[2 * r + (blk & 1)] / pe_div[f];
-        x[r * Dp + c] += blk < 2 ? sinf(a) : cosf(a);
-    }
-}
-
-__global__ void __launch_bounds__(256) bt_broadcast_rows_kernel(const float* __restrict__ src, float* __restrict__ dst, long per_bag, long total) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (; i < total; i += stride) dst[i] = src[i % per_bag];
-}
-
-#define RC(call)                          \
-    do {                                  \
-        int rc__ = (call);                \
-        if (rc__ != AMDS_OK) return rc__; \
-    } while (0)
-
-constexpr int CFG_TRAIN = -2;      // amds_gemm_ex: by shape, a ragged last row tile as its own small launch
-
-struct Dims {
+struct Dims : PadDims {
     int F, D, He, Hd, FF, Le, Ld, nt, pe, dt;
-    int Fp, Dp, FFp, Ha, Da, Db, KVp, hd_d, Bb, T, nchunk;
+    int Db, KVp, hd_d, Bb, T, nchunk;
     long M, M2;
 };
 
@@ -277,8 +232,8 @@ int make_dims(const amds_barspoon_cfg* c, int Bb, int T, Dims* d) {
     AMDS_REQUIRE(Bb > 0 && T > 0 && Bb <= 65535 && (long)Bb * c->dec_heads <= 65535, "amds_barspoon_train: bad shape bags=%d tiles=%d", Bb, T);
     d->F = c->n_feats; d->D = c->dim; d->He = c->enc_heads; d->Hd = c->dec_heads; d->FF = c->ff; d->Le = c->enc_layers; d->Ld = c->dec_layers;
     d->nt = c->n_targets; d->pe = c->positional_encoding != 0; d->dt = c->dtype;
-    d->Fp = up(d->F, 256); d->Dp = up(d->D, 256); d->FFp = up(d->FF, 256); d->Ha = up(d->He, 4); d->Da = 64 * d->Ha;
-    d->Db = 64 * d->Hd; d->KVp = up(2 * d->Db, 256); d->hd_d = d->D / d->Hd;
+    static_cast<PadDims&>(*d) = pad_dims(d->F, d->D, d->FF, d->He);
+    d->Db = 64 * d->Hd; d->KVp = round_up(2 * d->Db, 256); d->hd_d = d->D / d->Hd;
     d->Bb = Bb; d->T = T; d->nchunk = (T + CA_KEYS - 1) / CA_KEYS;
     d->M = (long)Bb * T; d->M2 = (long)Bb * d->nt;
     AMDS_REQUIRE(d->M < (1L << 31) - 65536, "amds_barspoon_train: %ld tile rows do not fit the 32-bit row index", d->M);
@@ -295,40 +250,39 @@ struct SavedPlan {
 };
 
 void plan_saved(const Dims& d, SavedPlan* p) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    Arena ar;
     const size_t M = d.M, M2 = d.M2, D = d.D;
-    p->a = take(M * d.Fp * 2);
-    p->zp = take(M * d.Dp * 2);
-    p->x_bytes = al(M * d.Dp * 4);
-    p->x0 = take(p->x_bytes * (d.Le + 1));
-    p->xe16 = take(M * d.Dp * 2);
-    p->y = take(M * d.Dp * 4);                                   // scratch of the forward's `x + drop(y)` sites
+    p->a = ar.take(M * d.Fp * 2);
+    p->zp = ar.take(M * d.Dp * 2);
+    p->x_bytes = align256(M * d.Dp * 4);
+    p->x0 = ar.take(p->x_bytes * (d.Le + 1));
+    p->xe16 = ar.take(M * d.Dp * 2);
+    p->y = ar.take(M * d.Dp * 4);                                   // scratch of the forward's `x + drop(y)` sites
     p->enc.resize(d.Le);
     for (int l = 0; l < d.Le; ++l) {
         EncOff& o = p->enc[l];
-        o.h1 = take(M * d.Dp * 2); o.mu1 = take(M * 4); o.rs1 = take(M * 4);
-        o.qkv = take(M * 3 * d.Da * 2); o.att = take(M * d.Da * 2); o.lse = take((size_t)d.Bb * d.Ha * d.T * 4);
-        o.x_mid = take(M * d.Dp * 4);
-        o.h2 = take(M * d.Dp * 2); o.mu2 = take(M * 4); o.rs2 = take(M * 4);
-        o.z = take(M * d.FFp * 2); o.u = take(M * d.FFp * 2);
+        o.h1 = ar.take(M * d.Dp * 2); o.mu1 = ar.take(M * 4); o.rs1 = ar.take(M * 4);
+        o.qkv = ar.take(M * 3 * d.Da * 2); o.att = ar.take(M * d.Da * 2); o.lse = ar.take((size_t)d.Bb * d.Ha * d.T * 4);
+        o.x_mid = ar.take(M * d.Dp * 4);
+        o.h2 = ar.take(M * d.Dp * 2); o.mu2 = ar.take(M * 4); o.rs2 = ar.take(M * 4);
+        o.z = ar.take(M * d.FFp * 2); o.u = ar.take(M * d.FFp * 2);
     }
-    p->tok_bytes = al(M2 * D * 4);
-    p->tok0 = take(p->tok_bytes * (d.Ld + 1));
-    p->ty = take(M2 * D * 4);
+    p->tok_bytes = align256(M2 * D * 4);
+    p->tok0 = ar.take(p->tok_bytes * (d.Ld + 1));
+    p->ty = ar.take(M2 * D * 4);
     p->dec.resize(d.Ld);
     const size_t pp = (size_t)d.Bb * d.Hd * d.nt * d.nt * 4;
     for (int l = 0; l < d.Ld; ++l) {
         DecOff& o = p->dec[l];
-        o.th1 = take(M2 * D * 4); o.mu1 = take(M2 * 4); o.rs1 = take(M2 * 4);
-        o.tqkv = take(M2 * 3 * D * 4); o.P = take(pp); o.Pd = take(pp); o.to = take(M2 * D * 4); o.t_mid1 = take(M2 * D * 4);
-        o.th2 = take(M2 * D * 4); o.mu2 = take(M2 * 4); o.rs2 = take(M2 * 4);
-        o.tq = take(M2 * D * 4); o.kv = take(M * 2 * d.Db * 2); o.clse = take((size_t)d.Bb * d.Hd * d.nt * 4); o.co = take(M2 * D * 4);
-        o.t_mid2 = take(M2 * D * 4);
-        o.th3 = take(M2 * D * 4); o.mu3 = take(M2 * 4); o.rs3 = take(M2 * 4);
-        o.tz = take(M2 * (size_t)d.FF * 4); o.tu = take(M2 * (size_t)d.FF * 4);
+        o.th1 = ar.take(M2 * D * 4); o.mu1 = ar.take(M2 * 4); o.rs1 = ar.take(M2 * 4);
+        o.tqkv = ar.take(M2 * 3 * D * 4); o.P = ar.take(pp); o.Pd = ar.take(pp); o.to = ar.take(M2 * D * 4); o.t_mid1 = ar.take(M2 * D * 4);
+        o.th2 = ar.take(M2 * D * 4); o.mu2 = ar.take(M2 * 4); o.rs2 = ar.take(M2 * 4);
+        o.tq = ar.take(M2 * D * 4); o.kv = ar.take(M * 2 * d.Db * 2); o.clse = ar.take((size_t)d.Bb * d.Hd * d.nt * 4); o.co = ar.take(M2 * D * 4);
+        o.t_mid2 = ar.take(M2 * D * 4);
+        o.th3 = ar.take(M2 * D * 4); o.mu3 = ar.take(M2 * 4); o.rs3 = ar.take(M2 * 4);
+        o.tz = ar.take(M2 * (size_t)d.FF * 4); o.tu = ar.take(M2 * (size_t)d.FF * 4);
     }
-    p->total = off;
+    p->total = ar.off;
 }
 
 struct WsPlan {
@@ -337,20 +291,19 @@ struct WsPlan {
 };
 
 void plan_ws(const Dims& d, int split_k, WsPlan* p) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    Arena ar;
     const size_t M = d.M, M2 = d.M2, D = d.D;
-    p->dx = take(M * d.Dp * 4);
-    p->dh = take(M * d.Dp * 4);
-    p->g16 = take(M * d.Dp * 2);
-    p->du = take(M * d.FFp * 2);
-    p->dz = take(M * d.FFp * 2);
-    p->datt = take(M * d.Da * 2);
-    p->dqkv = take(M * 3 * d.Da * 2);
-    p->dqs = take((size_t)d.Bb * d.Ha * d.T * 4);
-    p->dkv = take(M * d.KVp * 2);
+    p->dx = ar.take(M * d.Dp * 4);
+    p->dh = ar.take(M * d.Dp * 4);
+    p->g16 = ar.take(M * d.Dp * 2);
+    p->du = ar.take(M * d.FFp * 2);
+    p->dz = ar.take(M * d.FFp * 2);
+    p->datt = ar.take(M * d.Da * 2);
+    p->dqkv = ar.take(M * 3 * d.Da * 2);
+    p->dqs = ar.take((size_t)d.Bb * d.Ha * d.T * 4);
+    p->dkv = ar.take(M * d.KVp * 2);
     const size_t nk = std::max(std::max(std::max((size_t)3 * d.Da * d.Dp, (size_t)d.FFp * d.Dp), std::max((size_t)d.Dp * d.Da, (size_t)d.Dp * d.Fp)), (size_t)d.KVp * d.Dp);
-    p->part = take(nk * split_k * 4);
+    p->part = ar.take(nk * split_k * 4);
     size_t cs = amds_colsum_workspace_bytes(split_k, (int)std::min<size_t>(nk, 0x7fffffff));
     const int wide[] = {d.Dp, d.FFp, 3 * d.Da, d.KVp};
     for (int w : wide) cs = std::max(cs, amds_colsum_workspace_bytes((int)d.M, w));
@@ -358,39 +311,19 @@ void plan_ws(const Dims& d, int split_k, WsPlan* p) {
     for (int w : narrow) cs = std::max(cs, amds_colsum_workspace_bytes((int)d.M2, w));
     cs = std::max(cs, amds_colsum_workspace_bytes(d.Bb, (int)std::min<long>((long)d.nt * d.D, 0x7fffffff)));
     p->cs_bytes = std::max<size_t>(cs, 4);
-    p->cs = take(p->cs_bytes);
+    p->cs = ar.take(p->cs_bytes);
     p->lnb_bytes = std::max<size_t>(std::max(amds_layernorm_bwd_workspace_bytes((int)d.M, d.D), amds_layernorm_bwd_workspace_bytes((int)d.M2, d.D)), 4);
-    p->lnb = take(p->lnb_bytes);
-    p->dt = take(M2 * D * 4);
-    p->dy = take(M2 * D * 4);
-    p->d1 = take(M2 * (size_t)std::max(d.FF, 3 * d.D) * 4);
-    p->d2 = take(M2 * (size_t)std::max(d.FF, d.D) * 4);
-    p->dth = take(M2 * D * 4);
-    p->dP = take((size_t)d.Bb * d.Hd * d.nt * d.nt * 4);
-    p->dtq = take(M2 * D * 4);
+    p->lnb = ar.take(p->lnb_bytes);
+    p->dt = ar.take(M2 * D * 4);
+    p->dy = ar.take(M2 * D * 4);
+    p->d1 = ar.take(M2 * (size_t)std::max(d.FF, 3 * d.D) * 4);
+    p->d2 = ar.take(M2 * (size_t)std::max(d.FF, d.D) * 4);
+    p->dth = ar.take(M2 * D * 4);
+    p->dP = ar.take((size_t)d.Bb * d.Hd * d.nt * d.nt * 4);
+    p->dtq = ar.take(M2 * D * 4);
     p->dqp_bytes = std::max<size_t>(amds_cross_attention_bwd_workspace_bytes(d.Bb, d.T, d.nt, d.Hd), 4);
-    p->dqp = take(p->dqp_bytes);
-    p->total = off;
-}
-
-int gemm_dt(int dt, const void* A, long lda, const void* W, long ldw, long M, int N, int K, int epi, void* out, long ldo, const float* bias, void* st) {
-    return amds_gemm_ex(CFG_TRAIN, A, lda, W, ldw, (int)M, N, K, dt, epi, out, ldo, bias, nullptr, nullptr, 0, 0, 0, 1.0f, st);
-}
-
-// exact-fp32 batched product (amds_bgemm_f32's argument order without `diag`)
-inline int bg(const float* A, int lda, long sAo, long sAi, const float* B, int ldb, long sBo, long sBi, int tflags, float* Cm, int ldc, long sCo, long sCi,
-              int outer, int inner, int M, int N, int K, float alpha, const float* bias, int accumulate, void* st) {
-    return bgemm_f32_exact(A, lda, sAo, sAi, B, ldb, sBo, sBi, tflags, Cm, ldc, sCo, sCi, outer, inner, M, N, K, alpha, 0.0f, bias, accumulate, st);
-}
-// y[M][N] = x[M][K] w[N][K]^T + bias;   dx[M][K] = dy[M][N] w[N][K];   dw[N][K] = dy[M][N]^T x[M][K]
-inline int lin(const float* x, const float* w, const float* bias, float* y, long M, int N, int K, void* st) {
-    return bg(x, K, 0, 0, w, K, 0, 0, 1, y, N, 0, 0, 1, 1, (int)M, N, K, 1.0f, bias, 0, st);
-}
-inline int lin_dx(const float* dy, const float* w, float* dx, long M, int N, int K, void* st) {
-    return bg(dy, N, 0, 0, w, K, 0, 0, 0, dx, K, 0, 0, 1, 1, (int)M, K, N, 1.0f, nullptr, 0, st);
-}
-inline int lin_dw(const float* dy, const float* x, float* dw, long M, int N, int K, void* st) {
-    return bg(dy, N, 0, 0, x, K, 0, 0, 2, dw, K, 0, 0, 1, 1, N, K, (int)M, 1.0f, nullptr, 0, st);
+    p->dqp = ar.take(p->dqp_bytes);
+    p->total = ar.off;
 }
 
 bool weights_ok(const Dims& d, const amds_barspoon_train_weights* tw, bool backward) {
@@ -400,8 +333,7 @@ bool weights_ok(const Dims& d, const amds_barspoon_train_weights* tw, bool backw
         return false;
     for (int l = 0; l < d.Le; ++l) {
         const amds_mil_vit_layer& L = w.enc_layers_host[l];
-        if (!(L.ln1_w && L.ln1_b && L.in_w && L.in_b && L.out_w && L.out_b && L.ln2_w && L.ln2_b && L.fc1_w && L.fc1_b && L.fc2_w && L.fc2_b)) return false;
-        if (backward && !(L.in_wt && L.out_wt && L.fc1_wt && L.fc2_wt)) return false;
+        if (!enc_layer_complete(L) || (backward && !enc_layer_has_transposes(L))) return false;
     }
     for (int l = 0; l < d.Ld; ++l) {
         const amds_barspoon_dec_layer& L = w.dec_layers_host[l];
@@ -522,34 +454,19 @@ extern "C" int amds_barspoon_train_forward(const amds_barspoon_cfg* cfg_host, co
     const int dt = d.dt, Dp = d.Dp, Da = d.Da, FFp = d.FFp, Fp = d.Fp, D = d.D, Bb = d.Bb, T = d.T, Ha = d.Ha, nt = d.nt, Hd = d.Hd, hd = d.hd_d, FF = d.FF;
     const long M = d.M, M2 = d.M2;
     auto gemm = [&](const void* A, long lda, const void* W, long ldw, long Mr, int N, int K, int epi, void* out, long ldo, const float* bias) -> int {
-        return gemm_dt(dt, A, lda, W, ldw, Mr, N, K, epi, out, ldo, bias, stream);
+        return gemm_train(dt, A, lda, W, ldw, Mr, N, K, epi, out, ldo, bias, stream);
     };
 
     // ---- projector: Linear + ReLU (:171), positional encodings (:173-186); no dropout
     void* a = sv + sp.a;
     if (bags_dtype == dt && Fp == d.F) AMDS_HIP(hipMemcpyAsync(a, bags, (size_t)M * Fp * 2, hipMemcpyDeviceToDevice, st));
-    else {
-        const long total = M * Fp;
-        const int grid = (int)std::min<long>(8192, (total + 255) / 256);
-#define AMDS_STAGE(TI, TO) hipLaunchKernelGGL((bt_stage_kernel<TI, TO>), dim3(grid), dim3(256), 0, st, (const TI*)bags, (long)d.F, (TO*)a, Fp, total, d.F)
-        if (dt == AMDS_BF16) {
-            if (bags_dtype == AMDS_F32) AMDS_STAGE(float, bf16); else if (bags_dtype == AMDS_F16) AMDS_STAGE(f16, bf16); else AMDS_STAGE(bf16, bf16);
-        } else {
-            if (bags_dtype == AMDS_F32) AMDS_STAGE(float, f16); else if (bags_dtype == AMDS_F16) AMDS_STAGE(f16, f16); else AMDS_STAGE(bf16, f16);
-        }
-#undef AMDS_STAGE
-        AMDS_LAUNCH_CHECK("bt_stage_kernel");
-    }
+    else RC(stage_rows_dt(bags, bags_dtype, d.F, a, dt, Fp, M, d.F, stream));
     void* zp = sv + sp.zp;
     float* x = reinterpret_cast<float*>(sv + sp.x0);
     float* y = reinterpret_cast<float*>(sv + sp.y);
     RC(gemm(a, Fp, w.proj_w, Fp, M, Dp, Fp, AMDS_EPI_BIAS, zp, Dp, w.proj_b));
     RC(amds_relu_dropout_fwd(zp, x, M * Dp, dt, AMDS_F32, 0.f, 0, 0, stream));
-    if (d.pe) {
-        const long total = M * D;
-        hipLaunchKernelGGL(bt_pos_encoding_add_kernel, dim3((unsigned)std::min<long>(8192, (total + 255) / 256)), dim3(256), 0, st, x, Dp, D, positions, w.pe_div, M);
-        AMDS_LAUNCH_CHECK("bt_pos_encoding_add_kernel");
-    }
+    if (d.pe) RC(pos_encoding_add(x, Dp, D, positions, w.pe_div, M, st));
 
     // ---- encoder (:188): x += drop(SA(LN1(x)));  x += drop(W2 drop(relu(W1 LN2(x))))
     for (int l = 0; l < d.Le; ++l) {
@@ -594,12 +511,7 @@ extern "C" int amds_barspoon_train_forward(const amds_barspoon_cfg* cfg_host, co
 
     // ---- decoder (:190-193): the class tokens, exact fp32
     float* ty = reinterpret_cast<float*>(sv + sp.ty);
-    {
-        float* tok = reinterpret_cast<float*>(sv + sp.tok0);
-        const long total = M2 * D;
-        hipLaunchKernelGGL(bt_broadcast_rows_kernel, dim3((unsigned)std::min<long>(4096, (total + 255) / 256)), dim3(256), 0, st, w.class_tokens, tok, (long)nt * D, total);
-        AMDS_LAUNCH_CHECK("bt_broadcast_rows_kernel");
-    }
+    RC(broadcast_rows(w.class_tokens, reinterpret_cast<float*>(sv + sp.tok0), (long)nt * D, M2 * D, st));
     const float sa_scale = (float)(1.0 / sqrt((double)hd));
     for (int l = 0; l < d.Ld; ++l) {
         const amds_barspoon_dec_layer& L = w.dec_layers_host[l];
@@ -689,7 +601,7 @@ extern "C" int amds_barspoon_train_backward(const amds_barspoon_cfg* cfg_host, c
     const int dt = d.dt, Dp = d.Dp, Da = d.Da, FFp = d.FFp, Fp = d.Fp, D = d.D, Bb = d.Bb, T = d.T, Ha = d.Ha, nt = d.nt, Hd = d.Hd, hd = d.hd_d, FF = d.FF, KVp = d.KVp;
     const long M = d.M, M2 = d.M2;
     auto gemm = [&](const void* A, long lda, const void* W, long ldw, long Mr, int N, int K, int epi, void* out, long ldo, const float* bias) -> int {
-        return gemm_dt(dt, A, lda, W, ldw, Mr, N, K, epi, out, ldo, bias, stream);
+        return gemm_train(dt, A, lda, W, ldw, Mr, N, K, epi, out, ldo, bias, stream);
     };
     auto Wf = [&](size_t off) { return reinterpret_cast<float*>(wk + off); };
     auto Sf = [&](size_t off) { return reinterpret_cast<const float*>(sv + off); };

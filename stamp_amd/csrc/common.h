@@ -357,6 +357,8 @@ int nystrom_attn_bwd_ex(const amds_transmil_layer* w_host, int dim, const float*
 int layernorm_bwd_cast_dt(const float* dy, long dy_stride, const float* x, long x_stride, const float* mean, const float* rstd, const float* gamma, float* dx, long dx_stride,
                           int add_skip, float* dgamma, float* dbeta, int accumulate_params, int rows, int cols, void* ws, size_t ws_bytes, void* dx16, long dx16_stride,
                           int dx16_dtype, float p, uint64_t seed, uint32_t stream_id, void* stream);
+// the MIL heads' bag staging (elementwise.hip): [rows][F] fp32 / f16 / bf16 of pitch ld_src -> zero-padded f16 / bf16 rows of pitch Fp; min(8192, total / 256) blocks
+int stage_rows_dt(const void* src, int src_dtype, long ld_src, void* dst, int dst_dtype, int Fp, long rows, int F, void* stream);
 
 // amds_bgemm_f32 on the exact-fp32 MFMA whatever amds_set_matmul_precision says (transmil.hip): for the paths that promise exact fp32
 // ragged (variable-length) bags without padding, attention_flash.hip: a table built once per call from device offsets [n_bags + 1] (tile counts; bag i's

@@ -245,6 +245,35 @@ __global__ void cast_pad_kernel(const float* __restrict__ src, int ld_src, TO* _
     }
 }
 
+// rows [rows][F] (fp32 / f16 / bf16, pitch ld_src) -> 16-bit operand rows [rows][Fp], zero padded: the staging of every MIL head's bags (model_call.h)
+template <typename TI, typename TO>
+__global__ void __launch_bounds__(256) stage_rows_kernel(const TI* __restrict__ src, long ld_src, TO* __restrict__ dst, int Fp, long total, int F) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (; i < total; i += stride) {
+        const long r = i / Fp;
+        const int c = (int)(i - r * Fp);
+        dst[i] = c < F ? (TO)(float)src[r * ld_src + c] : (TO)0.f;
+    }
+}
+
+int stage_rows_dt(const void* src, int src_dtype, long ld_src, void* dst, int dst_dtype, int Fp, long rows, int F, void* stream) {
+    const long total = rows * Fp;
+    const int grid = (int)min((long)8192, (total + 255) / 256);
+    hipStream_t st = (hipStream_t)stream;
+    bool ok = false;
+    dispatch_16(dst_dtype, [&](auto to) {
+        typedef AMDS_TAG_T(to) TO;
+        ok = dispatch_16_32(src_dtype, [&](auto ti) {
+            typedef AMDS_TAG_T(ti) TI;
+            hipLaunchKernelGGL((stage_rows_kernel<TI, TO>), dim3(grid), dim3(256), 0, st, (const TI*)src, ld_src, (TO*)dst, Fp, total, F);
+        });
+    });
+    if (!ok) { set_error("stage_rows_dt: no kernel for dtypes %d -> %d", src_dtype, dst_dtype); return AMDS_ERR_INVALID; }      // (every caller has checked both)
+    AMDS_LAUNCH_CHECK("stage_rows_kernel");
+    return AMDS_OK;
+}
+
 // rows of a SwiGLUPacked fc1: [gate 0..H) | value 0..H)]  ->  blocks of 32: [gate 32j..][value 32j..]
 __global__ void pack_swiglu_rows_kernel(const float* __restrict__ src, float* __restrict__ dst, int H, int cols) {
     const long total = 2L * H * cols;

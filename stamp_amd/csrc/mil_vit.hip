@@ -8,18 +8,13 @@
 // out of the kernels the rest of the library already exposes one by one (amds_gemm, amds_layernorm, amds_attention*, amds_linear_f32);
 // the host only supplies padded device weights (amds_mil_vit_weights) and one workspace.  Nothing is allocated, no host
 // synchronisation happens: the call is a plain sequence of launches on `stream` (it can be captured in a hipGraph).
-#include "common.h"
-#include <atomic>
+#include "model_call.h"
 
 namespace amds {
 
 namespace {
 
-inline int up(int n, int m) { return (n + m - 1) / m * m; }
-inline size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
-
-struct MilPlan {
-    int Fp, Dp, FFp, Ha, Da;
+struct MilPlan : PadDims {
     size_t a, x, h, qkv, att, u, cls, coords, pad, total;
 };
 
@@ -30,37 +25,20 @@ int mil_plan(const amds_mil_vit_cfg* c, int Bb, int Tn, MilPlan* p) {
                  c->dim, c->heads);
     AMDS_REQUIRE(c->dtype == AMDS_F16 || c->dtype == AMDS_BF16, "amds_mil_vit: operand dtype must be f16 or bf16");
     AMDS_REQUIRE(Bb >= 0 && Tn > 0, "amds_mil_vit: bad shape bags=%d tiles=%d (empty bags have no class-token context)", Bb, Tn);
-    p->Fp = up(c->n_feats, 256);
-    p->Dp = up(c->dim, 256);
-    p->FFp = up(c->ff, 256);
-    p->Ha = up(c->heads, 4);
-    p->Da = 64 * p->Ha;
+    static_cast<PadDims&>(*p) = pad_dims(c->n_feats, c->dim, c->ff, c->heads);
     const size_t M = (size_t)Bb * (Tn + 1), Mt = (size_t)Bb * Tn;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-    p->a = take(Mt * p->Fp * 2);                    // staged bags, 16-bit, zero padded columns
-    p->x = take(M * p->Dp * 4);                     // residual stream fp32
-    p->h = take(M * p->Dp * 2);                     // LayerNorm output
-    p->qkv = take(M * 3 * p->Da * 2);
-    p->att = take(M * p->Da * 2);
-    p->u = take(M * p->FFp * 2);
-    p->cls = take((size_t)Bb * c->dim * 4);
-    p->coords = take(M * 2 * 4);
-    p->pad = take(M);
-    p->total = off;
+    Arena ar;
+    p->a = ar.take(Mt * p->Fp * 2);                    // staged bags, 16-bit, zero padded columns
+    p->x = ar.take(M * p->Dp * 4);                     // residual stream fp32
+    p->h = ar.take(M * p->Dp * 2);                     // LayerNorm output
+    p->qkv = ar.take(M * 3 * p->Da * 2);
+    p->att = ar.take(M * p->Da * 2);
+    p->u = ar.take(M * p->FFp * 2);
+    p->cls = ar.take((size_t)Bb * c->dim * 4);
+    p->coords = ar.take(M * 2 * 4);
+    p->pad = ar.take(M);
+    p->total = ar.off;
     return AMDS_OK;
-}
-
-// bags [Mt][F] (fp32 / f16 / bf16) -> 16-bit operand rows [Mt][Fp], zero padded
-template <typename TI, typename TO>
-__global__ void __launch_bounds__(256) stage_bags_kernel(const TI* __restrict__ src, long ld_src, TO* __restrict__ dst, int Fp, long total, int F) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (; i < total; i += stride) {
-        const long r = i / Fp;
-        const int c = (int)(i - r * Fp);
-        dst[i] = c < F ? (TO)(float)src[r * ld_src + c] : (TO)0.f;
-    }
 }
 
 // x rows: the class token in front of each bag's projected tiles; coords with the class token at (0, 0); padding mask with a leading 0
@@ -102,8 +80,7 @@ extern "C" int amds_mil_vit_forward(const amds_mil_vit_cfg* cfg_host, const amds
     const amds_mil_vit_cfg& c = *cfg_host;
     const amds_mil_vit_weights& w = *w_host;
     MilPlan p;
-    int rc = mil_plan(cfg_host, n_bags, n_tiles, &p);
-    if (rc != AMDS_OK) return rc;
+    RC(mil_plan(cfg_host, n_bags, n_tiles, &p));
     AMDS_REQUIRE(w.class_token && w.proj_w && w.proj_b && w.norm_w && w.norm_b && w.head_w && (c.layers == 0 || w.layers_host),
                  "amds_mil_vit_forward: incomplete weights");
     AMDS_REQUIRE(!c.alibi || coords, "amds_mil_vit_forward: use_alibi=True needs coords");
@@ -131,27 +108,12 @@ extern "C" int amds_mil_vit_forward(const amds_mil_vit_cfg* cfg_host, const amds
     // project_features: the bags as 16-bit operand rows (already in that form when dtype and pitch agree)
     const void* a = bags;
     if (!(bags_dtype == dt && c.n_feats == p.Fp)) {
-        const long total = Mt * p.Fp;
-        const int grid = (int)min((long)8192, (total + 255) / 256);
-#define STAGE(TI, TO) hipLaunchKernelGGL((stage_bags_kernel<TI, TO>), dim3(grid), dim3(256), 0, st, (const TI*)bags, (long)c.n_feats, (TO*)(base + p.a), \
-                                         p.Fp, total, c.n_feats)
-        if (dt == AMDS_F16) {
-            if (bags_dtype == AMDS_F32) STAGE(float, f16);
-            else if (bags_dtype == AMDS_F16) STAGE(f16, f16);
-            else STAGE(bf16, f16);
-        } else {
-            if (bags_dtype == AMDS_F32) STAGE(float, bf16);
-            else if (bags_dtype == AMDS_F16) STAGE(f16, bf16);
-            else STAGE(bf16, bf16);
-        }
-#undef STAGE
-        AMDS_LAUNCH_CHECK("stage_bags_kernel");
+        RC(stage_rows_dt(bags, bags_dtype, c.n_feats, base + p.a, dt, p.Fp, Mt, c.n_feats, stream));
         a = base + p.a;
     }
     // Linear + GELU in fp32 into scratch (the qkv region: 6 Da >= 4 Dp bytes per row always), then the rows move behind the class tokens
     float* proj = reinterpret_cast<float*>(qkv);
-    if ((rc = amds_gemm(a, p.Fp, w.proj_w, p.Fp, (int)Mt, Dp, p.Fp, dt, AMDS_EPI_BIAS_GELU_F32, proj, Dp, w.proj_b, nullptr, nullptr, 0, 0, 0, 1.0f,
-                        stream)) != AMDS_OK) return rc;
+    RC(amds_gemm(a, p.Fp, w.proj_w, p.Fp, (int)Mt, Dp, p.Fp, dt, AMDS_EPI_BIAS_GELU_F32, proj, Dp, w.proj_b, nullptr, nullptr, 0, 0, 0, 1.0f, stream));
     hipLaunchKernelGGL(prefix_cls_kernel, dim3((unsigned)M), dim3(128), 0, st, w.class_token, proj, x, Dp, coords, cw, mask, pad, Tn);
     AMDS_LAUNCH_CHECK("prefix_cls_kernel");
     if (Dp != D) AMDS_HIP(hipMemsetAsync(h, 0, (size_t)M * Dp * 2, st));      // LayerNorm writes the first D columns only
@@ -160,11 +122,10 @@ extern "C" int amds_mil_vit_forward(const amds_mil_vit_cfg* cfg_host, const amds
     // mask changes nothing for the class query: the reference's mask blocks (padded query, padded key) pairs and the class token as a KEY of the tile queries
     // (vision_tranformer.py:356-368) -- the class token is never padded, so its own row attends to every key, exactly the unmasked one-query attention.
     const bool cls_tail = ctx_mil_cls_tail() && !c.alibi && S <= 32768 && (long)(Bb - 1) * S * Dp * 4 < (1L << 31);
-    for (int l = 0; l < c.layers && rc == AMDS_OK; ++l) {
+    for (int l = 0; l < c.layers; ++l) {
         const amds_mil_vit_layer& L = w.layers_host[l];
-        AMDS_REQUIRE(L.ln1_w && L.ln1_b && L.in_w && L.in_b && L.out_w && L.out_b && L.ln2_w && L.ln2_b && L.fc1_w && L.fc1_b && L.fc2_w && L.fc2_b &&
-                     (!c.alibi || L.head_scale), "amds_mil_vit_forward: incomplete weights of layer %d", l);
-        if ((rc = amds_layernorm(x, Dp, L.ln1_w, L.ln1_b, h, Dp, (int)M, D, 1e-5f, dt, stream)) != AMDS_OK) break;
+        AMDS_REQUIRE(enc_layer_complete(L) && (!c.alibi || L.head_scale), "amds_mil_vit_forward: incomplete weights of layer %d", l);
+        RC(amds_layernorm(x, Dp, L.ln1_w, L.ln1_b, h, Dp, (int)M, D, 1e-5f, dt, stream));
         if (cls_tail && l == c.layers - 1) {
             // Class-row tail: the head reads x[:, 0] behind this block and nothing else (reference vision_tranformer.py: `self.mlp_head(x[:, 0])`), so the block
             // computes keys | values of every token, and query, attention, output projection and MLP of the class rows alone (row b * S of the token-major
@@ -172,38 +133,30 @@ extern "C" int amds_mil_vit_forward(const amds_mil_vit_cfg* cfg_host, const amds
             const int esz = 2;
             const char* w_kv = reinterpret_cast<const char*>(L.in_w) + (size_t)p.Da * Dp * esz;
             char* qkv_kv = reinterpret_cast<char*>(qkv) + (size_t)p.Da * esz;
-            if ((rc = amds_gemm(h, Dp, w_kv, Dp, (int)M, 2 * p.Da, Dp, dt, AMDS_EPI_BIAS, qkv_kv, 3 * p.Da, L.in_b + p.Da, nullptr, nullptr, 0, 0, 0, 1.0f,
-                                stream)) != AMDS_OK) break;
+            RC(amds_gemm(h, Dp, w_kv, Dp, (int)M, 2 * p.Da, Dp, dt, AMDS_EPI_BIAS, qkv_kv, 3 * p.Da, L.in_b + p.Da, nullptr, nullptr, 0, 0, 0, 1.0f, stream));
             char* qc = reinterpret_cast<char*>(att);                          // [Bb][Da] queries | [Bb][Da] attention outputs (the att buffer is idle)
             char* oc = qc + (size_t)Bb * p.Da * esz;
-            if ((rc = amds_gemm(h, (long)S * Dp, L.in_w, Dp, Bb, p.Da, Dp, dt, AMDS_EPI_BIAS, qc, p.Da, L.in_b, nullptr, nullptr, 0, 0, 0, 1.0f,
-                                stream)) != AMDS_OK) break;
-            if ((rc = amds_attention_row(qc, p.Da, qkv, oc, p.Da, Bb, S, p.Ha, dt, stream)) != AMDS_OK) break;
-            if ((rc = amds_gemm(oc, p.Da, L.out_w, p.Da, Bb, Dp, p.Da, dt, AMDS_EPI_RESIDUAL, x, (long)S * Dp, L.out_b, nullptr, nullptr, 0, 0, 0, 1.0f,
-                                stream)) != AMDS_OK) break;
-            if ((rc = amds_layernorm(x, (long)S * Dp, L.ln2_w, L.ln2_b, h, Dp, Bb, D, 1e-5f, dt, stream)) != AMDS_OK) break;      // (h's first Bb rows: its LN1 rows are consumed)
-            if ((rc = amds_gemm(h, Dp, L.fc1_w, Dp, Bb, p.FFp, Dp, dt, AMDS_EPI_BIAS_GELU, u, p.FFp, L.fc1_b, nullptr, nullptr, 0, 0, 0, 1.0f,
-                                stream)) != AMDS_OK) break;
-            rc = amds_gemm(u, p.FFp, L.fc2_w, p.FFp, Bb, Dp, p.FFp, dt, AMDS_EPI_RESIDUAL, x, (long)S * Dp, L.fc2_b, nullptr, nullptr, 0, 0, 0, 1.0f, stream);
+            RC(amds_gemm(h, (long)S * Dp, L.in_w, Dp, Bb, p.Da, Dp, dt, AMDS_EPI_BIAS, qc, p.Da, L.in_b, nullptr, nullptr, 0, 0, 0, 1.0f, stream));
+            RC(amds_attention_row(qc, p.Da, qkv, oc, p.Da, Bb, S, p.Ha, dt, stream));
+            RC(amds_gemm(oc, p.Da, L.out_w, p.Da, Bb, Dp, p.Da, dt, AMDS_EPI_RESIDUAL, x, (long)S * Dp, L.out_b, nullptr, nullptr, 0, 0, 0, 1.0f, stream));
+            RC(amds_layernorm(x, (long)S * Dp, L.ln2_w, L.ln2_b, h, Dp, Bb, D, 1e-5f, dt, stream));      // (h's first Bb rows: its LN1 rows are consumed)
+            RC(amds_gemm(h, Dp, L.fc1_w, Dp, Bb, p.FFp, Dp, dt, AMDS_EPI_BIAS_GELU, u, p.FFp, L.fc1_b, nullptr, nullptr, 0, 0, 0, 1.0f, stream));
+            RC(amds_gemm(u, p.FFp, L.fc2_w, p.FFp, Bb, Dp, p.FFp, dt, AMDS_EPI_RESIDUAL, x, (long)S * Dp, L.fc2_b, nullptr, nullptr, 0, 0, 0, 1.0f, stream));
             continue;
         }
-        if ((rc = amds_gemm(h, Dp, L.in_w, Dp, (int)M, 3 * p.Da, Dp, dt, AMDS_EPI_BIAS, qkv, 3 * p.Da, L.in_b, nullptr, nullptr, 0, 0, 0, 1.0f,
-                            stream)) != AMDS_OK) break;
+        RC(amds_gemm(h, Dp, L.in_w, Dp, (int)M, 3 * p.Da, Dp, dt, AMDS_EPI_BIAS, qkv, 3 * p.Da, L.in_b, nullptr, nullptr, 0, 0, 0, 1.0f, stream));
         if (c.alibi)        // output bf16 (range of the distance term), so the output projection runs on bf16 operands
-            rc = pad ? amds_attention_alibi_masked(qkv, cw, L.head_scale, pad, att, Bb, S, p.Ha, dt, stream)
-                     : amds_attention_alibi(qkv, cw, L.head_scale, att, Bb, S, p.Ha, dt, stream);
+            RC(pad ? amds_attention_alibi_masked(qkv, cw, L.head_scale, pad, att, Bb, S, p.Ha, dt, stream)
+                   : amds_attention_alibi(qkv, cw, L.head_scale, att, Bb, S, p.Ha, dt, stream));
         else
-            rc = pad ? amds_attention_masked(qkv, pad, att, Bb, S, p.Ha, c.heads, dt, stream) : amds_attention(qkv, att, Bb, S, p.Ha, dt, stream);
-        if (rc != AMDS_OK) break;
-        if ((rc = amds_gemm(att, p.Da, L.out_w, p.Da, (int)M, Dp, p.Da, c.alibi ? AMDS_BF16 : dt, AMDS_EPI_RESIDUAL, x, Dp, L.out_b, nullptr, nullptr, 0,
-                            0, 0, 1.0f, stream)) != AMDS_OK) break;                                                       // x = attn(x) + x   (:291-292)
-        if ((rc = amds_layernorm(x, Dp, L.ln2_w, L.ln2_b, h, Dp, (int)M, D, 1e-5f, dt, stream)) != AMDS_OK) break;
-        if ((rc = amds_gemm(h, Dp, L.fc1_w, Dp, (int)M, p.FFp, Dp, dt, AMDS_EPI_BIAS_GELU, u, p.FFp, L.fc1_b, nullptr, nullptr, 0, 0, 0, 1.0f,
-                            stream)) != AMDS_OK) break;
-        rc = amds_gemm(u, p.FFp, L.fc2_w, p.FFp, (int)M, Dp, p.FFp, dt, AMDS_EPI_RESIDUAL, x, Dp, L.fc2_b, nullptr, nullptr, 0, 0, 0, 1.0f, stream);   // x = ff(x) + x (:293)
+            RC(pad ? amds_attention_masked(qkv, pad, att, Bb, S, p.Ha, c.heads, dt, stream) : amds_attention(qkv, att, Bb, S, p.Ha, dt, stream));
+        RC(amds_gemm(att, p.Da, L.out_w, p.Da, (int)M, Dp, p.Da, c.alibi ? AMDS_BF16 : dt, AMDS_EPI_RESIDUAL, x, Dp, L.out_b, nullptr, nullptr, 0, 0, 0, 1.0f,
+                     stream));                                                                                         // x = attn(x) + x   (:291-292)
+        RC(amds_layernorm(x, Dp, L.ln2_w, L.ln2_b, h, Dp, (int)M, D, 1e-5f, dt, stream));
+        RC(amds_gemm(h, Dp, L.fc1_w, Dp, (int)M, p.FFp, Dp, dt, AMDS_EPI_BIAS_GELU, u, p.FFp, L.fc1_b, nullptr, nullptr, 0, 0, 0, 1.0f, stream));
+        RC(amds_gemm(u, p.FFp, L.fc2_w, p.FFp, (int)M, Dp, p.FFp, dt, AMDS_EPI_RESIDUAL, x, Dp, L.fc2_b, nullptr, nullptr, 0, 0, 0, 1.0f, stream));   // x = ff(x) + x (:293)
     }
-    if (rc != AMDS_OK) return rc;
     // final LayerNorm on the class-token rows only (row stride = one bag), then the head in exact fp32
-    if ((rc = amds_layernorm(x, (long)S * Dp, w.norm_w, w.norm_b, cls, D, Bb, D, 1e-5f, AMDS_F32, stream)) != AMDS_OK) return rc;
+    RC(amds_layernorm(x, (long)S * Dp, w.norm_w, w.norm_b, cls, D, Bb, D, 1e-5f, AMDS_F32, stream));
     return amds_linear_f32(cls, w.head_w, w.head_b, logits, Bb, c.classes, D, 0, stream);
 }

@@ -13,17 +13,13 @@
 // GEMM runs on the kernel the longest bag's own call would pick when that is kernel 0 (then every shorter bag's call picks it too), and by shape otherwise --
 // a bag whose own call leaves kernel 0 shares a call bit-identically only when it is alone (amds_mil_vit_ragged_max_shared_tiles; the Python grouping sends it
 // alone).  n_bags == 1 is the per-bag call's shape exactly.
-#include "common.h"
+#include "model_call.h"
 
 namespace amds {
 
 namespace {
 
-inline int up(int n, int m) { return (n + m - 1) / m * m; }
-inline size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
-
-struct RaggedPlan {
-    int Fp, Dp, FFp, Ha, Da;
+struct RaggedPlan : PadDims {
     size_t a, x, h, qkv, att, u, xc, hc, qc, oc, cls, coords, table, total;
 };
 
@@ -31,44 +27,27 @@ int ragged_plan(const amds_mil_vit_cfg* c, int n, long total_tiles, int max_tile
     if (amds_mil_vit_workspace_bytes(c, 1, 1) == 0) return AMDS_ERR_INVALID;        // the config checks of amds_mil_vit_forward (message set there)
     AMDS_REQUIRE(n >= 0 && n <= 65535 && total_tiles >= 0 && max_tiles >= 0 && max_tiles < (1 << 30),
                  "amds_mil_vit_forward_ragged: bad shape n_bags=%d total_tiles=%ld max_tiles=%d", n, total_tiles, max_tiles);
-    p->Fp = up(c->n_feats, 256);
-    p->Dp = up(c->dim, 256);
-    p->FFp = up(c->ff, 256);
-    p->Ha = up(c->heads, 4);
-    p->Da = 64 * p->Ha;
+    static_cast<PadDims&>(*p) = pad_dims(c->n_feats, c->dim, c->ff, c->heads);
     const size_t M = (size_t)total_tiles + n, Mt = (size_t)total_tiles;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-    p->a = take(Mt * p->Fp * 2);                    // staged tiles, 16-bit, zero padded columns
-    p->x = take(M * p->Dp * 4);                     // residual stream fp32
-    p->h = take(M * p->Dp * 2);                     // LayerNorm output
-    p->qkv = take(M * 3 * p->Da * 2);
-    p->att = take(M * p->Da * 2);
-    p->u = take(M * p->FFp * 2);
-    p->xc = take((size_t)n * p->Dp * 4);            // class rows, compact: residual | LayerNorm output | query | attention output
-    p->hc = take((size_t)n * p->Dp * 2);
-    p->qc = take((size_t)n * p->Da * 2);
-    p->oc = take((size_t)n * p->Da * 2);
-    p->cls = take((size_t)n * c->dim * 4);
-    p->coords = take(M * 2 * 4);
-    p->table = take(varlen_table_bytes(n, total_tiles));
-    p->total = off;
+    Arena ar;
+    p->a = ar.take(Mt * p->Fp * 2);                    // staged tiles, 16-bit, zero padded columns
+    p->x = ar.take(M * p->Dp * 4);                     // residual stream fp32
+    p->h = ar.take(M * p->Dp * 2);                     // LayerNorm output
+    p->qkv = ar.take(M * 3 * p->Da * 2);
+    p->att = ar.take(M * p->Da * 2);
+    p->u = ar.take(M * p->FFp * 2);
+    p->xc = ar.take((size_t)n * p->Dp * 4);            // class rows, compact: residual | LayerNorm output | query | attention output
+    p->hc = ar.take((size_t)n * p->Dp * 2);
+    p->qc = ar.take((size_t)n * p->Da * 2);
+    p->oc = ar.take((size_t)n * p->Da * 2);
+    p->cls = ar.take((size_t)n * c->dim * 4);
+    p->coords = ar.take(M * 2 * 4);
+    p->table = ar.take(varlen_table_bytes(n, total_tiles));
+    p->total = ar.off;
     return AMDS_OK;
 }
 
 #define FA_SPAN_OK(T, H) ((long)(T) * 3 * (H) * 128 < (1L << 31))        // attention_flash.hip: one bag's q | k | v rows under one buffer descriptor
-
-// tiles [Mt][F] (fp32 / f16 / bf16) -> 16-bit operand rows [Mt][Fp], zero padded (mil_vit.hip's staging)
-template <typename TI, typename TO>
-__global__ void __launch_bounds__(256) stage_tiles_kernel(const TI* __restrict__ src, long ld_src, TO* __restrict__ dst, int Fp, long total, int F) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (; i < total; i += stride) {
-        const long r = i / Fp;
-        const int c = (int)(i - r * Fp);
-        dst[i] = c < F ? (TO)(float)src[r * ld_src + c] : (TO)0.f;
-    }
-}
 
 // the bag owning token row r: the last bag whose first row is <= r (rows of the table ascend for well-formed offsets; for others the search still ends in range)
 __device__ __forceinline__ int bag_of_row(const int2* __restrict__ bags, int n, long r) {
@@ -198,21 +177,7 @@ extern "C" int amds_mil_vit_forward_ragged(const amds_mil_vit_cfg* cfg_host, con
     // project_features (as mil_vit.hip)
     const void* a = feats;
     if (Mt > 0 && !(feats_dtype == dt && c.n_feats == p.Fp)) {
-        const long total = Mt * p.Fp;
-        const int grid = (int)min((long)8192, (total + 255) / 256);
-#define STAGE(TI, TO) hipLaunchKernelGGL((stage_tiles_kernel<TI, TO>), dim3(grid), dim3(256), 0, st, (const TI*)feats, (long)c.n_feats, (TO*)(base + p.a), \
-                                         p.Fp, total, c.n_feats)
-        if (dt == AMDS_F16) {
-            if (feats_dtype == AMDS_F32) STAGE(float, f16);
-            else if (feats_dtype == AMDS_F16) STAGE(f16, f16);
-            else STAGE(bf16, f16);
-        } else {
-            if (feats_dtype == AMDS_F32) STAGE(float, bf16);
-            else if (feats_dtype == AMDS_F16) STAGE(f16, bf16);
-            else STAGE(bf16, bf16);
-        }
-#undef STAGE
-        AMDS_LAUNCH_CHECK("stage_tiles_kernel");
+        if ((rc = stage_rows_dt(feats, feats_dtype, c.n_feats, base + p.a, dt, p.Fp, Mt, c.n_feats, stream)) != AMDS_OK) return rc;
         a = base + p.a;
     }
     float* proj = reinterpret_cast<float*>(qkv);
@@ -229,8 +194,7 @@ extern "C" int amds_mil_vit_forward_ragged(const amds_mil_vit_cfg* cfg_host, con
     bool tail_done = false;
     for (int l = 0; l < c.layers && rc == AMDS_OK; ++l) {
         const amds_mil_vit_layer& L = w.layers_host[l];
-        AMDS_REQUIRE(L.ln1_w && L.ln1_b && L.in_w && L.in_b && L.out_w && L.out_b && L.ln2_w && L.ln2_b && L.fc1_w && L.fc1_b && L.fc2_w && L.fc2_b &&
-                     (!c.alibi || L.head_scale), "amds_mil_vit_forward_ragged: incomplete weights of layer %d", l);
+        AMDS_REQUIRE(enc_layer_complete(L) && (!c.alibi || L.head_scale), "amds_mil_vit_forward_ragged: incomplete weights of layer %d", l);
         if ((rc = amds_layernorm(x, Dp, L.ln1_w, L.ln1_b, h, Dp, (int)M, D, 1e-5f, dt, stream)) != AMDS_OK) break;
         if (cls_tail && l == c.layers - 1) {
             // keys | values of every token; query, attention, output projection and MLP of the class rows alone, gathered into compact buffers

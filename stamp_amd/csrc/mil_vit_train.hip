@@ -11,22 +11,18 @@
 // Nothing is allocated and the host never waits for the device.
 #include <algorithm>
 #include <vector>
-#include "common.h"
+#include "model_call.h"
 
 namespace amds {
 namespace {
-
-inline int up(int n, int m) { return (n + m - 1) / m * m; }
-inline long upl(long n, long m) { return (n + m - 1) / m * m; }
-inline size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
 
 struct LayerOff {
     size_t h1, mu1, rs1, qkv, att, lse, u_al, osm, x_mid, h2, mu2, rs2, z, u;
 };
 
-struct Dims {
+struct Dims : PadDims {
     int F, D, H, FF, C, L, alibi;
-    int Fp, Dp, FFp, Ha, Da, S, Bb, Tn;
+    int S, Bb, Tn;
     long M, Mt;
     int dt;          // AMDS_BF16 or AMDS_F16: the type of every 16-bit tensor of the step (weights' operand copies, saved activations, 16-bit gradients)
 };
@@ -47,7 +43,7 @@ int make_dims(const amds_mil_vit_cfg* c, int Bb, int Tn, Dims* d) {
     d->dt = c->dtype;
     AMDS_REQUIRE(Bb > 0 && Tn > 0, "amds_mil_vit_train: bad shape bags=%d tiles=%d", Bb, Tn);
     d->F = c->n_feats; d->D = c->dim; d->H = c->heads; d->FF = c->ff; d->C = c->classes; d->L = c->layers; d->alibi = c->alibi != 0;
-    d->Fp = up(d->F, 256); d->Dp = up(d->D, 256); d->FFp = up(d->FF, 256); d->Ha = up(d->H, 4); d->Da = 64 * d->Ha;
+    static_cast<PadDims&>(*d) = pad_dims(d->F, d->D, d->FF, d->H);
     d->S = Tn + 1; d->Bb = Bb; d->Tn = Tn;
     d->M = (long)Bb * d->S; d->Mt = (long)Bb * Tn;
     AMDS_REQUIRE(d->M < (1L << 31) - 65536, "amds_mil_vit_train: %ld token rows do not fit the 32-bit row index", d->M);
@@ -55,30 +51,29 @@ int make_dims(const amds_mil_vit_cfg* c, int Bb, int Tn, Dims* d) {
 }
 
 void plan_saved(const Dims& d, SavedPlan* p) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    Arena ar;
     const size_t M = d.M, Mt = d.Mt;
-    p->a = take(Mt * d.Fp * 2);
-    p->zp = take(Mt * d.Dp * 2);
-    p->xp = take(Mt * d.Dp * 4);
-    p->cc = take(M * 2 * 4);
-    p->y = take(M * d.Dp * 4);
-    p->x_bytes = al(M * d.Dp * 4);
-    p->x0 = take(p->x_bytes * (d.L + 1));
+    p->a = ar.take(Mt * d.Fp * 2);
+    p->zp = ar.take(Mt * d.Dp * 2);
+    p->xp = ar.take(Mt * d.Dp * 4);
+    p->cc = ar.take(M * 2 * 4);
+    p->y = ar.take(M * d.Dp * 4);
+    p->x_bytes = align256(M * d.Dp * 4);
+    p->x0 = ar.take(p->x_bytes * (d.L + 1));
     p->layer.resize(d.L);
     for (int l = 0; l < d.L; ++l) {
         LayerOff& o = p->layer[l];
-        o.h1 = take(M * d.Dp * 2); o.mu1 = take(M * 4); o.rs1 = take(M * 4);
-        o.qkv = take(M * 3 * d.Da * 2); o.att = take(M * d.Da * 2); o.lse = take((size_t)d.Bb * d.Ha * d.S * 4);
-        o.u_al = d.alibi ? take(M * d.Da * 2) : 0; o.osm = d.alibi ? take(M * d.Da * 2) : 0;
-        o.x_mid = take(M * d.Dp * 4);
-        o.h2 = take(M * d.Dp * 2); o.mu2 = take(M * 4); o.rs2 = take(M * 4);
-        o.z = take(M * d.FFp * 2); o.u = take(M * d.FFp * 2);
+        o.h1 = ar.take(M * d.Dp * 2); o.mu1 = ar.take(M * 4); o.rs1 = ar.take(M * 4);
+        o.qkv = ar.take(M * 3 * d.Da * 2); o.att = ar.take(M * d.Da * 2); o.lse = ar.take((size_t)d.Bb * d.Ha * d.S * 4);
+        o.u_al = d.alibi ? ar.take(M * d.Da * 2) : 0; o.osm = d.alibi ? ar.take(M * d.Da * 2) : 0;
+        o.x_mid = ar.take(M * d.Dp * 4);
+        o.h2 = ar.take(M * d.Dp * 2); o.mu2 = ar.take(M * 4); o.rs2 = ar.take(M * 4);
+        o.z = ar.take(M * d.FFp * 2); o.u = ar.take(M * d.FFp * 2);
     }
-    p->clsn = take((size_t)d.Bb * d.D * 4);
-    p->muf = take((size_t)d.Bb * 4);
-    p->rsf = take((size_t)d.Bb * 4);
-    p->total = off;
+    p->clsn = ar.take((size_t)d.Bb * d.D * 4);
+    p->muf = ar.take((size_t)d.Bb * 4);
+    p->rsf = ar.take((size_t)d.Bb * 4);
+    p->total = ar.off;
 }
 
 struct WsPlan {
@@ -90,13 +85,13 @@ struct WsPlan {
 // `lean`: the plan of a backward that stops at the projection's output with no parameter gradients (amds_mil_vit_gradcam): the buffers only the weight
 // gradients, the column sums and the projection's own backward touch take no room.
 void plan_ws(const Dims& d, int split_k, WsPlan* p, bool lean = false) {
-    size_t off = 0;
-    auto take_always = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-    auto take = [&](size_t bytes) { return take_always(lean ? 0 : bytes); };
+    Arena ar;
+    auto take_always = [&](size_t bytes) { return ar.take(bytes); };
+    auto take = [&](size_t bytes) { return ar.take(lean ? 0 : bytes); };
     const size_t M = d.M, Mt = d.Mt;
     const long unit = 64L * split_k;
-    p->Mp = upl(d.M, unit);
-    p->Mtp = upl(d.Mt, unit);
+    p->Mp = round_up(d.M, unit);
+    p->Mtp = round_up(d.Mt, unit);
     const size_t Mpp = (size_t)(p->Mp > p->Mtp ? p->Mp : p->Mtp);
     const int wg = std::max(std::max(3 * d.Da, d.FFp), d.Dp);                       // widest gradient matrix that gets transposed
     const int wa = std::max(std::max(std::max(d.FFp, d.Dp), d.Da), d.Fp);           // widest activation matrix
@@ -125,8 +120,8 @@ void plan_ws(const Dims& d, int split_k, WsPlan* p, bool lean = false) {
     // and the chunk partials of every bias gradient, each in its own region
     {
         const size_t nblk = (M + 63) / 64, nch = (M + 1023) / 1024 + 1;
-        size_t b = (size_t)(2 * d.L + 1) * 2 * al(nblk * d.D * 4);
-        b += (size_t)d.L * (2 * al(nch * d.Dp * 4) + al(nch * d.FFp * 4) + al(nch * 3 * d.Da * 4) + al(nch * d.Ha * 4)) + al(nch * d.Dp * 4);
+        size_t b = (size_t)(2 * d.L + 1) * 2 * align256(nblk * d.D * 4);
+        b += (size_t)d.L * (2 * align256(nch * d.Dp * 4) + align256(nch * d.FFp * 4) + align256(nch * 3 * d.Da * 4) + align256(nch * d.Ha * 4)) + align256(nch * d.Dp * 4);
         p->sums_bytes = b + 4096;
         p->sums = take(p->sums_bytes);
     }
@@ -138,18 +133,7 @@ void plan_ws(const Dims& d, int split_k, WsPlan* p, bool lean = false) {
     p->dlt = take((size_t)d.Bb * d.C * 4);
     p->dxp = take(Mt * d.Dp * 4);
     p->dzp = take(Mt * d.Dp * 2);
-    p->total = off;
-}
-
-template <typename TI, typename TO>
-__global__ void __launch_bounds__(256) stage_bags_bf16_kernel(const TI* __restrict__ src, long ld_src, TO* __restrict__ dst, int Fp, long total, int F) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (; i < total; i += stride) {
-        const long r = i / Fp;
-        const int c = (int)(i - r * Fp);
-        dst[i] = c < F ? (TO)(float)src[r * ld_src + c] : (TO)0.f;
-    }
+    p->total = ar.off;
 }
 
 // x rows: class token in front of each bag's projected tiles; coords with the class token at (0, 0) (:347-351).  One block per row.
@@ -259,14 +243,6 @@ int cam_rowdot(const float* dx, const void* zp, const float* bias, float* out, c
     return AMDS_OK;
 }
 
-#define RC(call)                          \
-    do {                                  \
-        int rc__ = (call);                \
-        if (rc__ != AMDS_OK) return rc__; \
-    } while (0)
-
-constexpr int CFG_TRAIN = -2;      // amds_gemm_ex: by shape, ragged last row tile as its own small launch (M = bags x 1025 is never a multiple of 256)
-
 // the last block on its class rows alone (amds_mil_vit_dropout.cls_tail, else the context's amds_set_mil_cls_tail; with ALiBi the one-query kernel carries the
 // distance term: amds_attention_row_alibi_fwd_train).  The pitched rows (a class row every S rows) must fit the 32-bit buffer descriptors of the GEMMs AND of the token-major weight-gradient kernel, which spans
 // chunk + 63 rows of pitch S * width 16-bit elements per split (amds_wgrad_tn: chunk = 64 for Bb <= 64 split_k) -- a bag of 8192 tiles with dim_feedforward 2048 passes
@@ -276,10 +252,6 @@ bool cls_tail(const Dims& d, int want) {
     const long wide = std::max(std::max(d.FFp, 3 * d.Da), d.Dp);
     const long chunk = (d.Bb + 63) / 64 * 64;
     return on && d.L > 0 && d.S <= (d.alibi ? 16384 : 32768) && (long)(d.Bb + 1) * d.S * wide * 4 < (1L << 31) && (chunk + 63) * d.S * wide * 2 < (1L << 31);
-}
-
-int gemm_dt(int dt, const void* A, long lda, const void* W, long ldw, long M, int N, int K, int epi, void* out, long ldo, const float* bias, void* st) {
-    return amds_gemm_ex(CFG_TRAIN, A, lda, W, ldw, (int)M, N, K, dt, epi, out, ldo, bias, nullptr, nullptr, 0, 0, 0, 1.0f, st);
 }
 
 }  // namespace
@@ -326,7 +298,7 @@ extern "C" int amds_mil_vit_train_forward(const amds_mil_vit_cfg* cfg_host, cons
     char* sv = reinterpret_cast<char*>(saved);
     const int BF = d.dt;                                       // (the name dates from the bf16-only step)
     auto gemm = [&](const void* A, long lda, const void* W, long ldw, long Mr, int N, int K, int epi, void* out, long ldo, const float* bias, void* s2) -> int {
-        return gemm_dt(BF, A, lda, W, ldw, Mr, N, K, epi, out, ldo, bias, s2);
+        return gemm_train(BF, A, lda, W, ldw, Mr, N, K, epi, out, ldo, bias, s2);
     };
     const float p_proj = drop_host->p_proj, p_ff = drop_host->p_ff, p_att = d.alibi ? 0.f : drop_host->p_att;
     const uint64_t seed = drop_host->seed;
@@ -337,22 +309,7 @@ extern "C" int amds_mil_vit_train_forward(const amds_mil_vit_cfg* cfg_host, cons
     void* a = sv + sp.a;
     if (bags_dtype == AMDS_F16 && BF == AMDS_BF16 && Fp == d.F) RC(amds_convert_f16_bf16(bags, a, Mt * Fp, stream));
     else if (bags_dtype == BF && Fp == d.F) AMDS_HIP(hipMemcpyAsync(a, bags, (size_t)Mt * Fp * 2, hipMemcpyDeviceToDevice, st));       // already the operand type
-    else {
-        const long total = Mt * Fp;
-        const int grid = (int)std::min<long>(8192, (total + 255) / 256);
-#define AMDS_STAGE(TI, TO) hipLaunchKernelGGL((stage_bags_bf16_kernel<TI, TO>), dim3(grid), dim3(256), 0, st, (const TI*)bags, (long)d.F, (TO*)a, Fp, total, d.F)
-        if (BF == AMDS_BF16) {
-            if (bags_dtype == AMDS_F32) AMDS_STAGE(float, bf16);
-            else if (bags_dtype == AMDS_F16) AMDS_STAGE(f16, bf16);
-            else AMDS_STAGE(bf16, bf16);
-        } else {
-            if (bags_dtype == AMDS_F32) AMDS_STAGE(float, f16);
-            else if (bags_dtype == AMDS_F16) AMDS_STAGE(f16, f16);
-            else AMDS_STAGE(bf16, f16);
-        }
-#undef AMDS_STAGE
-        AMDS_LAUNCH_CHECK("stage_bags_bf16_kernel");
-    }
+    else RC(stage_rows_dt(bags, bags_dtype, d.F, a, BF, Fp, Mt, d.F, stream));
     void* zp = sv + sp.zp;
     float* xp = reinterpret_cast<float*>(sv + sp.xp);
     RC(gemm(a, Fp, w.proj_w, Fp, Mt, Dp, Fp, AMDS_EPI_BIAS, zp, Dp, w.proj_b, stream));
@@ -365,8 +322,7 @@ extern "C" int amds_mil_vit_train_forward(const amds_mil_vit_cfg* cfg_host, cons
     for (int l = 0; l < d.L; ++l) {
         const amds_mil_vit_layer& Lw = w.layers_host[l];
         const LayerOff& o = sp.layer[l];
-        AMDS_REQUIRE(Lw.ln1_w && Lw.ln1_b && Lw.in_w && Lw.in_b && Lw.out_w && Lw.out_b && Lw.ln2_w && Lw.ln2_b && Lw.fc1_w && Lw.fc1_b && Lw.fc2_w &&
-                     Lw.fc2_b && (!d.alibi || (Lw.bias_scale && Lw.inv_running_mean)), "amds_mil_vit_train_forward: incomplete weights of layer %d", l);
+        AMDS_REQUIRE(enc_layer_complete(Lw) && (!d.alibi || (Lw.bias_scale && Lw.inv_running_mean)), "amds_mil_vit_train_forward: incomplete weights of layer %d", l);
         float* x_in = reinterpret_cast<float*>(sv + sp.x0 + (size_t)l * sp.x_bytes);
         float* x_out = reinterpret_cast<float*>(sv + sp.x0 + (size_t)(l + 1) * sp.x_bytes);
         float* x_mid = reinterpret_cast<float*>(sv + o.x_mid);
@@ -463,7 +419,7 @@ static int mil_vit_backward_body(const amds_mil_vit_cfg* cfg_host, const amds_mi
     char* wk = reinterpret_cast<char*>(ws);
     const int BF = d.dt;
     auto gemm = [&](const void* A, long lda, const void* W, long ldw, long Mr, int N, int K, int epi, void* out, long ldo, const float* bias, void* s2) -> int {
-        return gemm_dt(BF, A, lda, W, ldw, Mr, N, K, epi, out, ldo, bias, s2);
+        return gemm_train(BF, A, lda, W, ldw, Mr, N, K, epi, out, ldo, bias, s2);
     };
     const float p_proj = drop_host->p_proj, p_ff = drop_host->p_ff, p_att = d.alibi ? 0.f : drop_host->p_att;
     const uint64_t seed = drop_host->seed;
@@ -490,7 +446,7 @@ static int mil_vit_backward_body(const amds_mil_vit_cfg* cfg_host, const amds_mi
         return amds_colsum_multi(sum_e, n, stream);
     };
     auto take_sums = [&](size_t bytes, int entries, float** out) -> int {          // a region that lives until the next flush; nullptr: does not fit at all
-        bytes = al(bytes);
+        bytes = align256(bytes);
         *out = nullptr;
         if (bytes > wp.sums_bytes) return AMDS_OK;
         if (sums_used + bytes > wp.sums_bytes || n_sum + entries > 32) RC(flush_sums());
@@ -530,9 +486,9 @@ static int mil_vit_backward_body(const amds_mil_vit_cfg* cfg_host, const amds_mi
         }
         if (defer_sums && nblk <= 2048) {
             float* pr;
-            RC(take_sums((size_t)2 * al((size_t)nblk * D * 4), 2, &pr));
+            RC(take_sums((size_t)2 * align256((size_t)nblk * D * 4), 2, &pr));
             if (pr) {
-                float* pb = reinterpret_cast<float*>(reinterpret_cast<char*>(pr) + al((size_t)nblk * D * 4));
+                float* pb = reinterpret_cast<float*>(reinterpret_cast<char*>(pr) + align256((size_t)nblk * D * 4));
                 RC(layernorm_bwd_partials_dt(dy, dys, x, xs, mu, rs, gamma, dxo, dxs, add_skip, pr, pb, (int)rows, D, dx16, ld16, BF, p, seed, sid, stream));
                 sum_e[n_sum++] = amds_colsum_entry{pr, dgamma, (long)D, (int)nblk, D, 0};
                 sum_e[n_sum++] = amds_colsum_entry{pb, dbeta, (long)D, (int)nblk, D, 0};
@@ -605,7 +561,7 @@ static int mil_vit_backward_body(const amds_mil_vit_cfg* cfg_host, const amds_mi
     for (int l = d.L - 1; l >= 0; --l) {
         const amds_mil_vit_layer& Lw = w.layers_host[l];
         const LayerOff& o = sp.layer[l];
-        AMDS_REQUIRE(Lw.in_wt && Lw.out_wt && Lw.fc1_wt && Lw.fc2_wt, "amds_mil_vit_train_backward: layer %d has no transposed weights (training pack)", l);
+        AMDS_REQUIRE(enc_layer_has_transposes(Lw), "amds_mil_vit_train_backward: layer %d has no transposed weights (training pack)", l);
         const amds_mil_vit_layer_grads* Gl = need_params ? &G->layers_host[l] : nullptr;
         AMDS_REQUIRE(!need_params || (Gl->ln1_w && Gl->ln1_b && Gl->in_w && Gl->in_b && Gl->out_w && Gl->out_b && Gl->ln2_w && Gl->ln2_b && Gl->fc1_w &&
                                       Gl->fc1_b && Gl->fc2_w && Gl->fc2_b && (!d.alibi || Gl->bias_scale)),
@@ -769,7 +725,7 @@ extern "C" int amds_mil_vit_train_backward(const amds_mil_vit_cfg* cfg_host, con
 // ---- amds_mil_vit_gradcam (include/amdstamp.h): |mean_f feats * d logit_c / d feats| per tile and class, no [tiles][n_feats] tensor ----------------------------
 namespace {
 constexpr int CAM_SPLIT_K = 1;          // (the lean plan holds no split-K buffers; the value only has to be valid)
-size_t cam_basis_bytes(const Dims& d) { return al((size_t)d.C * d.Bb * d.C * 4); }
+size_t cam_basis_bytes(const Dims& d) { return align256((size_t)d.C * d.Bb * d.C * 4); }
 }  // namespace
 
 extern "C" size_t amds_mil_vit_gradcam_workspace_bytes(const amds_mil_vit_cfg* cfg_host, int n_bags, int n_tiles) {

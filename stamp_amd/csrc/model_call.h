@@ -1,0 +1,52 @@
+// model_call.h -- host-only helpers shared by the "one C call" model entries (mil_vit*.hip, barspoon*.hip, ticon.hip, transmil_*.hip, nystrom_train.hip):
+// the padded operand layout of the MIL heads, the arena arithmetic of their plans, the status chain.  The launch sequences stay with the entries.
+#pragma once
+#include "launch.h"
+
+namespace amds {
+
+inline int round_up(int n, int m) { return (n + m - 1) / m * m; }
+inline long round_up(long n, long m) { return (n + m - 1) / m * m; }
+inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// offsets of a plan's regions in one caller-owned buffer: every region starts 256-byte aligned, `off` ends as the buffer's size
+struct Arena {
+    size_t off = 0;
+    size_t take(size_t bytes) { size_t o = off; off += align256(bytes); return o; }
+};
+
+// the first failing status leaves the entry; nothing is launched behind it
+#define RC(call)                          \
+    do {                                  \
+        int rc__ = (call);                \
+        if (rc__ != AMDS_OK) return rc__; \
+    } while (0)
+
+// The padded operand layout of the MIL heads (amds_mil_vit_layer): feature, model and feed-forward widths rounded up to 256 (the GEMMs' K / N tiles), heads
+// to 4 (amds_attention wants H % 4 == 0) of 64 channels each.  Bags are staged as zero-padded 16-bit rows of pitch Fp (stage_rows_dt, elementwise.hip);
+// LayerNorm writes the first D columns of its output only, so an entry with Dp != D zeroes that buffer once.
+struct PadDims { int Fp, Dp, FFp, Ha, Da; };
+inline PadDims pad_dims(int n_feats, int dim, int ff, int heads) {
+    PadDims p;
+    p.Fp = round_up(n_feats, 256);
+    p.Dp = round_up(dim, 256);
+    p.FFp = round_up(ff, 256);
+    p.Ha = round_up(heads, 4);
+    p.Da = 64 * p.Ha;
+    return p;
+}
+
+// the 12 pointers every user of an encoder layer needs; what only one caller needs (head_scale, bias_scale, inv_running_mean) stays with it
+inline bool enc_layer_complete(const amds_mil_vit_layer& L) {
+    return L.ln1_w && L.ln1_b && L.in_w && L.in_b && L.out_w && L.out_b && L.ln2_w && L.ln2_b && L.fc1_w && L.fc1_b && L.fc2_w && L.fc2_b;
+}
+// the transposed 16-bit matrices of a training pack (the backward's dx GEMMs)
+inline bool enc_layer_has_transposes(const amds_mil_vit_layer& L) { return L.in_wt && L.out_wt && L.fc1_wt && L.fc2_wt; }
+
+// A GEMM of a training step: amds_gemm_ex's kernel -2 = by shape, with a ragged last row tile as its own small launch (M = bags x 1025 token rows is
+// never a multiple of 256).
+inline int gemm_train(int dt, const void* A, long lda, const void* W, long ldw, long M, int N, int K, int epi, void* out, long ldo, const float* bias, void* st) {
+    return amds_gemm_ex(-2, A, lda, W, ldw, (int)M, N, K, dt, epi, out, ldo, bias, nullptr, nullptr, 0, 0, 0, 1.0f, st);
+}
+
+}  // namespace amds

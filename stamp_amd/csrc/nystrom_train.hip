@@ -15,12 +15,11 @@
 // Everything fp32 on the exact-fp32 MFMA (amds_bgemm_f32) and the kernels of transmil.hip / train.hip / dropout.hip: launch sequences,
 // nothing allocated, no host synchronisation.
 #include <algorithm>
-#include "common.h"
+#include "model_call.h"
 
 namespace amds {
 namespace {
 
-inline size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
 constexpr int HEADS = 8, ITERS = 6, CONV_K = 33;          // trans_mil.py:252-254, :52
 
 struct NyDims {
@@ -46,28 +45,27 @@ struct NySaved {
 };
 
 void ny_saved(const NyDims& p, NySaved* s) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    Arena ar;
     const size_t b = p.b, H = HEADS, np = p.np, m = p.m, d = p.d, Cd = p.Cd;
-    s->mm_bytes = al(b * H * m * m * 4);
-    s->yp = take(b * np * Cd * 4);
-    s->qkv = take(b * np * 3 * Cd * 4);
-    s->ql = take(b * H * m * d * 4);
-    s->kl = take(b * H * m * d * 4);
-    s->a1 = take(b * H * np * m * 4);
-    s->a2 = take(b * H * m * m * 4);
-    s->a3 = take(b * H * m * np * 4);
-    s->zs = take(s->mm_bytes * (ITERS + 1));          // z_0 .. z_6
-    s->A = take(s->mm_bytes * ITERS);
-    s->T1 = take(s->mm_bytes * ITERS);
-    s->T2 = take(s->mm_bytes * ITERS);
-    s->T3 = take(s->mm_bytes * ITERS);
-    s->av = take(b * H * m * d * 4);
-    s->a1z = take(b * H * np * m * 4);
-    s->merged = take(b * np * Cd * 4);
-    s->out = take(b * p.n * Cd * 4);                  // to_out's output before the dropout (forward scratch)
-    s->scratch = take(256);
-    s->total = off;
+    s->mm_bytes = align256(b * H * m * m * 4);
+    s->yp = ar.take(b * np * Cd * 4);
+    s->qkv = ar.take(b * np * 3 * Cd * 4);
+    s->ql = ar.take(b * H * m * d * 4);
+    s->kl = ar.take(b * H * m * d * 4);
+    s->a1 = ar.take(b * H * np * m * 4);
+    s->a2 = ar.take(b * H * m * m * 4);
+    s->a3 = ar.take(b * H * m * np * 4);
+    s->zs = ar.take(s->mm_bytes * (ITERS + 1));          // z_0 .. z_6
+    s->A = ar.take(s->mm_bytes * ITERS);
+    s->T1 = ar.take(s->mm_bytes * ITERS);
+    s->T2 = ar.take(s->mm_bytes * ITERS);
+    s->T3 = ar.take(s->mm_bytes * ITERS);
+    s->av = ar.take(b * H * m * d * 4);
+    s->a1z = ar.take(b * H * np * m * 4);
+    s->merged = ar.take(b * np * Cd * 4);
+    s->out = ar.take(b * p.n * Cd * 4);                  // to_out's output before the dropout (forward scratch)
+    s->scratch = ar.take(256);
+    s->total = ar.off;
 }
 
 struct NyWs {
@@ -76,30 +74,29 @@ struct NyWs {
 };
 
 void ny_ws(const NyDims& p, NyWs* w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    Arena ar;
     const size_t b = p.b, H = HEADS, np = p.np, m = p.m, d = p.d, Cd = p.Cd, mmb = b * H * m * m * 4;
-    w->dout = take(b * p.n * Cd * 4);
-    w->dmerged = take(b * np * Cd * 4);
-    w->dqkv = take(b * np * 3 * Cd * 4);
-    w->wflip = take(HEADS * CONV_K * 4);
-    w->da1z = take(b * H * np * m * 4);
-    w->dav = take(b * H * m * d * 4);
-    w->da1 = take(b * H * np * m * 4);
-    w->dzA = take(mmb); w->dzB = take(mmb);
-    w->da3 = take(b * H * m * np * 4);
-    w->da2 = take(mmb); w->dT3 = take(mmb); w->dA = take(mmb); w->dT2 = take(mmb);
+    w->dout = ar.take(b * p.n * Cd * 4);
+    w->dmerged = ar.take(b * np * Cd * 4);
+    w->dqkv = ar.take(b * np * 3 * Cd * 4);
+    w->wflip = ar.take(HEADS * CONV_K * 4);
+    w->da1z = ar.take(b * H * np * m * 4);
+    w->dav = ar.take(b * H * m * d * 4);
+    w->da1 = ar.take(b * H * np * m * 4);
+    w->dzA = ar.take(mmb); w->dzB = ar.take(mmb);
+    w->da3 = ar.take(b * H * m * np * 4);
+    w->da2 = ar.take(mmb); w->dT3 = ar.take(mmb); w->dA = ar.take(mmb); w->dT2 = ar.take(mmb);
     w->pinv_bytes = std::max<size_t>(amds_pinv_init_bwd_workspace_bytes((int)p.Z), 4);
-    w->pinv = take(w->pinv_bytes);
-    w->dkl = take(b * H * m * d * 4);
-    w->dql = take(b * H * m * d * 4);
-    w->dyp = take(b * np * Cd * 4);
-    w->part = take(b * (size_t)3 * Cd * Cd * 4);
+    w->pinv = ar.take(w->pinv_bytes);
+    w->dkl = ar.take(b * H * m * d * 4);
+    w->dql = ar.take(b * H * m * d * 4);
+    w->dyp = ar.take(b * np * Cd * 4);
+    w->part = ar.take(b * (size_t)3 * Cd * Cd * 4);
     w->cs_bytes = std::max<size_t>(std::max(amds_colsum_workspace_bytes(p.b, 3 * p.Cd * p.Cd), amds_colsum_workspace_bytes(p.b * p.n, p.Cd)), 4);
-    w->cs = take(w->cs_bytes);
+    w->cs = ar.take(w->cs_bytes);
     w->conv_bytes = std::max<size_t>(amds_dwconv_seq_wgrad_workspace_bytes(p.b, HEADS, CONV_K), 4);
-    w->conv = take(w->conv_bytes);
-    w->total = off;
+    w->conv = ar.take(w->conv_bytes);
+    w->total = ar.off;
 }
 
 // y [b][n][Cd] -> yp [b][pad + n][Cd], `pad` zero rows in FRONT of every bag (:100); and its inverse (rows dropped)
@@ -159,12 +156,6 @@ __global__ void __launch_bounds__(256) ny_dwconv_row_wgrad_kernel(const float* _
     __syncthreads();
     if (tid == 0) dw[(long)zi * taps + k] = (red[0] + red[1]) + (red[2] + red[3]);
 }
-
-#define RC(call)                          \
-    do {                                  \
-        int rc__ = (call);                \
-        if (rc__ != AMDS_OK) return rc__; \
-    } while (0)
 
 inline int bg(const float* A, int lda, long sAo, long sAi, const float* B, int ldb, long sBo, long sBi, int tflags, float* Cm, int ldc, long sCo, long sCi,
               int outer, int inner, int M, int N, int K, float alpha, float diag, const float* bias, int accumulate, void* st) {

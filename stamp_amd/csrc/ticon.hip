@@ -9,24 +9,21 @@
 // under the pre-softmax distance bias of `Attention.forward` :183-215.  The MIL `vit` head's recipe: fp32 residual stream, 16-bit MFMA GEMMs on zero-padded
 // weights (q | k | v stacked, heads padded to 64 channels), amds_attention_distbias for the attention, SWIGLU and RESIDUAL (LayerScale) epilogues.
 #include <algorithm>
-#include "launch.h"
+#include "model_call.h"
 
 namespace amds {
 namespace {
-inline size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
-
 struct TcPlan { size_t e, x, t, u, total; };
 
 int tc_plan(const amds_ticon_weights* w, int B, TcPlan* p) {
     AMDS_REQUIRE(w, "amds_ticon: null weights");
     AMDS_REQUIRE(w->in_dim > 0 && w->dim > 0 && w->dim % 4 == 0 && w->hidden > 0 && w->hidden % 2 == 0 && w->depth >= 0 && B >= 0, "amds_ticon: bad configuration");
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-    p->e = take((size_t)B * w->in_dim * 4);
-    p->x = take((size_t)B * w->dim * 4);
-    p->t = take((size_t)B * w->dim * 4);
-    p->u = take((size_t)B * std::max(w->hidden, w->dim) * 4);
-    p->total = off;
+    Arena ar;
+    p->e = ar.take((size_t)B * w->in_dim * 4);
+    p->x = ar.take((size_t)B * w->dim * 4);
+    p->t = ar.take((size_t)B * w->dim * 4);
+    p->u = ar.take((size_t)B * std::max(w->hidden, w->dim) * 4);
+    p->total = ar.off;
     return AMDS_OK;
 }
 
@@ -36,17 +33,9 @@ __global__ void __launch_bounds__(256) tc_f16_to_f32_kernel(const f16* __restric
     for (; i < n; i += stride) dst[i] = (float)src[i];
 }
 
-#define RC(call)                          \
-    do {                                  \
-        int rc__ = (call);                \
-        if (rc__ != AMDS_OK) return rc__; \
-    } while (0)
-
 // ---- slide mode -------------------------------------------------------------------------------------------------------------------------------------------
-inline int up(int n, int m) { return (n + m - 1) / m * m; }
-
 struct TsPlan {
-    int Fp, Dp, Ha, Da, Hp;
+    int Fp, Dp, Ha, Da, Hp;      // (the MLP's padded width is TICON's own Hp, not PadDims::FFp)
     size_t a, x, h, qkv, att, u, total;
 };
 
@@ -57,36 +46,21 @@ int ts_plan(const amds_ticon_slide_cfg* c, int B, int T, TsPlan* p) {
                  "amds_ticon_slide: needs dim %% heads == 0, head_dim <= 64, dim %% 4 == 0 and dim <= 8192 (dim=%d, heads=%d)", c->dim, c->heads);
     AMDS_REQUIRE(c->dtype == AMDS_F16 || c->dtype == AMDS_BF16, "amds_ticon_slide: operand dtype must be f16 or bf16");
     AMDS_REQUIRE(B >= 0 && B <= 65535 && T > 0, "amds_ticon_slide: bad shape slides=%d tiles=%d", B, T);
-    p->Fp = up(c->in_dim, 256);
-    p->Dp = up(c->dim, 256);
-    p->Ha = up(c->heads, 4);
-    p->Da = 64 * p->Ha;
-    p->Hp = up(c->hidden / 2, 128);
+    const PadDims pd = pad_dims(c->in_dim, c->dim, c->hidden, c->heads);
+    p->Fp = pd.Fp; p->Dp = pd.Dp; p->Ha = pd.Ha; p->Da = pd.Da;
+    p->Hp = round_up(c->hidden / 2, 128);
     AMDS_REQUIRE((long)T * 3 * p->Ha * 128 < (1L << 31), "amds_ticon_slide: %d tiles of %d heads: a slide's q | k | v rows must stay below 2 GB", T, p->Ha);
     const size_t M = (size_t)B * T;
     AMDS_REQUIRE(M < ((size_t)1 << 31), "amds_ticon_slide: %zu token rows do not fit the 32-bit row index", M);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-    p->a = take(M * p->Fp * 2);                     // staged embeddings, 16-bit, zero padded columns
-    p->x = take(M * p->Dp * 4);                     // residual stream fp32
-    p->h = take(M * p->Dp * 2);                     // LayerNorm output / the input projection's hidden
-    p->qkv = take(M * 3 * p->Da * 2);               // (first: fp32 scratch of the input projection, 6 Da >= 4 Dp bytes per row)
-    p->att = take(M * p->Da * 2);
-    p->u = take(M * p->Hp * 2);
-    p->total = off;
+    Arena ar;
+    p->a = ar.take(M * p->Fp * 2);                     // staged embeddings, 16-bit, zero padded columns
+    p->x = ar.take(M * p->Dp * 4);                     // residual stream fp32
+    p->h = ar.take(M * p->Dp * 2);                     // LayerNorm output / the input projection's hidden
+    p->qkv = ar.take(M * 3 * p->Da * 2);               // (first: fp32 scratch of the input projection, 6 Da >= 4 Dp bytes per row)
+    p->att = ar.take(M * p->Da * 2);
+    p->u = ar.take(M * p->Hp * 2);
+    p->total = ar.off;
     return AMDS_OK;
-}
-
-// emb [M][F] (fp32 / f16) -> 16-bit operand rows [M][Fp], zero padded
-template <typename TI, typename TO>
-__global__ void __launch_bounds__(256) ts_stage_kernel(const TI* __restrict__ src, int F, TO* __restrict__ dst, int Fp, long total) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (; i < total; i += stride) {
-        const long r = i / Fp;
-        const int c = (int)(i - r * Fp);
-        dst[i] = c < F ? (TO)(float)src[r * F + c] : (TO)0.f;
-    }
 }
 
 // the input projection's activation: fp32 fc1 rows -> silu -> 16-bit operand rows of fc2 (padding columns: silu(0) = 0)
@@ -210,14 +184,7 @@ extern "C" int amds_ticon_slide_forward(const amds_ticon_slide_cfg* cfg_host, co
     // the embeddings as 16-bit operand rows of pitch Fp (already in that form when dtype and pitch agree)
     const void* a = emb;
     if (staged) {
-        const long total = (long)M * p.Fp;
-        const dim3 grid((unsigned)std::min<long>(8192, (total + 255) / 256));
-        dispatch_16(dt, [&](auto t) {
-            typedef AMDS_TAG_T(t) TO;
-            if (emb_dtype == AMDS_F32) hipLaunchKernelGGL((ts_stage_kernel<float, TO>), grid, dim3(256), 0, st, (const float*)emb, c.in_dim, (TO*)(base + p.a), p.Fp, total);
-            else hipLaunchKernelGGL((ts_stage_kernel<f16, TO>), grid, dim3(256), 0, st, (const f16*)emb, c.in_dim, (TO*)(base + p.a), p.Fp, total);
-        });
-        AMDS_LAUNCH_CHECK("ts_stage_kernel");
+        RC(stage_rows_dt(emb, emb_dtype, c.in_dim, base + p.a, dt, p.Fp, M, c.in_dim, stream));
         a = base + p.a;
     }
     // input projection: Linear, SiLU, Linear, LayerNorm (:94-98); the two fp32 intermediates live in the qkv region

@@ -9,13 +9,12 @@
 // Everything is fp32 like the reference (the pseudo-inverse iteration is numerically touchy): matrix products on the exact-fp32 MFMA
 // (amds_bgemm_f32), the rest in the kernels of transmil.hip.  A plain sequence of launches on `stream` over one caller-owned workspace.
 #include <algorithm>
-#include "common.h"
+#include "model_call.h"
 #include <cstdlib>
 
 namespace amds {
 namespace {
 
-inline size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
 constexpr int HEADS = 8, ITERS = 6, CONV_K = 33;          // trans_mil.py:252-254 (heads = 8, pinv_iterations = 6), :52 (residual_conv_kernel = 33)
 
 struct TmPlan {
@@ -40,29 +39,28 @@ int tm_plan(const amds_transmil_cfg* c, int Bb, int T, TmPlan* p) {
     p->np = p->n + p->pad;
     p->l = (p->n + p->m - 1) / p->m;                                // l = ceil(n / m) (:113)
     const size_t b = Bb, H = HEADS, np = p->np, m = p->m, d = p->d, Cd = p->Cd;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-    p->hf = take(b * T * (size_t)c->n_feats * 4);
-    p->x = take(b * p->n * Cd * 4);
-    p->y = take(b * p->n * Cd * 4);
-    p->yp = take(b * np * Cd * 4);
-    p->qkv = take(b * np * 3 * Cd * 4);
-    p->ql = take(b * H * m * d * 4);
-    p->kl = take(b * H * m * d * 4);
-    p->a1 = take(b * H * np * m * 4);
-    p->a2 = take(b * H * m * m * 4);
-    p->a3 = take(b * H * m * np * 4);
-    p->z = take(b * H * m * m * 4);
-    p->z2 = take(b * H * m * m * 4);
-    p->xz = take(b * H * m * m * 4);
-    p->t1 = take(b * H * m * m * 4);
-    p->t2 = take(b * H * m * m * 4);
-    p->av = take(b * H * m * d * 4);
-    p->a1z = take(b * H * np * m * 4);
-    p->merged = take(b * np * Cd * 4);
-    p->scratch = take(256);
-    p->cls = take(b * Cd * 4);
-    p->total = off;
+    Arena ar;
+    p->hf = ar.take(b * T * (size_t)c->n_feats * 4);
+    p->x = ar.take(b * p->n * Cd * 4);
+    p->y = ar.take(b * p->n * Cd * 4);
+    p->yp = ar.take(b * np * Cd * 4);
+    p->qkv = ar.take(b * np * 3 * Cd * 4);
+    p->ql = ar.take(b * H * m * d * 4);
+    p->kl = ar.take(b * H * m * d * 4);
+    p->a1 = ar.take(b * H * np * m * 4);
+    p->a2 = ar.take(b * H * m * m * 4);
+    p->a3 = ar.take(b * H * m * np * 4);
+    p->z = ar.take(b * H * m * m * 4);
+    p->z2 = ar.take(b * H * m * m * 4);
+    p->xz = ar.take(b * H * m * m * 4);
+    p->t1 = ar.take(b * H * m * m * 4);
+    p->t2 = ar.take(b * H * m * m * 4);
+    p->av = ar.take(b * H * m * d * 4);
+    p->a1z = ar.take(b * H * np * m * 4);
+    p->merged = ar.take(b * np * Cd * 4);
+    p->scratch = ar.take(256);
+    p->cls = ar.take(b * Cd * 4);
+    p->total = ar.off;
     return AMDS_OK;
 }
 
@@ -98,12 +96,6 @@ __global__ void __launch_bounds__(128) front_pad_kernel(const float* __restrict_
         for (int c = threadIdx.x; c < Cd; c += 128) dst[c] = src[c];
     }
 }
-
-#define RC(call)                          \
-    do {                                  \
-        int rc__ = (call);                \
-        if (rc__ != AMDS_OK) return rc__; \
-    } while (0)
 
 int bg(const float* A, int lda, long sAo, long sAi, const float* B, int ldb, long sBo, long sBi, int transb, float* Cm, int ldc, long sCo, long sCi, int outer,
        int inner, int M, int N, int K, float alpha, float diag, const float* bias, int accumulate, void* st) {

@@ -14,12 +14,11 @@
 // wrap and after PPEG, then whatever to_out adds) and the LayerNorm outputs' pad rows are zeroed before to_qkv, which is what the reference's F.pad gives.
 #include <algorithm>
 #include <vector>
-#include "common.h"
+#include "model_call.h"
 
 namespace amds {
 namespace {
 
-inline size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
 constexpr int HEADS = 8, ITERS = 6, CONV_K = 33;          // trans_mil.py:252-254 (heads = 8, pinv_iterations = 6), :52 (residual_conv_kernel = 33)
 constexpr int FC1_ROWS = 128;                              // row tile of the bf16 x 3 product kernel: _fc1 runs as whole tiles + one zero-filled tail tile
 
@@ -87,36 +86,35 @@ int rg_plan(const amds_transmil_cfg* c, int n_bags, const int* tiles, RgPlan* p)
     for (const Bucket& k : p->buckets) max_bucket_rows = std::max(max_bucket_rows, (long)k.count * k.np);
     const size_t N = n_bags, H = HEADS, R = row, Cd = p->Cd, d = p->d, mm = (size_t)m * m, F = c->n_feats;
     const size_t fc1_rows = (size_t)((p->tiles + FC1_ROWS - 1) / FC1_ROWS) * FC1_ROWS;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-    p->hf = take((size_t)p->tiles * F * 4);                         // the bags as fp32 (fp16 / bf16 input)
-    p->tail = take((size_t)FC1_ROWS * F * 4);                       // _fc1's last, partial row tile, zero-filled
-    p->x = take(R * Cd * 4);                                        // per padded token row: x, y, yp, merged (4 x dim) + qkv (3 x dim) floats
-    p->y = take(R * Cd * 4);
-    p->yp = take(R * Cd * 4);
-    p->qkv = take(std::max(R * 3 * Cd, fc1_rows * Cd) * 4);         // (_fc1's output lives here before the first to_qkv)
-    p->merged = take(R * Cd * 4);
-    p->ql = take(N * H * m * d * 4);                                // landmark-sized: the whole call
-    p->kl = take(N * H * m * d * 4);
-    p->a2 = take(N * H * mm * 4);
-    p->z = take(N * H * mm * 4);
-    p->z2 = take(N * H * mm * 4);
-    p->xz = take(N * H * mm * 4);
-    p->t1 = take(N * H * mm * 4);
-    p->t2 = take(N * H * mm * 4);
-    p->av = take(N * H * m * d * 4);
-    p->a1 = take((size_t)max_bucket_rows * H * m * 4);              // token count x landmarks: the largest bucket, re-used bucket after bucket
-    p->a3 = take((size_t)max_bucket_rows * H * m * 4);
-    p->a1z = take((size_t)max_bucket_rows * H * m * 4);
-    p->scratch = take(N * 8);
-    p->qc = take(N * Cd * 4);                                       // the class-row tail of layer 2
-    p->a1c = take(N * H * m * 4);
-    p->a1zc = take(N * H * m * 4);
-    p->mc = take(N * Cd * 4);
-    p->xc = take(N * Cd * 4);
-    p->cls = take(N * Cd * 4);
-    p->lg = take(N * (size_t)c->classes * 4);
-    p->total = off;
+    Arena ar;
+    p->hf = ar.take((size_t)p->tiles * F * 4);                         // the bags as fp32 (fp16 / bf16 input)
+    p->tail = ar.take((size_t)FC1_ROWS * F * 4);                       // _fc1's last, partial row tile, zero-filled
+    p->x = ar.take(R * Cd * 4);                                        // per padded token row: x, y, yp, merged (4 x dim) + qkv (3 x dim) floats
+    p->y = ar.take(R * Cd * 4);
+    p->yp = ar.take(R * Cd * 4);
+    p->qkv = ar.take(std::max(R * 3 * Cd, fc1_rows * Cd) * 4);         // (_fc1's output lives here before the first to_qkv)
+    p->merged = ar.take(R * Cd * 4);
+    p->ql = ar.take(N * H * m * d * 4);                                // landmark-sized: the whole call
+    p->kl = ar.take(N * H * m * d * 4);
+    p->a2 = ar.take(N * H * mm * 4);
+    p->z = ar.take(N * H * mm * 4);
+    p->z2 = ar.take(N * H * mm * 4);
+    p->xz = ar.take(N * H * mm * 4);
+    p->t1 = ar.take(N * H * mm * 4);
+    p->t2 = ar.take(N * H * mm * 4);
+    p->av = ar.take(N * H * m * d * 4);
+    p->a1 = ar.take((size_t)max_bucket_rows * H * m * 4);              // token count x landmarks: the largest bucket, re-used bucket after bucket
+    p->a3 = ar.take((size_t)max_bucket_rows * H * m * 4);
+    p->a1z = ar.take((size_t)max_bucket_rows * H * m * 4);
+    p->scratch = ar.take(N * 8);
+    p->qc = ar.take(N * Cd * 4);                                       // the class-row tail of layer 2
+    p->a1c = ar.take(N * H * m * 4);
+    p->a1zc = ar.take(N * H * m * 4);
+    p->mc = ar.take(N * Cd * 4);
+    p->xc = ar.take(N * Cd * 4);
+    p->cls = ar.take(N * Cd * 4);
+    p->lg = ar.take(N * (size_t)c->classes * 4);
+    p->total = ar.off;
     return AMDS_OK;
 }
 
@@ -256,12 +254,6 @@ __global__ void __launch_bounds__(64) dwconv_cls_varlen_kernel(const float* __re
     }
     out[(long)slot * Cd + head * d + c] += s;
 }
-
-#define RC(call)                          \
-    do {                                  \
-        int rc__ = (call);                \
-        if (rc__ != AMDS_OK) return rc__; \
-    } while (0)
 
 int bg(const float* A, int lda, long sAo, long sAi, const float* B, int ldb, long sBo, long sBi, int transb, float* Cm, int ldc, long sCo, long sCi, int outer,
        int inner, int M, int N, int K, float alpha, float diag, const float* bias, int accumulate, void* st) {

@@ -6,12 +6,10 @@
 // the class rows, layer2, PPEG (weight gradients as tap correlations, data gradient = the same convolutions with flipped kernels), layer1, class token,
 // the wrap-padded tiles' gradients added onto the first tiles', ReLU, _fc1.  fp32 throughout; launch sequences over caller-owned arenas.
 #include <algorithm>
-#include "common.h"
+#include "model_call.h"
 
 namespace amds {
 namespace {
-inline size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
-
 struct TtDims { int F, Cd, C, Bb, T, side, n, add; };
 
 int tt_dims(const amds_transmil_cfg* c, int Bb, int T, TtDims* d) {
@@ -31,42 +29,40 @@ int tt_dims(const amds_transmil_cfg* c, int Bb, int T, TtDims* d) {
 struct TtSaved { size_t a, h, x1, mu1, rs1, ny1, xp, x2, mu2, rs2, ny2, xf, clsn, muf, rsf, y, total, ny_bytes; };
 
 int tt_saved(const TtDims& d, TtSaved* s) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    Arena ar;
     const size_t Mt = (size_t)d.Bb * d.T, M = (size_t)d.Bb * d.n, Cd = d.Cd;
     s->ny_bytes = amds_nystrom_attn_saved_bytes(d.Cd, d.Bb, d.n);
     if (s->ny_bytes == 0) return AMDS_ERR_INVALID;
-    s->a = take(Mt * d.F * 4); s->h = take(Mt * Cd * 4);
-    s->x1 = take(M * Cd * 4); s->mu1 = take(M * 4); s->rs1 = take(M * 4); s->ny1 = take(s->ny_bytes);
-    s->xp = take(M * Cd * 4); s->x2 = take(M * Cd * 4); s->mu2 = take(M * 4); s->rs2 = take(M * 4); s->ny2 = take(s->ny_bytes);
-    s->xf = take(M * Cd * 4); s->clsn = take((size_t)d.Bb * Cd * 4); s->muf = take((size_t)d.Bb * 4); s->rsf = take((size_t)d.Bb * 4);
-    s->y = take(M * Cd * 4);
-    s->total = off;
+    s->a = ar.take(Mt * d.F * 4); s->h = ar.take(Mt * Cd * 4);
+    s->x1 = ar.take(M * Cd * 4); s->mu1 = ar.take(M * 4); s->rs1 = ar.take(M * 4); s->ny1 = ar.take(s->ny_bytes);
+    s->xp = ar.take(M * Cd * 4); s->x2 = ar.take(M * Cd * 4); s->mu2 = ar.take(M * 4); s->rs2 = ar.take(M * 4); s->ny2 = ar.take(s->ny_bytes);
+    s->xf = ar.take(M * Cd * 4); s->clsn = ar.take((size_t)d.Bb * Cd * 4); s->muf = ar.take((size_t)d.Bb * 4); s->rsf = ar.take((size_t)d.Bb * 4);
+    s->y = ar.take(M * Cd * 4);
+    s->total = ar.off;
     return AMDS_OK;
 }
 
 struct TtWs { size_t dx, dx2, dy, dcls, dlt, dh, dzh, part, cs, lnb, pw, zb, wflip, ny, gsc, total, cs_bytes, lnb_bytes, pw_bytes, ny_bytes; };
 
 int tt_ws(const TtDims& d, TtWs* w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    Arena ar;
     const size_t Mt = (size_t)d.Bb * d.T, M = (size_t)d.Bb * d.n, Cd = d.Cd;
     w->ny_bytes = amds_nystrom_attn_workspace_bytes(d.Cd, d.Bb, d.n);
     if (w->ny_bytes == 0) return AMDS_ERR_INVALID;
-    w->dx = take(M * Cd * 4); w->dx2 = take(M * Cd * 4); w->dy = take(M * Cd * 4);
-    w->dcls = take((size_t)d.Bb * Cd * 4); w->dlt = take((size_t)d.Bb * d.C * 4);
-    w->dh = take(Mt * Cd * 4); w->dzh = take(Mt * Cd * 4);
-    w->part = take((size_t)d.Bb * Cd * d.F * 4);
+    w->dx = ar.take(M * Cd * 4); w->dx2 = ar.take(M * Cd * 4); w->dy = ar.take(M * Cd * 4);
+    w->dcls = ar.take((size_t)d.Bb * Cd * 4); w->dlt = ar.take((size_t)d.Bb * d.C * 4);
+    w->dh = ar.take(Mt * Cd * 4); w->dzh = ar.take(Mt * Cd * 4);
+    w->part = ar.take((size_t)d.Bb * Cd * d.F * 4);
     size_t cs = amds_colsum_workspace_bytes(d.Bb, d.Cd * d.F);
     cs = std::max(cs, amds_colsum_workspace_bytes((int)Mt, d.Cd));
     cs = std::max(cs, amds_colsum_workspace_bytes(d.Bb, std::max(d.Cd, d.C)));
-    w->cs_bytes = std::max<size_t>(cs, 4); w->cs = take(w->cs_bytes);
-    w->lnb_bytes = std::max<size_t>(amds_layernorm_bwd_workspace_bytes((int)M, d.Cd), 4); w->lnb = take(w->lnb_bytes);
-    w->pw_bytes = std::max<size_t>(amds_ppeg_wgrad_workspace_bytes(d.Bb, d.Cd), 4); w->pw = take(w->pw_bytes);
-    w->zb = take(Cd * 4); w->wflip = take(Cd * (49 + 25 + 9) * 4);
-    w->ny = take(w->ny_bytes);
-    w->gsc = take((size_t)(2 * Cd + 50 * Cd) * 4);
-    w->total = off;
+    w->cs_bytes = std::max<size_t>(cs, 4); w->cs = ar.take(w->cs_bytes);
+    w->lnb_bytes = std::max<size_t>(amds_layernorm_bwd_workspace_bytes((int)M, d.Cd), 4); w->lnb = ar.take(w->lnb_bytes);
+    w->pw_bytes = std::max<size_t>(amds_ppeg_wgrad_workspace_bytes(d.Bb, d.Cd), 4); w->pw = ar.take(w->pw_bytes);
+    w->zb = ar.take(Cd * 4); w->wflip = ar.take(Cd * (49 + 25 + 9) * 4);
+    w->ny = ar.take(w->ny_bytes);
+    w->gsc = ar.take((size_t)(2 * Cd + 50 * Cd) * 4);
+    w->total = ar.off;
     return AMDS_OK;
 }
 
@@ -111,11 +107,6 @@ __global__ void tt_transpose_small_kernel(const float* __restrict__ src, float* 
     }
 }
 
-#define RC(call)                          \
-    do {                                  \
-        int rc__ = (call);                \
-        if (rc__ != AMDS_OK) return rc__; \
-    } while (0)
 }  // namespace
 }  // namespace amds
 
