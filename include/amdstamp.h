@@ -912,6 +912,14 @@ int amds_attention_row_varlen(const void* q, long ldq, const void* qkv, const in
 /* ws: contents on entry are ignored (the call initialises every byte it reads);
  *     nothing outside [ws, ws + amds_attention_varlen_workspace_bytes) is written. */
 
+/* The same attention for a layout WITHOUT a class token (the barspoon head's encoder): bag i owns rows offsets[i] .. offsets[i+1] - 1 of qkv [total_rows][3 H 64]
+ * and out [total_rows][H 64] (Tn_i = len_i), max_rows >= every len_i, max_rows * 3 * H * 128 < 2^31.  Under each bag's slice the result equals
+ * amds_attention(qkv_slice, ..., B = 1, T = len_i, ...) bit for bit.  Workspace: amds_attention_varlen_workspace_bytes(n_bags, total_rows). */
+int amds_attention_varlen_rows(const void* qkv, const int* offsets, void* out, int n_bags, long total_rows, int max_rows, int H, int dtype, void* ws,
+                               size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_attention_varlen_workspace_bytes) is written. */
+
 /* The TRAINING step of the same head, forward and backward as one call each (reference: the train-mode forward of
  * vision_tranformer.py:332-384 with its Dropout sites :157-169, :191, :314-318 live, and loss.backward() through it,
  * src/stamp/modeling/models/__init__.py:239-279).  cfg.dtype = AMDS_BF16 or AMDS_F16: the type of EVERY 16-bit tensor of the step (operand copies of the
@@ -1040,6 +1048,31 @@ int amds_barspoon_forward(const amds_barspoon_cfg* cfg_host, const amds_barspoon
                           const float* positions, float* logits, int n_bags, int n_tiles, void* ws, size_t ws_bytes, void* stream);
 /* ws: contents on entry are ignored (the call initialises every byte it reads);
  *     nothing outside [ws, ws + amds_barspoon_workspace_bytes) is written. */
+
+/* ---- ragged bags: the same deploy / validation forward over bags of DIFFERENT lengths packed without padding, one call ---------------------------------------
+ * The reference validates and deploys barspoon at one full bag per batch (src/stamp/modeling/train.py:467-477; barspoon.py:327-344).  Layout (as the MIL `vit`
+ * head's ragged call, without a class token among the tile rows): `offsets` is a DEVICE int32 array [n_bags + 1]; bag i owns rows offsets[i] .. offsets[i+1] - 1
+ * of the packed feats [total_tiles][n_feats] (AMDS_F32 / F16 / BF16) and positions fp32 [total_tiles][2] (required when cfg.positional_encoding); every len_i >= 1,
+ * max_tiles >= every len_i.  logits fp32 [n_bags][sum_t n_out_t] as amds_barspoon_forward.  The library cannot read `offsets` without a host synchronisation:
+ * the kernels clamp them (offsets to [0, total_tiles], lengths to [0, max_tiles]) so that a malformed array cannot address outside the buffers -- its results are
+ * then undefined; callers validate on the host (stamp_amd.mil_core.pack_bags).  Limits: n_bags <= 65535 and n_bags * dec_heads <= 65535 (one batched fp32
+ * product over (bag, head)); total_tiles fits the 32-bit row index as in the dense call; a bag's q | k | v rows stay below the 2 GB of a buffer descriptor,
+ * max_tiles * 3 * Ha * 128 < 2^31 (Ha = enc_heads rounded up to 4; AMDS_ERR_INVALID otherwise).  n_bags == 0 returns AMDS_OK and launches nothing.  Launches
+ * only, on `stream`; ws 256-byte aligned.  Inference only (eval mode).
+ *
+ * Bag i's logits row equals amds_barspoon_forward on that bag alone (n_bags = 1, n_tiles = len_i), bit for bit, when the bag has at most
+ * amds_barspoon_ragged_max_shared_tiles(cfg) tiles or is the call's only bag: each 16-bit GEMM runs on the kernel of the longest bag's own call when that is the
+ * small-problem kernel and by shape otherwise (the default dispatch picks by M, amds_gemm_ex); the exact-fp32 products of the class tokens run with the bag as
+ * their batch dimension, i.e. through the one-bag call's dispatch; attention and cross-attention are the fixed-pitch kernels' arithmetic per bag. */
+size_t amds_barspoon_ragged_workspace_bytes(const amds_barspoon_cfg* cfg_host, int n_bags, long total_tiles, int max_tiles);
+int amds_barspoon_forward_ragged(const amds_barspoon_cfg* cfg_host, const amds_barspoon_weights* w_host, const void* feats, int feats_dtype,
+                                 const float* positions, const int* offsets, float* logits, int n_bags, long total_tiles, int max_tiles, void* ws, size_t ws_bytes,
+                                 void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_barspoon_ragged_workspace_bytes) is written. */
+/* The largest tile count a bag may have and still share a ragged call with other bags bit-identically, over the head's GEMM shapes (T, Dp, Fp), (T, 3 Da, Dp),
+ * (T, Dp, Da), (T, FFp, Dp), (T, Dp, FFp), (T, 2 Db, Dp); 2^30 - 1 when no size leaves the small-problem kernel; -1 on a bad cfg.  Host-side, no launch. */
+int amds_barspoon_ragged_max_shared_tiles(const amds_barspoon_cfg* cfg_host);
 
 /* ---- the TRAINING step of the barspoon head, forward and backward as one call each -----------------------------------------------------------------------
  * Reference: the train-mode forward of barspoon.py:164-205 -- torch's pre-norm containers with their documented `norm_first=True` dropout sites live

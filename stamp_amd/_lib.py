@@ -295,10 +295,14 @@ PROTOTYPES = {
     "amds_mil_vit_ragged_max_shared_tiles": (_i, [_vp]),
     "amds_attention_varlen_workspace_bytes": (_sz, [_i, _l]),
     "amds_attention_varlen": (_i, [_vp, _vp, _vp, _i, _l, _i, _i, _i, _vp, _sz, _vp]),
+    "amds_attention_varlen_rows": (_i, [_vp, _vp, _vp, _i, _l, _i, _i, _i, _vp, _sz, _vp]),
     "amds_attention_alibi_varlen": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _l, _i, _i, _i, _vp, _sz, _vp]),
     "amds_attention_row_varlen": (_i, [_vp, _l, _vp, _vp, _vp, _l, _i, _l, _i, _i, _i, _vp, _sz, _vp]),
     "amds_barspoon_workspace_bytes": (_sz, [_vp, _i, _i]),
     "amds_barspoon_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "amds_barspoon_ragged_workspace_bytes": (_sz, [_vp, _i, _l, _i]),
+    "amds_barspoon_forward_ragged": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _l, _i, _vp, _sz, _vp]),
+    "amds_barspoon_ragged_max_shared_tiles": (_i, [_vp]),
     "amds_barspoon_train_saved_bytes": (_sz, [_vp, _i, _i]),
     "amds_barspoon_train_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "amds_barspoon_train_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),

@@ -9,6 +9,8 @@ tokens in exact fp32.  `forward` is eval + no-grad only (a forward that needs gr
 `LitMilClassificationMixin.step`, :263-321) goes through `forward_train`: one torch.autograd.Function whose forward and backward are
 `amds_barspoon_train_forward` / `amds_barspoon_train_backward` (csrc/barspoon_train.hip), `.grad` of every nn.Parameter in the reference's shapes.
 `stamp_amd.barspoon_train.HipBarspoonTrainer` drives it with the reference's loss and optimiser.
+`forward_ragged(bags, positions)` is the same deploy forward over bags of DIFFERENT lengths packed without padding (`amds_barspoon_forward_ragged`,
+csrc/barspoon_ragged.hip): one call per group of bags, each bag's logits bit-identical to its own `forward` call.
 """
 from __future__ import annotations
 
@@ -156,11 +158,66 @@ class EncDecTransformer(nn.Module):
         logits = torch.empty(Bb, total, dtype=torch.float32, device=dev)
         _lib.check(lib.amds_barspoon_forward(C.byref(cfg), C.byref(wc), x.data_ptr(), ops._DT[x.dtype], pos.data_ptr() if pos is not None else None,
                                              logits.data_ptr(), Bb, T, ws.data_ptr(), ws.numel(), ops._stream()), "barspoon_forward")
+        return self._split_targets(logits, no)
+
+    # ---- ragged inference forward: N bags of different lengths, no padding, one call per group -----------------------------------------------
+    def max_shared_tiles(self, device) -> int:
+        """Longest bag that shares a ragged call with others and keeps its own call's bits (amds_barspoon_ragged_max_shared_tiles); a longer bag runs alone."""
+        n = int(_lib.lib().amds_barspoon_ragged_max_shared_tiles(C.byref(self._pack(torch.device(device)).cfg)))
+        if n < 0:
+            _lib.check(-1, "barspoon_ragged_max_shared_tiles")
+        return n
+
+    def _split_targets(self, logits: torch.Tensor, no) -> dict[str, torch.Tensor]:
         out, col = {}, 0
         for j, t in enumerate(self.target_labels):
             out[t] = logits[:, col:col + no[j]]
             col += no[j]
         return out
+
+    def forward_ragged(self, bags, positions=None, *, bags_per_call: int | None = None, max_rows_per_call: int = 1 << 62) -> dict[str, torch.Tensor]:
+        """Bags of DIFFERENT lengths without padding: lists of [T_i, d_features] (and [T_i, 2] positions) tensors -> `{target: logits [N, n_out]}` in the
+        list's order, bag i's rows bit-identical to `forward(bags[i][None], positions[i][None])`.  Validated and grouped on the host (`mil_core.group_bags`
+        with extra_rows=0: at most `bags_per_call` bags and `max_rows_per_call` tile rows per call, a bag longer than `max_shared_tiles` runs alone), ONE
+        library call per group (amds_barspoon_forward_ragged, csrc/barspoon_ragged.hip).  Inference only: eval mode under torch.no_grad() /
+        inference_mode()."""
+        from . import mil_core
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError("forward_ragged is the inference forward: call it in eval mode (.eval()) under torch.no_grad() or torch.inference_mode()")
+        bags = list(bags)
+        pl = list(positions) if positions is not None else None
+        if pl is not None and not self.positional_encoding:
+            pl = None                                                # `forward` ignores them too
+        try:
+            lengths = mil_core._validate_bags(bags, pl, self.d_features, False)
+        except ValueError as e:
+            raise ValueError(str(e).replace("coords", "positions")) from None
+        if self.positional_encoding and bags and pl is None:
+            raise ValueError("positional_encoding=True needs the tile positions of every bag")
+        if bags and not all(b.is_cuda for b in bags):
+            raise RuntimeError("HIP barspoon needs bags on the GPU (no CPU fallback)")
+        dev = bags[0].device if bags else next(self.parameters()).device
+        if not bags:
+            return {t: torch.empty(0, n, dtype=torch.float32, device=dev) for t, n in self.target_n_outs.items()}
+        pack = self._pack(dev)
+        cfg, wc = pack.cfg, pack.wc
+        lib = _lib.lib()
+        # one fp32 product of the call is batched over (bag, decoder head): 65535 batches
+        per_call = min(bags_per_call or len(bags), 65535 // self.num_decoder_heads)
+        outs = []
+        for a, e in mil_core.group_bags(lengths, per_call, max_rows_per_call, self.max_shared_tiles(dev), extra_rows=0):
+            rb = mil_core.pack_bags(bags[a:e], None if pl is None else pl[a:e], n_feats=self.d_features, device=dev)
+            n, total, mx = rb.n_bags, rb.total_tiles, rb.max_tiles
+            need = lib.amds_barspoon_ragged_workspace_bytes(C.byref(cfg), n, total, mx)
+            if need == 0:
+                _lib.check(-1, "barspoon_ragged_workspace_bytes")
+            ws = ops.scratch("barspoon_ragged", dev, need)
+            logits = torch.empty(n, pack.total_out, dtype=torch.float32, device=dev)
+            _lib.check(lib.amds_barspoon_forward_ragged(C.byref(cfg), C.byref(wc), rb.feats.data_ptr(), ops._DT[rb.feats.dtype],
+                                                        rb.coords.data_ptr() if rb.coords is not None else None, rb.offsets.data_ptr(), logits.data_ptr(), n,
+                                                        total, mx, ws.data_ptr(), ws.numel(), ops._stream()), "barspoon_forward_ragged")
+            outs.append(logits)
+        return self._split_targets(outs[0] if len(outs) == 1 else torch.cat(outs, dim=0), pack.no)
 
     # ---- training (the reference's `LitMilClassificationMixin.step`, barspoon.py:263-321) -------------------------------------------------
     def forward_train(self, tile_tokens: torch.Tensor, tile_positions: torch.Tensor, *, seed: int | None = None,

@@ -3,7 +3,8 @@
 `HipBarspoonTrainer` is the reference's `LitMilClassificationMixin` (src/stamp/modeling/models/barspoon.py:211-348) without Lightning: one
 `step` = `EncDecTransformer.forward_train` (ONE library call forward, ONE backward; csrc/barspoon_train.hip), the reference's loss
 (:285-292: the sum over the targets of `F.cross_entropy(logits, float one-hot, weight=)`, in torch like the other heads' losses), and
-`torch.optim.Adam(lr)` (:346-348) over the module's own parameters.  `predict` is the deploy forward (`EncDecTransformer.forward` in eval mode).
+`torch.optim.Adam(lr)` (:346-348) over the module's own parameters.  `predict` is the deploy forward (`EncDecTransformer.forward` in eval mode),
+`predict_ragged` the same over bags of different lengths in one call (`forward_ragged`).
 `fit` is the epoch loop of the reference's `train_model_` (src/stamp/modeling/train.py:504-564): validation loss after every epoch, early stopping
 on it (mode min), the best epoch's weights restored.  There is no CPU fallback: CPU tensors raise.
 """
@@ -68,10 +69,62 @@ class HipBarspoonTrainer:
         finally:
             self.model.train(was)
 
-    def fit(self, train_batches, valid_batches, *, max_epochs: int, patience: int = 16, weights=None, log=None) -> dict:
+    @torch.no_grad()
+    def predict_ragged(self, bags, positions, *, bags_per_call: int | None = None, max_rows_per_call: int = 1 << 62) -> dict[str, torch.Tensor]:
+        """The eval forward on the current weights over bags of DIFFERENT lengths (`EncDecTransformer.forward_ragged`): lists of [T_i, d_features] and
+        [T_i, 2] tensors -> `{target: logits [N, n_out]}`, bag i's rows bit-identical to `predict(bags[i][None], positions[i][None])`."""
+        bags = list(bags)
+        for b in bags:
+            self._check(b)
+        was = self.model.training
+        self.model.eval()
+        try:
+            return self.model.forward_ragged(bags, positions, bags_per_call=bags_per_call, max_rows_per_call=max_rows_per_call)
+        finally:
+            self.model.train(was)
+
+    def _validation_sum(self, valid_batches, weights, bags_per_call: int, max_rows_per_call: int) -> tuple[float, int]:
+        """Sum over the validation batches of loss * batch size, and the bag count.  bags_per_call > 1: consecutive one-bag batches share ragged calls;
+        each bag's loss is formed from its own logits row and the host reads once per group -- the same values added in the same order as the loop's."""
+        dev = self.dev
+        vtot, vcnt = 0.0, 0
+        pend: list = []
+
+        def flush():
+            nonlocal vtot, vcnt
+            if not pend:
+                return
+            pos = None if pend[0][1] is None else [p for _, p, _ in pend]
+            lg = self.predict_ragged([b for b, _, _ in pend], pos, bags_per_call=bags_per_call, max_rows_per_call=max_rows_per_call)
+            losses = torch.stack([multi_target_loss({t: v[i:i + 1] for t, v in lg.items()}, pend[i][2], weights) for i in range(len(pend))])
+            for v in losses.tolist():           # one device-to-host read
+                vtot += v
+            vcnt += len(pend)
+            pend.clear()
+
+        for feats, positions, targets in valid_batches():
+            if bags_per_call > 1 and feats.shape[0] == 1:
+                if pend and (pend[0][1] is None) != (positions is None):
+                    flush()
+                pend.append((feats[0].to(dev), None if positions is None else positions[0].to(dev), targets))
+                if len(pend) >= bags_per_call:
+                    flush()
+                continue
+            flush()
+            lg = self.predict(feats.to(dev), None if positions is None else positions.to(dev))
+            vtot += float(multi_target_loss(lg, targets, weights)) * feats.shape[0]
+            vcnt += feats.shape[0]
+        flush()
+        return vtot, vcnt
+
+    def fit(self, train_batches, valid_batches, *, max_epochs: int, patience: int = 16, weights=None, log=None, valid_bags_per_call: int = 1,
+            valid_max_rows_per_call: int = 262144) -> dict:
         """train_batches / valid_batches: callables returning an iterable of (feats, positions, targets) per epoch.  Validation loss (eval forward,
         Lightning's mean over batches weighted by batch size) after every epoch; stops when it has not improved for `patience` epochs; the best epoch's
-        weights are restored.  Returns the history."""
+        weights are restored.  valid_bags_per_call > 1: one-bag validation batches share ragged calls of at most that many bags and
+        `valid_max_rows_per_call` tile rows (`predict_ragged`), with the losses of the one-bag loop.  Returns the history."""
+        if valid_bags_per_call < 1 or valid_max_rows_per_call < 1:
+            raise ValueError("valid_bags_per_call and valid_max_rows_per_call must be >= 1")
         dev = self.dev
         best = {"loss": float("inf"), "epoch": -1, "state": None}
         hist = {"train_loss": [], "validation_loss": [], "best_epoch": -1, "stopped_epoch": None}
@@ -83,11 +136,7 @@ class HipBarspoonTrainer:
                 tot += float(loss) * feats.shape[0]
                 cnt += feats.shape[0]
             hist["train_loss"].append(tot / max(cnt, 1))
-            vtot, vcnt = 0.0, 0
-            for feats, positions, targets in valid_batches():
-                lg = self.predict(feats.to(dev), None if positions is None else positions.to(dev))
-                vtot += float(multi_target_loss(lg, targets, weights)) * feats.shape[0]
-                vcnt += feats.shape[0]
+            vtot, vcnt = self._validation_sum(valid_batches, weights, valid_bags_per_call, valid_max_rows_per_call)
             vloss = vtot / max(vcnt, 1)
             hist["validation_loss"].append(vloss)
             if log:

@@ -692,11 +692,12 @@ __global__ void __launch_bounds__(256) attn_row_alibi_bwd_kernel(const T* __rest
 
 // ---- ragged bags: the per-call table of the VARLEN kernels ---------------------------------------------------------------------------------------------------
 // One workgroup: bag i = tiles offsets[i] .. offsets[i+1] - 1, clamped so that a malformed array cannot address outside the buffers (offsets to [0, total],
-// lengths to [0, max_tiles]); its Tn = len + 1 token rows (class token first) start at row offsets[i] + i < total + n_bags.  Then the flattened (bag, q block)
-// list: an exclusive scan of the per-bag block counts (256 thread chunks + an LDS scan), each thread writes its bags' items, the slack up to `nwork` gets
+// lengths to [0, max_tiles]); its Tn = len + extra_rows token rows start at row offsets[i] + i * extra_rows < total + n_bags * extra_rows.  extra_rows = 1: a
+// class token in front of every bag (the MIL `vit` head); 0: the tile rows alone (barspoon's encoder; an empty bag then has no work item).  Then the flattened
+// (bag, q block) list: an exclusive scan of the per-bag block counts (256 thread chunks + an LDS scan), each thread writes its bags' items, the slack up to `nwork` gets
 // Tn = 0.  Items past `nwork` (only possible for overlapping, malformed offsets) are dropped.
-__global__ void __launch_bounds__(256) varlen_plan_kernel(const int* __restrict__ offsets, int n, long total, int max_tiles, int2* __restrict__ bags,
-                                                          int4* __restrict__ work, long nwork) {
+__global__ void __launch_bounds__(256) varlen_plan_kernel(const int* __restrict__ offsets, int n, long total, int max_tiles, int extra_rows,
+                                                          int2* __restrict__ bags, int4* __restrict__ work, long nwork) {
     __shared__ long ssum[256];
     const int tid = threadIdx.x;
     const int per = (n + 255) / 256;
@@ -704,7 +705,7 @@ __global__ void __launch_bounds__(256) varlen_plan_kernel(const int* __restrict_
     auto bag = [&](int i) {
         const long a = min(max((long)offsets[i], 0L), total), e = min(max((long)offsets[i + 1], 0L), total);
         const long len = min(max(e - a, 0L), (long)max_tiles);
-        return make_int2((int)(a + i), (int)(len + 1));
+        return make_int2((int)(a + (long)i * extra_rows), (int)(len + extra_rows));
     };
     long acc = 0;
     for (int i = i0; i < i1; ++i) {
@@ -734,14 +735,14 @@ namespace {
 inline size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
 }  // namespace
 
-// sum over bags of ceil((len + 1) / 128) <= (total + n + 127 n) / 128
+// sum over bags of ceil((len + 1) / 128) <= (total + n + 127 n) / 128; without the class-token row (extra_rows = 0) the sum is no larger
 long varlen_work_items(int n_bags, long total_tiles) { return (total_tiles + 128L * n_bags) / 128 + 1; }
 size_t varlen_table_bytes(int n_bags, long total_tiles) { return al256((size_t)n_bags * 8) + al256((size_t)varlen_work_items(n_bags, total_tiles) * 16); }
 const int2* varlen_table_bags(const void* table) { return reinterpret_cast<const int2*>(table); }
 
-int varlen_table_build(const int* offsets, int n_bags, long total_tiles, int max_tiles, void* table, hipStream_t st) {
+int varlen_table_build(const int* offsets, int n_bags, long total_tiles, int max_tiles, int extra_rows, void* table, hipStream_t st) {
     char* t = reinterpret_cast<char*>(table);
-    hipLaunchKernelGGL(varlen_plan_kernel, dim3(1), dim3(256), 0, st, offsets, n_bags, total_tiles, max_tiles, reinterpret_cast<int2*>(t),
+    hipLaunchKernelGGL(varlen_plan_kernel, dim3(1), dim3(256), 0, st, offsets, n_bags, total_tiles, max_tiles, extra_rows, reinterpret_cast<int2*>(t),
                        reinterpret_cast<int4*>(t + al256((size_t)n_bags * 8)), varlen_work_items(n_bags, total_tiles));
     AMDS_LAUNCH_CHECK("varlen_plan_kernel");
     return AMDS_OK;
@@ -1027,10 +1028,10 @@ extern "C" size_t amds_attention_varlen_workspace_bytes(int n_bags, long total_t
 }
 
 static int varlen_check(const char* who, const void* qkv, const int* offsets, const void* out, int n_bags, long total_tiles, int max_tiles, int H, int dtype,
-                        const void* ws, size_t ws_bytes, int t_limit) {
+                        const void* ws, size_t ws_bytes, int t_limit, int extra_rows = 1) {
     AMDS_REQUIRE(qkv && offsets && out && ws, "%s: null pointer", who);
-    AMDS_REQUIRE(n_bags >= 0 && n_bags <= 65535 && total_tiles >= 0 && max_tiles >= 0 && max_tiles + 1 <= t_limit && H > 0 && H <= 65535 &&
-                 total_tiles + n_bags < (1L << 31) && FA_SPAN_OK(max_tiles + 1, H),
+    AMDS_REQUIRE(n_bags >= 0 && n_bags <= 65535 && total_tiles >= 0 && max_tiles >= 0 && max_tiles + extra_rows <= t_limit && H > 0 && H <= 65535 &&
+                 total_tiles + (long)n_bags * extra_rows < (1L << 31) && FA_SPAN_OK(max_tiles + extra_rows, H),
                  "%s: bad shape n_bags=%d total_tiles=%ld max_tiles=%d H=%d (a bag's q | k | v rows must stay below the 2 GB of a buffer descriptor)", who, n_bags,
                  total_tiles, max_tiles, H);
     AMDS_REQUIRE(dtype == AMDS_F16 || dtype == AMDS_BF16, "%s: bad dtype %d", who, dtype);
@@ -1048,8 +1049,19 @@ extern "C" int amds_attention_varlen(const void* qkv, const int* offsets, void* 
     int rc = varlen_check("amds_attention_varlen", qkv, offsets, out, n_bags, total_tiles, max_tiles, H, dtype, ws, ws_bytes, 1 << 30);
     if (rc != AMDS_OK || n_bags == 0) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = varlen_table_build(offsets, n_bags, total_tiles, max_tiles, ws, st)) != AMDS_OK) return rc;
+    if ((rc = varlen_table_build(offsets, n_bags, total_tiles, max_tiles, 1, ws, st)) != AMDS_OK) return rc;
     return attention_varlen_launch(qkv, nullptr, nullptr, out, ws, n_bags, total_tiles, H, dtype, st);
+}
+
+// the class-token-less layout (barspoon's encoder): bag i = rows offsets[i] .. offsets[i+1] - 1 of qkv / out [total_rows]; the same kernel on a table built
+// with extra_rows = 0
+extern "C" int amds_attention_varlen_rows(const void* qkv, const int* offsets, void* out, int n_bags, long total_rows, int max_rows, int H, int dtype, void* ws,
+                                          size_t ws_bytes, void* stream) {
+    int rc = varlen_check("amds_attention_varlen_rows", qkv, offsets, out, n_bags, total_rows, max_rows, H, dtype, ws, ws_bytes, 1 << 30, 0);
+    if (rc != AMDS_OK || n_bags == 0) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = varlen_table_build(offsets, n_bags, total_rows, max_rows, 0, ws, st)) != AMDS_OK) return rc;
+    return attention_varlen_launch(qkv, nullptr, nullptr, out, ws, n_bags, total_rows, H, dtype, st);
 }
 
 extern "C" int amds_attention_alibi_varlen(const void* qkv, const float* coords, const float* head_scale, const int* offsets, void* out, int n_bags,
@@ -1058,7 +1070,7 @@ extern "C" int amds_attention_alibi_varlen(const void* qkv, const float* coords,
     int rc = varlen_check("amds_attention_alibi_varlen", qkv, offsets, out, n_bags, total_tiles, max_tiles, H, dtype, ws, ws_bytes, 1 << 30);
     if (rc != AMDS_OK || n_bags == 0) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = varlen_table_build(offsets, n_bags, total_tiles, max_tiles, ws, st)) != AMDS_OK) return rc;
+    if ((rc = varlen_table_build(offsets, n_bags, total_tiles, max_tiles, 1, ws, st)) != AMDS_OK) return rc;
     return attention_varlen_launch(qkv, coords, head_scale, out, ws, n_bags, total_tiles, H, dtype, st);
 }
 
@@ -1070,6 +1082,6 @@ extern "C" int amds_attention_row_varlen(const void* q, long ldq, const void* qk
     AMDS_REQUIRE(ldq >= H * 64 && ldo >= H * 64 && ldq % 8 == 0, "amds_attention_row_varlen: bad pitches ldq=%ld ldo=%ld", ldq, ldo);
     if (n_bags == 0) return AMDS_OK;
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = varlen_table_build(offsets, n_bags, total_tiles, max_tiles, ws, st)) != AMDS_OK) return rc;
+    if ((rc = varlen_table_build(offsets, n_bags, total_tiles, max_tiles, 1, ws, st)) != AMDS_OK) return rc;
     return attention_row_varlen_launch(q, ldq, qkv, out, ldo, ws, n_bags, max_tiles, H, dtype, st);
 }

@@ -362,10 +362,11 @@ int stage_rows_dt(const void* src, int src_dtype, long ld_src, void* dst, int ds
 
 // amds_bgemm_f32 on the exact-fp32 MFMA whatever amds_set_matmul_precision says (transmil.hip): for the paths that promise exact fp32
 // ragged (variable-length) bags without padding, attention_flash.hip: a table built once per call from device offsets [n_bags + 1] (tile counts; bag i's
-// token rows, class token first, start at offsets[i] + i), lengths clamped to [0, max_tiles] and rows to the buffers on the device
+// token rows, class token first, start at offsets[i] + i; extra_rows = 0: no class token, bag i's rows are offsets[i] .. offsets[i+1] - 1), lengths clamped
+// to [0, max_tiles] and rows to the buffers on the device
 long varlen_work_items(int n_bags, long total_tiles);
 size_t varlen_table_bytes(int n_bags, long total_tiles);
-int varlen_table_build(const int* offsets, int n_bags, long total_tiles, int max_tiles, void* table, hipStream_t st);
+int varlen_table_build(const int* offsets, int n_bags, long total_tiles, int max_tiles, int extra_rows, void* table, hipStream_t st);
 const int2* varlen_table_bags(const void* table);      // int2 {first token row, token count} per bag
 int attention_varlen_launch(const void* qkv, const float* coords, const float* head_scale, void* out, const void* table, int n_bags, long total_tiles,
                             int H, int dtype, hipStream_t st);           // coords != NULL: ALiBi (out bf16)

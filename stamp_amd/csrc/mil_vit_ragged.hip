@@ -12,7 +12,7 @@
 // computes it, and the library's default picks the kernel by M (include/amdstamp.h, amds_gemm_ex: ids 12 / 13 differ from 0 in the last bits).  So each
 // GEMM runs on the kernel the longest bag's own call would pick when that is kernel 0 (then every shorter bag's call picks it too), and by shape otherwise --
 // a bag whose own call leaves kernel 0 shares a call bit-identically only when it is alone (amds_mil_vit_ragged_max_shared_tiles; the Python grouping sends it
-// alone).  n_bags == 1 is the per-bag call's shape exactly.
+// alone).  n_bags == 1 is the per-bag call's shape exactly.  The rule is ragged_cfg (model_call.h), shared with barspoon_ragged.hip.
 #include "model_call.h"
 
 namespace amds {
@@ -46,8 +46,6 @@ int ragged_plan(const amds_mil_vit_cfg* c, int n, long total_tiles, int max_tile
     p->total = ar.off;
     return AMDS_OK;
 }
-
-#define FA_SPAN_OK(T, H) ((long)(T) * 3 * (H) * 128 < (1L << 31))        // attention_flash.hip: one bag's q | k | v rows under one buffer descriptor
 
 // the bag owning token row r: the last bag whose first row is <= r (rows of the table ascend for well-formed offsets; for others the search still ends in range)
 __device__ __forceinline__ int bag_of_row(const int2* __restrict__ bags, int n, long r) {
@@ -95,12 +93,6 @@ __global__ void __launch_bounds__(128) gather_cls_kernel(const float* __restrict
     }
 }
 
-// GEMM kernel of a ragged call whose bags have at most `rows` rows in this GEMM (see the file comment)
-int ragged_cfg(int n_bags, long rows, int N, int K) {
-    if (n_bags == 1) return -1;
-    return default_gemm_cfg((int)min(rows, (long)INT32_MAX), N, K) == 0 ? 0 : -1;
-}
-
 }  // namespace
 }  // namespace amds
 
@@ -121,15 +113,7 @@ extern "C" int amds_mil_vit_ragged_max_shared_tiles(const amds_mil_vit_cfg* cfg_
         return default_gemm_cfg(T, p.Dp, p.Fp) == 0 && default_gemm_cfg(T + 1, 3 * p.Da, p.Dp) == 0 && default_gemm_cfg(T + 1, 2 * p.Da, p.Dp) == 0 &&
                default_gemm_cfg(T + 1, p.Dp, p.Da) == 0 && default_gemm_cfg(T + 1, p.FFp, p.Dp) == 0 && default_gemm_cfg(T + 1, p.Dp, p.FFp) == 0;
     };
-    const int cap = 32767;                          // longer bags take the full last block in their own call (cls_tail, mil_vit.hip)
-    if (!shared(1)) return cap;                     // a fixed kernel (AMDS_GEMM_CFG): every M gives the same rows
-    if (shared(cap)) return cap;
-    int lo = 1, hi = cap;                           // shared(lo), !shared(hi)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) / 2;
-        if (shared(mid)) lo = mid; else hi = mid;
-    }
-    return lo;
+    return ragged_max_shared(shared, 32767);        // longer bags take the full last block in their own call (cls_tail, mil_vit.hip)
 }
 
 extern "C" int amds_mil_vit_forward_ragged(const amds_mil_vit_cfg* cfg_host, const amds_mil_vit_weights* w_host, const void* feats, int feats_dtype,
@@ -173,7 +157,7 @@ extern "C" int amds_mil_vit_forward_ragged(const amds_mil_vit_cfg* cfg_host, con
     void* table = base + p.table;
     const int2* bags = varlen_table_bags(table);
 
-    if ((rc = varlen_table_build(offsets, Bn, total_tiles, max_tiles, table, st)) != AMDS_OK) return rc;
+    if ((rc = varlen_table_build(offsets, Bn, total_tiles, max_tiles, 1, table, st)) != AMDS_OK) return rc;
     // project_features (as mil_vit.hip)
     const void* a = feats;
     if (Mt > 0 && !(feats_dtype == dt && c.n_feats == p.Fp)) {

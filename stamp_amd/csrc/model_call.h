@@ -1,6 +1,9 @@
 // model_call.h -- host-only helpers shared by the "one C call" model entries (mil_vit*.hip, barspoon*.hip, ticon.hip, transmil_*.hip, nystrom_train.hip):
-// the padded operand layout of the MIL heads, the arena arithmetic of their plans, the status chain.  The launch sequences stay with the entries.
+// the padded operand layout of the MIL heads, the arena arithmetic of their plans, the status chain, the GEMM kernel rule of the ragged calls.  The launch
+// sequences stay with the entries.
 #pragma once
+#include <algorithm>
+#include <cstdint>
 #include "launch.h"
 
 namespace amds {
@@ -47,6 +50,29 @@ inline bool enc_layer_has_transposes(const amds_mil_vit_layer& L) { return L.in_
 // never a multiple of 256).
 inline int gemm_train(int dt, const void* A, long lda, const void* W, long ldw, long M, int N, int K, int epi, void* out, long ldo, const float* bias, void* st) {
     return amds_gemm_ex(-2, A, lda, W, ldw, (int)M, N, K, dt, epi, out, ldo, bias, nullptr, nullptr, 0, 0, 0, 1.0f, st);
+}
+
+// attention_flash.hip addresses one bag's q | k | v rows under one buffer descriptor (2 GB): the ragged calls check their longest bag against it
+#define FA_SPAN_OK(T, H) ((long)(T) * 3 * (H) * 128 < (1L << 31))
+
+// GEMM kernel of a ragged call (mil_vit_ragged.hip, barspoon_ragged.hip) whose bags have at most `rows` rows in this GEMM.  A GEMM row depends on the kernel
+// that computes it and the library's default picks the kernel by M, so the call runs on the kernel the longest bag's own call would pick when that is kernel 0
+// (then every shorter bag's call picks it too), and by shape otherwise; one bag alone is its own call's shape exactly.
+inline int ragged_cfg(int n_bags, long rows, int N, int K) {
+    if (n_bags == 1) return -1;
+    return default_gemm_cfg((int)std::min(rows, (long)INT32_MAX), N, K) == 0 ? 0 : -1;
+}
+// the longest bag all of whose GEMMs (shared(T): every shape of a bag of T tiles picks kernel 0; monotone in T) stay on kernel 0, at most `cap`
+template <typename F>
+inline int ragged_max_shared(F shared, int cap) {
+    if (!shared(1)) return cap;                     // a fixed kernel (AMDS_GEMM_CFG): every M gives the same rows
+    if (shared(cap)) return cap;
+    int lo = 1, hi = cap;                           // shared(lo), !shared(hi)
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        if (shared(mid)) lo = mid; else hi = mid;
+    }
+    return lo;
 }
 
 }  // namespace amds

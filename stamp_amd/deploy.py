@@ -98,15 +98,45 @@ def _ragged_outputs(model, batches, device, bags_per_call: int, max_rows_per_cal
     return outs
 
 
+def _barspoon_outputs(model, batches, device, bags_per_call: int, max_rows_per_call: int) -> list[dict]:
+    """The `{target: logits}` of the barspoon loop in `predict_`, in batch order, with consecutive one-bag batches grouped into ragged calls
+    (`EncDecTransformer.forward_ragged`, which sends a bag too long to share alone): one dict of [n, n_out] rows per group, each row the one its own
+    forward gives, bit for bit.  Batches of several bags keep the dense forward."""
+    outs: list = []
+    pend: list = []
+
+    def flush():
+        if not pend:
+            return
+        pos = None if pend[0][1] is None else [p for _, p in pend]
+        out = model.forward_ragged([b for b, _ in pend], pos, bags_per_call=bags_per_call, max_rows_per_call=max_rows_per_call)
+        outs.append(out)
+        pend.clear()
+
+    for bags, coords, *_ in batches:
+        if bags.shape[0] == 1:
+            if pend and (pend[0][1] is None) != (coords is None):
+                flush()
+            pend.append((bags[0].to(device), None if coords is None else coords[0].to(device)))
+            if len(pend) >= bags_per_call:
+                flush()
+            continue
+        flush()
+        outs.append(model(bags.to(device), None if coords is None else coords.to(device)))
+    flush()
+    return outs
+
+
 @torch.no_grad()
 def predict_(model: torch.nn.Module, batches: Iterable, patient_ids: Sequence[str], *, task: str, device="cuda", bags_per_call: int = 1,
              max_rows_per_call: int = 262144) -> dict[str, torch.Tensor]:
     """batches: iterable of (bags, coords, bag_sizes, targets) as the reference's test DataLoader yields them (full bags, batch 1,
     `modeling/data.py:255-277`); only bags / coords are used (`Lit*.predict_step`, `models/__init__.py:302-313`: `mask=None`).
     Returns patient -> prediction on the CPU: class probabilities (classification), raw value (regression), risk score (survival).
-    bags_per_call > 1 (`vit` and TransMIL heads; other heads ignore it): consecutive bags share ONE ragged forward, at most `bags_per_call` bags and
-    `max_rows_per_call` token rows per call (TransMIL: padded token rows), a bag too long to share runs alone; every prediction is the one of the one-bag
-    loop (`vit`: bit for bit; TransMIL: to fp32 rounding, every bag with its own grid, padding and pseudo-inverse scale as at batch 1)."""
+    bags_per_call > 1 (`vit`, TransMIL and barspoon heads; any other module ignores it): consecutive bags share ONE ragged forward, at most
+    `bags_per_call` bags and `max_rows_per_call` token rows per call (TransMIL: padded token rows; barspoon: tile rows), a bag too long to share runs alone;
+    every prediction is the one of the one-bag loop (`vit` and barspoon: bit for bit; TransMIL: to fp32 rounding, every bag with its own grid, padding and
+    pseudo-inverse scale as at batch 1)."""
     if bags_per_call < 1 or max_rows_per_call < 1:
         raise ValueError("bags_per_call and max_rows_per_call must be >= 1")
     if task not in ("classification", "regression", "survival"):
@@ -115,9 +145,14 @@ def predict_(model: torch.nn.Module, batches: Iterable, patient_ids: Sequence[st
     if hasattr(model, "target_labels") and hasattr(model, "class_tokens"):
         # multi-target head (barspoon): `LitMilClassificationMixin.predict_step` returns softmax(logits) per target (barspoon.py:333-344) and the
         # reference's `_predict` applies softmax to what it gets AGAIN when the task is classification (deploy.py:416-438) -- reproduced, not repaired
+        from .barspoon import EncDecTransformer
+
         per: dict[str, list[torch.Tensor]] = {}
-        for bags, coords, *_ in batches:
-            out = model(bags.to(device), coords.to(device))
+        if isinstance(model, EncDecTransformer) and bags_per_call > 1:
+            outs_mt = _barspoon_outputs(model, batches, device, bags_per_call, max_rows_per_call)
+        else:               # any other multi-target module keeps its own forward, one batch at a time
+            outs_mt = (model(bags.to(device), coords.to(device)) for bags, coords, *_ in batches)
+        for out in outs_mt:
             for t, v in out.items():
                 per.setdefault(t, []).append(torch.softmax(v.float(), 1).cpu())
         if not per:

@@ -453,12 +453,14 @@ def max_shared_tiles(pk: PackedVit) -> int:
     return n
 
 
-def group_bags(lengths, bags_per_call: int, max_rows_per_call: int, max_shared: int = MAX_SOLO_TILES) -> list[tuple[int, int]]:
-    """Consecutive bags -> [start, end) groups for the ragged forward: at most `bags_per_call` bags and `max_rows_per_call` token rows (tiles + one class
-    token per bag) per group; a bag longer than `max_shared` tiles (or than MAX_SOLO_TILES) is a group of its own, as is a bag whose rows alone exceed
-    the row limit.  Order is kept; host-only."""
+def group_bags(lengths, bags_per_call: int, max_rows_per_call: int, max_shared: int = MAX_SOLO_TILES, extra_rows: int = 1) -> list[tuple[int, int]]:
+    """Consecutive bags -> [start, end) groups for the ragged forward: at most `bags_per_call` bags and `max_rows_per_call` token rows (tiles +
+    `extra_rows` per bag: the `vit` head's class token; 0 for barspoon, whose encoder has none) per group; a bag longer than `max_shared` tiles (or than
+    MAX_SOLO_TILES) is a group of its own, as is a bag whose rows alone exceed the row limit.  Order is kept; host-only."""
     if bags_per_call < 1 or max_rows_per_call < 1:
         raise ValueError("bags_per_call and max_rows_per_call must be >= 1")
+    if extra_rows not in (0, 1):
+        raise ValueError("extra_rows must be 0 or 1")
     limit = min(int(max_shared), MAX_SOLO_TILES)
     groups: list[tuple[int, int]] = []
     start, rows = 0, 0
@@ -466,10 +468,10 @@ def group_bags(lengths, bags_per_call: int, max_rows_per_call: int, max_shared: 
     for i, t in enumerate(lengths):
         t = int(t)
         solo = t > limit
-        if i > start and (solo or i - start >= bags_per_call or rows + t + 1 > max_rows_per_call):
+        if i > start and (solo or i - start >= bags_per_call or rows + t + extra_rows > max_rows_per_call):
             groups.append((start, i))
             start, rows = i, 0
-        rows += t + 1
+        rows += t + extra_rows
         if solo:
             groups.append((i, i + 1))
             start, rows = i + 1, 0
