@@ -810,6 +810,29 @@ int amds_gather_rows(const void* src, long src_ld, const long* idx, int n_idx, v
  * 32-bit pattern of every element; shifts (u8, drawn by the caller with torch.randint like the reference). */
 int amds_vary_precision(const void* bits_in, const uint8_t* shifts, void* bits_out, long n, int elem_bytes, void* stream);
 
+/* A whole training batch of fixed-size bags out of a feature store that stays in HBM, ONE launch (csrc/bag_batch.hip): `_to_fixed_size_bag`
+ * (reference src/stamp/modeling/data.py:811-862) plus the `.float()` of :617 for n_bags bags at once.
+ *   store         [rows][store_ld] AMDS_F16 / AMDS_F32, device; may exceed 4 GiB (every byte offset is 64-bit)
+ *   store_coords  fp32 [rows][2], or NULL together with coords_out
+ *   idx           device int64 [n_bags][bag_size]: absolute store rows, drawn by the caller; a negative entry (-1) is a padding row.  The call does not
+ *                 know how many rows the store has: an index past its end is the caller's error.
+ *   bags_out      [n_bags][bag_size][out_ld]: columns 0..cols) = cast(vp(float(store[idx]))); columns cols..out_ld) and every padding row are written as
+ *                 zeros, so out_ld = the padded pitch of a 16-bit GEMM operand gives the operand rows as they are
+ *   coords_out    fp32 [n_bags][bag_size][2] = store_coords[idx], (0, 0) for a padding row
+ * dtype pairs: f16 -> f32, f16 -> f16, f16 -> bf16 (round to nearest even: the bits of amds_convert_f16_bf16), f32 -> f32.  16-byte loads and stores when
+ * store_ld and out_ld are multiples of 8 elements and both bases 16-byte aligned, element-wise otherwise (any cols >= 1).
+ * vp_min_fraction_bits in 1..22: vary_precision (reference src/stamp/modeling/transforms.py:5-29) fused in: the fp32 pattern of every real element is masked
+ * with ~0 << s before the cast, s uniform on [0, 23 - vp_min_fraction_bits), drawn from the library's counter-based hash (the dropout masks' hash) keyed on
+ * (seed, stream_id, output element index (b * bag_size + i) * cols + c) -- independent of idx.  0: off.  This is the reference's DISTRIBUTION, not torch's CPU
+ * random stream (which would take one host draw per element of every patient's whole feature matrix); amds_bag_batch_shifts writes the same s values.
+ * n_bags == 0 succeeds without a launch; NULL pointers, bag_size < 1, out_ld < cols, another dtype pair or vp_min_fraction_bits outside 0..22 return
+ * AMDS_ERR_INVALID before any launch.  No atomics, no workspace; deterministic; launches only, on `stream`. */
+int amds_bag_batch_gather(const void* store, long store_ld, int store_dtype, const float* store_coords, const long* idx, void* bags_out, long out_ld,
+                          int out_dtype, float* coords_out, int n_bags, int bag_size, int cols, int vp_min_fraction_bits, uint64_t seed, uint32_t stream_id,
+                          void* stream);
+/* the shifts the call above draws, u8 [n_bags][bag_size][cols] (all 0 when vp_min_fraction_bits == 0); for tests */
+int amds_bag_batch_shifts(uint8_t* shifts, int n_bags, int bag_size, int cols, int vp_min_fraction_bits, uint64_t seed, uint32_t stream_id, void* stream);
+
 /* Mean over tiles: x [B][T][F] (f16/f32) -> out fp32 [B][F] (reference src/stamp/modeling/models/mlp.py:40-41). */
 int amds_mean_pool(const void* x, float* out, int B, int T, int F, int in_dtype, void* stream);
 /* its gradient: dx fp32 [B][T][F] = dy[B][F] / T (training the MLP / Linear heads on bags, mlp.py:40-41) */

@@ -12,7 +12,8 @@ Mirrors the reference's src/stamp/modeling/data.py (the part `stamp train` / `st
 Files are read through `stamp_amd.h5io` (h5py, else libhdf5 via ctypes, else the pure-Python subset), coordinates through its `get_coords`
 (the reference's three conventions).  Sampling draws from torch's CPU generator exactly like the reference (`torch.randperm`), so a seeded run
 picks the same tiles.  This is host code, as in the reference (DataLoader workers); with `device=` the row gather of the fixed-size bag runs on
-the GPU (`amds_gather_rows`) for callers that keep a cohort's features resident in HBM.  Pinned by tests/golden/bag_dataset.json, made by
+the GPU (`amds_gather_rows`); `stamp_amd.cohort.ResidentCohort` keeps a whole cohort's features resident in HBM and builds the same batches with
+one launch each.  Pinned by tests/golden/bag_dataset.json, made by
 executing the reference's own definitions (tools/make_golden.py::golden_bag_dataset)."""
 from __future__ import annotations
 

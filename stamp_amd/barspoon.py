@@ -199,25 +199,45 @@ class EncDecTransformer(nn.Module):
         dev = bags[0].device if bags else next(self.parameters()).device
         if not bags:
             return {t: torch.empty(0, n, dtype=torch.float32, device=dev) for t, n in self.target_n_outs.items()}
-        pack = self._pack(dev)
-        cfg, wc = pack.cfg, pack.wc
-        lib = _lib.lib()
         # one fp32 product of the call is batched over (bag, decoder head): 65535 batches
         per_call = min(bags_per_call or len(bags), 65535 // self.num_decoder_heads)
         outs = []
         for a, e in mil_core.group_bags(lengths, per_call, max_rows_per_call, self.max_shared_tiles(dev), extra_rows=0):
             rb = mil_core.pack_bags(bags[a:e], None if pl is None else pl[a:e], n_feats=self.d_features, device=dev)
-            n, total, mx = rb.n_bags, rb.total_tiles, rb.max_tiles
-            need = lib.amds_barspoon_ragged_workspace_bytes(C.byref(cfg), n, total, mx)
-            if need == 0:
-                _lib.check(-1, "barspoon_ragged_workspace_bytes")
-            ws = ops.scratch("barspoon_ragged", dev, need)
-            logits = torch.empty(n, pack.total_out, dtype=torch.float32, device=dev)
-            _lib.check(lib.amds_barspoon_forward_ragged(C.byref(cfg), C.byref(wc), rb.feats.data_ptr(), ops._DT[rb.feats.dtype],
-                                                        rb.coords.data_ptr() if rb.coords is not None else None, rb.offsets.data_ptr(), logits.data_ptr(), n,
-                                                        total, mx, ws.data_ptr(), ws.numel(), ops._stream()), "barspoon_forward_ragged")
-            outs.append(logits)
-        return self._split_targets(outs[0] if len(outs) == 1 else torch.cat(outs, dim=0), pack.no)
+            outs.append(self._ragged_call(rb))
+        return self._split_targets(outs[0] if len(outs) == 1 else torch.cat(outs, dim=0), self._pack(dev).no)
+
+    def _ragged_call(self, rb) -> torch.Tensor:
+        """Packed bags -> logits [n_bags, total outputs]: ONE amds_barspoon_forward_ragged."""
+        dev = rb.feats.device
+        pack = self._pack(dev)
+        cfg, wc = pack.cfg, pack.wc
+        lib = _lib.lib()
+        n, total, mx = rb.n_bags, rb.total_tiles, rb.max_tiles
+        need = lib.amds_barspoon_ragged_workspace_bytes(C.byref(cfg), n, total, mx)
+        if need == 0:
+            _lib.check(-1, "barspoon_ragged_workspace_bytes")
+        ws = ops.scratch("barspoon_ragged", dev, need)
+        logits = torch.empty(n, pack.total_out, dtype=torch.float32, device=dev)
+        pos = rb.coords if self.positional_encoding else None
+        _lib.check(lib.amds_barspoon_forward_ragged(C.byref(cfg), C.byref(wc), rb.feats.data_ptr(), ops._DT[rb.feats.dtype],
+                                                    pos.data_ptr() if pos is not None else None, rb.offsets.data_ptr(), logits.data_ptr(), n,
+                                                    total, mx, ws.data_ptr(), ws.numel(), ops._stream()), "barspoon_forward_ragged")
+        return logits
+
+    def forward_infer_ragged(self, rb) -> dict[str, torch.Tensor]:
+        """Bags that are already packed (`mil_core.RaggedBags`, e.g. a view of a resident cohort: `ResidentCohort.ragged_group`) -> `{target: logits}` in
+        ONE library call, nothing copied.  Grouping is the caller's: a bag longer than `max_shared_tiles` keeps its own call's bits only when alone.
+        Inference only, like `forward_ragged`."""
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError("forward_infer_ragged is the inference forward: call it in eval mode (.eval()) under torch.no_grad() or torch.inference_mode()")
+        if rb.n_bags == 0:
+            return {t: torch.empty(0, n, dtype=torch.float32, device=rb.feats.device) for t, n in self.target_n_outs.items()}
+        if not rb.feats.is_cuda or rb.feats.dim() != 2 or rb.feats.shape[1] != self.d_features or not rb.feats.is_contiguous() or rb.feats.dtype not in ops._DT:
+            raise ValueError(f"packed bags must be a contiguous [tiles, {self.d_features}] f16 / bf16 / f32 tensor on the GPU")
+        if self.positional_encoding and rb.coords is None:
+            raise ValueError("positional_encoding=True needs the tile positions of every bag")
+        return self._split_targets(self._ragged_call(rb), self._pack(rb.feats.device).no)
 
     # ---- training (the reference's `LitMilClassificationMixin.step`, barspoon.py:263-321) -------------------------------------------------
     def forward_train(self, tile_tokens: torch.Tensor, tile_positions: torch.Tensor, *, seed: int | None = None,

@@ -1,0 +1,208 @@
+"""A cohort's tile features resident in HBM, feeding the MIL trainers: one gather launch per training batch, zero-copy views for validation.
+
+`bags.tile_bag_dataloader` restates the reference's feed (src/stamp/modeling/data.py:532-655): every epoch, for every patient, a DataLoader worker reads all of
+the patient's `.h5` files again, converts them to fp32, samples a bag, and the batch crosses PCIe as fp32.  A cohort fits on the card (1 000 patients x 10 k
+tiles x 1 024 fp16 features = 20 GB of 288 GB), so `ResidentCohort` reads every file ONCE, keeps the rows packed in device memory in the files' own precision
+
+    feats  [R, F]   fp16 when every file is fp16, else fp32      patient p = rows offsets[p] .. offsets[p] + lengths[p]
+    coords [R, 2]   fp32 micrometres (h5io.get_coords)           (its slides concatenated in the order of its file list, as BagDataset does)
+
+and builds a training batch with one `amds_bag_batch_gather` launch (csrc/bag_batch.hip: gather + `.float()` + zero padding of `_to_fixed_size_bag`,
+data.py:811-862, optionally the reference's `vary_precision` transform).  The packed store IS the layout the ragged inference forwards take
+(`mil_core.RaggedBags`), so a validation group is a view: a row slice and rebased offsets, no copy.
+
+Random draws, per epoch of `train_batches`, all from `generator` (None: torch's global CPU generator), in this order:
+  1. shuffle: ONE `torch.randperm(len(cohort))` -- the patient order of the epoch;
+  2. the bags' own draws, `mil.fixed_size_bag_indices` per patient in that order (a `torch.randperm(n)` for every patient with more than `bag_size` tiles):
+     exactly what fetching `BagDataset` items in that order with `num_workers=0` consumes;
+  3. with `vary_precision_bits`: one `torch.randint` = the epoch's mask seed; batch j masks with (seed, stream_id = j) through the library's counter-based
+     hash.  That is the reference transform's distribution, not torch's random stream (include/amdstamp.h, amds_bag_batch_gather).
+The epoch's whole index plan is built on the host and uploaded once; the loop then only launches (no host synchronisation).
+There is no spilling: a cohort that does not fit `max_bytes` or the free device memory is refused before anything is allocated.  One device; no CPU fallback."""
+from __future__ import annotations
+
+import time
+from collections.abc import Iterable, Sequence
+from typing import Any
+
+import numpy as np
+import torch
+
+from . import h5io
+from .bags import PatientData, parse_targets
+
+MAX_ROWS = 2 ** 31 - 1          # the ragged forwards address tile rows with 32-bit offsets
+
+
+def plan_indices(offsets: Sequence[int], lengths: Sequence[int], patients: Iterable[int], bag_size: int, deterministic: bool = False,
+                 generator: torch.Generator | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """-> (idx int64 [B, bag_size] of absolute store rows, -1 = padding row; bag_sizes int64 [B] = min(bag_size, tiles)) for the patients of a batch (or of a
+    whole epoch) in the given order: `mil.fixed_size_bag_indices` per patient, so a seeded generator is consumed exactly as by `BagDataset` items fetched in
+    that order.  Host only."""
+    from .mil import fixed_size_bag_indices
+    if bag_size < 1:
+        raise ValueError("bag_size must be >= 1")
+    patients = [int(p) for p in patients]
+    idx = torch.full((len(patients), int(bag_size)), -1, dtype=torch.int64)
+    sizes = torch.empty(len(patients), dtype=torch.int64)
+    for b, p in enumerate(patients):
+        local = fixed_size_bag_indices(int(lengths[p]), int(bag_size), deterministic, generator)
+        idx[b, :local.numel()] = local + int(offsets[p])
+        sizes[b] = local.numel()
+    return idx, sizes
+
+
+def _check_size(nbytes: int, max_bytes: int | None, device) -> None:
+    if max_bytes is not None and nbytes > max_bytes:
+        raise ValueError(f"the cohort needs {nbytes} bytes of device memory, max_bytes allows {int(max_bytes)} (there is no spilling)")
+    free = torch.cuda.mem_get_info(device)[0]
+    if nbytes > free:
+        raise ValueError(f"the cohort needs {nbytes} bytes of device memory, {free} are free on {device} (there is no spilling)")
+
+
+class ResidentCohort:
+    def __init__(self, patient_data: Sequence[PatientData] | None = None, *, task: str, categories: Sequence[str] | None = None, device="cuda",
+                 max_bytes: int | None = None, feature_files: Sequence[Iterable] | None = None, ground_truths: Sequence[Any] | None = None) -> None:
+        """patient_data (or `feature_files` per patient + `ground_truths`), `task` / `categories` as `bags.parse_targets` takes them.  Files are read as
+        `BagDataset.__getitem__` reads them (`feats` or `patch_embeddings`, `h5io.get_coords`, a patient's slides concatenated in order), one patient at a
+        time through a pinned staging buffer: the host never holds more than two patients."""
+        if patient_data is None:
+            if feature_files is None or ground_truths is None or len(feature_files) != len(ground_truths):
+                raise ValueError("give patient_data, or feature_files and as many ground_truths")
+            patient_data = [PatientData(ground_truth=g, feature_files=f) for f, g in zip(feature_files, ground_truths)]
+        self.files = [[f for f in p.feature_files] for p in patient_data]
+        self.targets, self.categories = parse_targets(patient_data=patient_data, task=task, categories=categories)
+        self.multi_target = isinstance(self.targets, list)
+        self.device = torch.device(device)
+        # ---- pass 1: dataset headers -> rows per patient, feature width, precision; the refusal comes before any allocation
+        shapes = [[h5io.feature_shape(f) for f in fs] for fs in self.files]
+        widths = {s[1] for ps in shapes for s in ps}
+        if len(widths) != 1:
+            raise ValueError(f"the cohort's files must share one feature width, got {sorted(widths)}")
+        self.n_feats = widths.pop()
+        self.dtype = torch.float16 if all(s[2] == np.float16 for ps in shapes for s in ps) else torch.float32
+        self.lengths = [sum(s[0] for s in ps) for ps in shapes]
+        self.offsets = [0]
+        for n in self.lengths:
+            self.offsets.append(self.offsets[-1] + n)
+        R = self.offsets[-1]
+        if R > MAX_ROWS:
+            raise ValueError(f"{R} tile rows do not fit the 32-bit row index (at most {MAX_ROWS})")
+        item = 2 if self.dtype == torch.float16 else 4
+        self.nbytes = R * (self.n_feats * item + 8)
+        _check_size(self.nbytes, max_bytes, self.device)
+        # ---- pass 2: read and upload
+        t0 = time.perf_counter()
+        self.feats = torch.empty(R, self.n_feats, dtype=self.dtype, device=self.device)
+        self.coords = torch.empty(R, 2, dtype=torch.float32, device=self.device)
+        self._upload(max(self.lengths, default=0), item)
+        self._offsets_dev = torch.tensor(self.offsets, dtype=torch.int32).to(self.device)
+        self._lengths_dev = torch.tensor(self.lengths, dtype=torch.int64).to(self.device)
+        if self.multi_target:
+            self._targets_dev = {k: torch.stack([t[k] for t in self.targets]).to(self.device) for k in (self.targets[0] if self.targets else {})}
+        else:
+            self._targets_dev = self.targets.to(self.device)
+        torch.cuda.synchronize(self.device)
+        self.load_seconds = time.perf_counter() - t0
+
+    def _upload(self, max_rows: int, item: int) -> None:
+        Fd, dev = self.n_feats, self.device
+        stage = [(torch.empty(max(max_rows, 1) * Fd, dtype=self.dtype).pin_memory(), torch.empty(max(max_rows, 1) * 2, dtype=torch.float32).pin_memory(),
+                  torch.cuda.Event()) for _ in range(2)]
+        used = [False, False]
+        for p, fs in enumerate(self.files):
+            fbuf, cbuf, ev = stage[p % 2]
+            if used[p % 2]:
+                ev.synchronize()                  # the copy that last read this staging buffer has finished
+            n, o = self.lengths[p], 0
+            fv, cv = fbuf[:n * Fd].view(n, Fd), cbuf[:n * 2].view(n, 2)
+            for f in fs:
+                d, a = h5io.read_file(f)
+                x = np.asarray(d["feats"] if "feats" in d else d["patch_embeddings"])
+                c = np.asarray(h5io.get_coords(d, a).coords_um)
+                if o + x.shape[0] > n or x.shape[1] != Fd or c.shape != (x.shape[0], 2):
+                    raise RuntimeError(f"{f}: shape {x.shape} / coords {c.shape} differ from the file's header (changed while loading?)")
+                fv[o:o + x.shape[0]].copy_(torch.from_numpy(np.ascontiguousarray(x)))           # (the `.float()` of data.py:617 when the store is fp32)
+                cv[o:o + x.shape[0]].copy_(torch.from_numpy(np.ascontiguousarray(c)))
+                o += x.shape[0]
+            if o != n:
+                raise RuntimeError(f"patient {p}: read {o} rows, the headers announced {n}")
+            a0 = self.offsets[p]
+            self.feats[a0:a0 + n].copy_(fv, non_blocking=True)
+            self.coords[a0:a0 + n].copy_(cv, non_blocking=True)
+            ev.record()
+            used[p % 2] = True
+
+    def __len__(self) -> int:
+        return len(self.lengths)
+
+    # ---- index planning (host) -----------------------------------------------------------------------------------------------------------------
+    def plan_indices(self, patients: Iterable[int], bag_size: int, deterministic: bool = False, generator: torch.Generator | None = None):
+        """`plan_indices` of this cohort's offsets and lengths."""
+        return plan_indices(self.offsets, self.lengths, patients, bag_size, deterministic, generator)
+
+    def _targets_of(self, sel: torch.Tensor):
+        if self.multi_target:
+            return {k: v[sel] for k, v in self._targets_dev.items()}          # the dict `bags.collate_multitarget` builds
+        return self._targets_dev[sel]
+
+    # ---- training batches ------------------------------------------------------------------------------------------------------------------------
+    def _epoch(self, batch_size, bag_size, shuffle, generator, out_dtype, vary_precision_bits, drop_last, with_sizes):
+        from . import ops
+        N = len(self)
+        order = torch.randperm(N, generator=generator) if shuffle else torch.arange(N)
+        if drop_last:
+            order = order[:N - N % batch_size]
+        idx, sizes = self.plan_indices(order.tolist(), bag_size, deterministic=not shuffle, generator=generator)
+        bits = int(vary_precision_bits or 0)
+        seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator).item()) if bits else 0
+        idx, sizes, order = idx.to(self.device), sizes.to(self.device), order.to(self.device)          # the epoch's plan: uploaded once
+        for j, a in enumerate(range(0, order.numel(), batch_size)):
+            e = min(a + batch_size, order.numel())
+            bags, coords = ops.bag_batch_gather(self.feats, self.coords, idx[a:e], out_dtype, vary_precision_bits=bits, seed=seed, stream_id=j)
+            targets = self._targets_of(order[a:e])
+            yield (bags, coords, sizes[a:e], targets) if with_sizes else (bags, coords, targets)
+
+    def train_batches(self, batch_size: int, bag_size: int, shuffle: bool = True, generator: torch.Generator | None = None,
+                      out_dtype: torch.dtype = torch.float32, vary_precision_bits: int | None = None, drop_last: bool = False):
+        """-> the callable `mil_train.fit` takes: per epoch an iterable of (bags [B, bag_size, F] `out_dtype`, coords fp32 [B, bag_size, 2], bag_sizes int64
+        [B], targets [B, D] -- or the dict of a multi-target cohort) on the device.  Sampling is random when shuffling and equidistant when not, like
+        `tile_bag_dataloader`; the draws and their order: module docstring."""
+        if batch_size < 1 or bag_size < 1:
+            raise ValueError("batch_size and bag_size must be >= 1")
+        return lambda: self._epoch(batch_size, bag_size, shuffle, generator, out_dtype, vary_precision_bits, drop_last, True)
+
+    def barspoon_batches(self, batch_size: int, bag_size: int, shuffle: bool = True, generator: torch.Generator | None = None,
+                         out_dtype: torch.dtype = torch.float32, vary_precision_bits: int | None = None, drop_last: bool = False):
+        """`train_batches` as the (feats, positions, targets) 3-tuples `HipBarspoonTrainer.fit` takes."""
+        if batch_size < 1 or bag_size < 1:
+            raise ValueError("batch_size and bag_size must be >= 1")
+        return lambda: self._epoch(batch_size, bag_size, shuffle, generator, out_dtype, vary_precision_bits, drop_last, False)
+
+    # ---- validation: views of the store ----------------------------------------------------------------------------------------------------------
+    def _valid(self, with_sizes):
+        for p in range(len(self)):
+            a, n = self.offsets[p], self.lengths[p]
+            item = (self.feats[a:a + n].unsqueeze(0), self.coords[a:a + n].unsqueeze(0))
+            targets = {k: v[p:p + 1] for k, v in self._targets_dev.items()} if self.multi_target else self._targets_dev[p:p + 1]
+            yield (*item, self._lengths_dev[p:p + 1], targets) if with_sizes else (*item, targets)
+
+    def valid_batches(self):
+        """-> the callable `fit` takes for validation: one whole bag per batch (the reference's `bag_size=None`, batch 1 loader), every tensor a view of the
+        store (features in the store's precision)."""
+        return lambda: self._valid(True)
+
+    def barspoon_valid_batches(self):
+        return lambda: self._valid(False)
+
+    def ragged_group(self, a: int, e: int):
+        """Patients a .. e - 1 as `mil_core.RaggedBags` for the ragged inference forwards: a row slice of the features and of the coordinates, offsets rebased
+        to the slice -- views and one small subtraction, no concatenation."""
+        from .mil_core import RaggedBags
+        if not 0 <= a <= e <= len(self):
+            raise ValueError(f"patients {a}..{e} outside 0..{len(self)}")
+        r0, r1 = self.offsets[a], self.offsets[e]
+        return RaggedBags(self.feats[r0:r1], self.coords[r0:r1], self._offsets_dev[a:e + 1] - r0, tuple(self.lengths[a:e]))
+
+
+__all__ = ["ResidentCohort", "plan_indices", "MAX_ROWS"]

@@ -375,6 +375,37 @@ def read_file(path) -> tuple[dict[str, np.ndarray], dict]:
     return _c_read(str(path))
 
 
+def feature_shape(path) -> tuple[int, int, np.dtype]:
+    """(rows, columns, dtype) of a tile file's `feats` (or `patch_embeddings`) dataset, for sizing a buffer before the data is read.  h5py and libhdf5
+    read the dataset's header only; the pure-Python backend parses whole files and reads this one once more."""
+    be = backend()
+    if be == "h5py":
+        with _h5py.File(path, "r") as f:
+            d = f["feats"] if "feats" in f else f["patch_embeddings"]
+            return int(d.shape[0]), int(d.shape[1]), np.dtype(d.dtype)
+    if be == "c":
+        lib = _lib()
+        f = _chk(lib.H5Fopen(str(path).encode(), _F_RDONLY, 0), f"H5Fopen({path})")
+        try:
+            name = b"feats" if lib.H5Lexists(f, b"feats", 0) > 0 else b"patch_embeddings"
+            d = _chk(lib.H5Dopen2(f, name, 0), f"H5Dopen2({name.decode()})")
+            sp, t = lib.H5Dget_space(d), lib.H5Dget_type(d)
+            dims = (C.c_uint64 * 2)()
+            nd = lib.H5Sget_simple_extent_ndims(sp)
+            if nd == 2:
+                lib.H5Sget_simple_extent_dims(sp, dims, None)
+            cls, size = lib.H5Tget_class(t), lib.H5Tget_size(t)
+            lib.H5Tclose(t); lib.H5Sclose(sp); lib.H5Dclose(d)
+            if nd != 2 or cls != _CLS_FLOAT or size not in (2, 4, 8):
+                raise TypeError(f"{path}: {name.decode()} must be a 2-d floating dataset")
+            return int(dims[0]), int(dims[1]), np.dtype({2: np.float16, 4: np.float32, 8: np.float64}[size])
+        finally:
+            lib.H5Fclose(f)
+    d, _ = read_file(path)
+    a = d["feats"] if "feats" in d else d["patch_embeddings"]
+    return int(a.shape[0]), int(a.shape[1]), np.dtype(a.dtype)
+
+
 def read_open_h5py(f) -> tuple[dict[str, np.ndarray], dict]:
     """`read_file` on an h5py handle that is already open (stamp_amd.bags keeps handles open between reads, as the reference does): only the
     three datasets STAMP reads, attributes normalised (bytes decoded, numpy scalars as Python scalars)."""

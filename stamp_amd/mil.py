@@ -281,6 +281,13 @@ class VisionTransformer(nn.Module):
             return torch.empty(0, self.dim_output, dtype=torch.float32, device=dev)
         return mil_core.forward_ragged(self._infer_pack(dev), bags, coords, device=dev)
 
+    def forward_infer_ragged(self, rb: "mil_core.RaggedBags") -> torch.Tensor:
+        """Bags that are already packed (e.g. `ResidentCohort.ragged_group`: a view of the resident store) -> logits [n_bags, dim_output] in ONE library call,
+        nothing copied.  Grouping is the caller's (`mil_core.group_bags`).  Inference only, like `forward_ragged`."""
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError("forward_infer_ragged is the inference forward: call it in eval mode (.eval()) under torch.no_grad() or torch.inference_mode()")
+        return mil_core.forward_infer_ragged(self._infer_pack(rb.feats.device), rb)
+
     def forward(self, bags: torch.Tensor, *, coords: torch.Tensor | None = None, mask: torch.Tensor | None = None):
         if not bags.is_cuda:
             raise RuntimeError("HIP MIL head needs bags on the GPU (no CPU fallback)")
@@ -602,6 +609,19 @@ class TransMIL(nn.Module):
             return torch.empty(0, self.n_classes, dtype=torch.float32, device=dev)
         dims = (self._fc1[0].in_features, self.dim_hidden, self.n_classes)
         return transmil_core.forward_ragged(self._c_weights(dev), dims, bags, bags_per_call=bags_per_call, max_rows_per_call=max_rows_per_call)
+
+    def forward_infer_ragged(self, rb: "mil_core.RaggedBags") -> torch.Tensor:
+        """Bags that are already packed (e.g. `ResidentCohort.ragged_group`) -> logits [n_bags, dim_output] in ONE library call, nothing copied.  Grouping
+        is the caller's (`transmil_core.group_bags_padded`).  Inference only, like `forward_ragged`."""
+        from . import transmil_core
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError("forward_infer_ragged is the inference forward: call it in eval mode (.eval()) under torch.no_grad() or torch.inference_mode()")
+        if rb.n_bags == 0:
+            return torch.empty(0, self.n_classes, dtype=torch.float32, device=rb.feats.device)
+        if not rb.feats.is_cuda or rb.feats.shape[1] != self._fc1[0].in_features:
+            raise ValueError(f"packed bags must be [tiles, {self._fc1[0].in_features}] on the GPU")
+        dims = (self._fc1[0].in_features, self.dim_hidden, self.n_classes)
+        return transmil_core.forward_infer_ragged(self._c_weights(rb.feats.device), dims, rb)
 
     def _forward_c(self, h: torch.Tensor) -> torch.Tensor:
         import ctypes as C

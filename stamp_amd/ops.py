@@ -518,6 +518,43 @@ def vary_precision(data: torch.Tensor, shifts: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def bag_batch_gather(store: torch.Tensor, store_coords: torch.Tensor | None, idx: torch.Tensor, out_dtype: torch.dtype = torch.float32, *,
+                     out_ld: int | None = None, out: torch.Tensor | None = None, coords_out: torch.Tensor | None = None, vary_precision_bits: int = 0,
+                     seed: int = 0, stream_id: int = 0):
+    """A batch of fixed-size bags out of a resident feature store in one launch (amds_bag_batch_gather): store [R, F] f16 / f32 (rows may be pitched),
+    store_coords fp32 [R, 2] or None, idx int64 [B, bag_size] of store rows with -1 = padding row -> (bags [B, bag_size, F] in `out_dtype`, a view of rows at
+    pitch `out_ld` whose pad columns are zero; coords fp32 [B, bag_size, 2] or None).  `out` (flat, B * bag_size * out_ld elements) / `coords_out`: write
+    there instead of allocating.  vary_precision_bits in 1..22 fuses the reference's vary_precision in (counter-based shifts: `bag_batch_shifts`)."""
+    _dev(store, store_coords, idx)
+    assert store.dim() == 2 and store.stride(1) == 1 and idx.dim() == 2 and idx.dtype == torch.int64 and idx.is_contiguous()
+    Bb, bag = idx.shape
+    Fd = store.shape[1]
+    ld = Fd if out_ld is None else int(out_ld)
+    if out is None:
+        out = torch.empty(Bb * bag * max(ld, 0), dtype=out_dtype, device=store.device)
+    assert out.is_contiguous() and out.dtype == out_dtype and out.numel() >= Bb * bag * ld
+    if store_coords is not None:
+        assert store_coords.dtype == torch.float32 and store_coords.is_contiguous() and store_coords.shape == (store.shape[0], 2)
+        if coords_out is None:
+            coords_out = torch.empty(Bb, bag, 2, dtype=torch.float32, device=store.device)
+        assert coords_out.is_contiguous() and coords_out.dtype == torch.float32 and coords_out.numel() == Bb * bag * 2
+    if Bb:          # (an empty batch has no storage to point at, and the call would launch nothing)
+        _lib.check(_lib.lib().amds_bag_batch_gather(_p(store), store.stride(0), _DT[store.dtype], _p(store_coords), _p(idx), _p(out), ld, _DT[out_dtype],
+                                                    _p(coords_out) if store_coords is not None else None, Bb, bag, Fd, int(vary_precision_bits),
+                                                    int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 32 - 1), _stream()), "bag_batch_gather")
+    bags = out[:Bb * bag * ld].view(Bb, bag, ld)
+    return (bags if ld == Fd else bags[:, :, :Fd]), (coords_out.view(Bb, bag, 2) if store_coords is not None else None)
+
+
+def bag_batch_shifts(n_bags: int, bag_size: int, cols: int, vary_precision_bits: int, seed: int, stream_id: int, device) -> torch.Tensor:
+    """The shifts `bag_batch_gather` draws for these arguments: uint8 [n_bags, bag_size, cols] (amds_bag_batch_shifts)."""
+    s = torch.empty(n_bags, bag_size, cols, dtype=torch.uint8, device=device)
+    _dev(s)
+    _lib.check(_lib.lib().amds_bag_batch_shifts(_p(s), n_bags, bag_size, cols, int(vary_precision_bits), int(seed) & (2 ** 64 - 1),
+                                                int(stream_id) & (2 ** 32 - 1), _stream()), "bag_batch_shifts")
+    return s
+
+
 def mean_pool(x: torch.Tensor) -> torch.Tensor:
     _dev(x)
     assert x.dim() == 3 and x.is_contiguous()

@@ -302,18 +302,26 @@ def group_bags_padded(lengths, dim_hidden: int, bags_per_call: int, max_rows_per
     return groups
 
 
-def forward_infer_ragged(w: "_lib.TransMilWeights", dims: tuple[int, int, int], bags: list) -> torch.Tensor:
-    """Bags [T_i, dim_input] on one device -> logits [N, dim_output], ONE library call: row i is the reference's forward of bag i at batch 1."""
+def forward_infer_ragged(w: "_lib.TransMilWeights", dims: tuple[int, int, int], bags) -> torch.Tensor:
+    """Bags [T_i, dim_input] on one device -> logits [N, dim_output], ONE library call: row i is the reference's forward of bag i at batch 1.
+    `bags`: a list of tensors, or bags that are already packed (`mil_core.RaggedBags`, e.g. a view of a resident cohort: used as they are)."""
     import ctypes as C
+    from .mil_core import RaggedBags
     Fd, Cd, Cc = dims
-    dev = bags[0].device
-    n = len(bags)
-    lengths = [int(b.shape[0]) for b in bags]
-    dts = {b.dtype for b in bags}
-    dt = dts.pop() if len(dts) == 1 else torch.float32
-    if dt not in ops._DT:
-        dt = torch.float32
-    feats = (bags[0].to(dt) if n == 1 else torch.cat([b.to(dt) for b in bags], dim=0)).contiguous()
+    if isinstance(bags, RaggedBags):
+        feats, lengths = bags.feats, [int(t) for t in bags.lengths]
+        dev, n = feats.device, len(lengths)
+        if n == 0 or feats.dtype not in ops._DT or not feats.is_contiguous() or feats.shape[0] != sum(lengths):
+            raise ValueError("packed bags must be a non-empty, contiguous [sum(lengths), dim_input] f16 / bf16 / f32 tensor")
+    else:
+        dev = bags[0].device
+        n = len(bags)
+        lengths = [int(b.shape[0]) for b in bags]
+        dts = {b.dtype for b in bags}
+        dt = dts.pop() if len(dts) == 1 else torch.float32
+        if dt not in ops._DT:
+            dt = torch.float32
+        feats = (bags[0].to(dt) if n == 1 else torch.cat([b.to(dt) for b in bags], dim=0)).contiguous()
     lib = _lib.lib()
     cfg = _lib.TransMilCfg(Fd, Cd, Cc)
     tiles = (C.c_int * n)(*lengths)
