@@ -159,10 +159,18 @@ int amds_swin_mlp192(float* x, int M, const void* packed_w, const float* fc1_b, 
  * 14 = kernel 12 with the one-phase form of its 16-bit-output epilogues (BIAS / BIAS_GELU / BIAS_RELU: the whole tile's values staged in LDS behind a
  * workgroup barrier, then stored) instead of the streamed one (each wave drains its quadrant block row by block row, stores in flight under the
  * value arithmetic): same bits as 12, kept for A/B.  AMDS_GEMM_EPI_STREAM=0 in the environment (read at every call, like AMDS_VIT_PLANES) turns
- * kernels 12 / 13 back to the one-phase form wherever they run -- amds_gemm, amds_gemm_ex, amds_gemm_batched, amds_gemm_lnfold, the encoders. */
+ * kernels 12 / 13 back to the one-phase form wherever they run -- amds_gemm, amds_gemm_ex, amds_gemm_batched, amds_gemm_lnfold, the encoders.
+ * 16 = kernel 12 in its persistent form: min(tiles, CUs rounded down to a multiple of 8) workgroups walk the 256 x 256 output tiles (b, b + G, ...) and
+ * request the next tile's first operands under the current tile's last K tile, so the streamed epilogue's stores drain under the next tile's MFMAs.
+ * It exists for the streamed 16-bit-output epilogues of a single (unbatched) product, the LayerNorm-folded consumer included; every other call of id 16
+ * runs what id 12 runs.  Same bits as 12.  Kernel 12 itself takes this form wherever it exists unless AMDS_GEMM_PERSIST=0 (read at every call);
+ * AMDS_GEMM_EPI_STREAM=0 implies the one-tile form.  AMDS_GEMM_PERSIST_WGS=<n> (read at every call) caps the persistent grid at n workgroups, rounded
+ * down to a multiple of 8 and at least 8: a test and A/B knob that makes small problems walk several tiles per workgroup. */
 int amds_gemm_ex(int cfg, const void* A, long lda, const void* W, long ldw, int M, int N, int K,
                  int dtype, int epi, void* out, long ldo, const float* bias, const float* scale,
                  const float* pos, int np, int T, int P, float acc_scale, void* stream);
+/* Debug counter: how many GEMM launches of this process ran a persistent instantiation (kernel 16 / 12) so far. */
+long amds_gemm_persist_launches(void);
 
 /* OPT-IN fp8 (OCP e4m3) GEMM on v_mfma_f32_16x16x128_f8f6f4 (gfx950: 5 PFLOP/s dense peak, twice the fp16 rate), fp32 accumulate -- the "fp8 MFMA
  * weights" of BASELINE.json configs[4].  The reference computes in fp32 (src/stamp/preprocessing/__init__.py:324-325): e4m3 has 3 mantissa bits,

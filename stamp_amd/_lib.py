@@ -228,6 +228,7 @@ PROTOTYPES = {
     "amds_layernorm": (_i, [_vp, _l, _vp, _vp, _vp, _l, _i, _i, _f, _i, _vp]),
     "amds_gemm": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "amds_gemm_ex": (_i, [_i, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "amds_gemm_persist_launches": (_l, []),
     "amds_gemm_fp8": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _vp]),
     "amds_layernorm_quant_e4m3": (_i, [_vp, _l, _vp, _vp, _f, _vp, _l, _vp, _vp, _i, _i, _vp]),
     "amds_row_bound_scale": (_i, [_vp, _f, _f, _vp, _i, _vp]),

@@ -414,6 +414,8 @@ extern "C" int amds_gemm_lnfold_planes(const void* A, long lda, const void* W, l
     return gemm_dispatch<f16>(12, AMDS_EPI_RESIDUAL, A, lda, W, ldw, M, N, K, ep, st);
 }
 
+extern "C" long amds_gemm_persist_launches(void) { return g_gemm_persist_launches.load(std::memory_order_relaxed); }
+
 // tuning hook: explicit kernel id (see gemm_kernel.h)
 extern "C" int amds_gemm_ex(int cfg, const void* A, long lda, const void* W, long ldw, int M, int N, int K, int dtype,
                             int epi, void* out, long ldo, const float* bias, const float* scale, const float* pos,

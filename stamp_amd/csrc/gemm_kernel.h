@@ -21,6 +21,7 @@
 //     co-resident tiles of an XCD share A and W panels through its L2.
 #pragma once
 #include <stdlib.h>
+#include <atomic>
 #include <type_traits>
 #include "launch.h"
 
@@ -415,13 +416,19 @@ static int launch_gemm_8p64(const void* A, long lda, const void* W, long ldw, in
 template <typename T, int EPI>
 static int launch_gemm_4w64(const void* A, long lda, const void* W, long ldw, int M, int N, int K, const EpiArgs& ep,
                             hipStream_t st);   // gemm_4w64.h
-template <typename T, int EPI, bool SPREAD, int P3, int P0, int PRL, int PRS, bool STREAM, bool TN>
+template <typename T, int EPI, bool SPREAD, int P3, int P0, int PRL, int PRS, bool STREAM, bool PERSIST, bool TN>
 static int launch_gemm_4w16(const void* A, long lda, const void* W, long ldw, int M, int N, int K, const EpiArgs& ep,
                             hipStream_t st);   // gemm_4w16.h
 
 // AMDS_GEMM_EPI_STREAM=0: the one-phase 16-bit epilogue of gemm_4w16.h instead of the streamed one (A/B; read at every call)
 static inline bool gemm_epi_stream() {
     const char* e = getenv("AMDS_GEMM_EPI_STREAM");
+    return !(e && *e && atoi(e) == 0);
+}
+inline std::atomic<long> g_gemm_persist_launches{0};      // launches of a persistent instantiation by this process (amds_gemm_persist_launches)
+// AMDS_GEMM_PERSIST=0: kernel id 12 keeps one output tile per workgroup where its persistent form (id 16) would run (A/B; read at every call)
+static inline bool gemm_persist() {
+    const char* e = getenv("AMDS_GEMM_PERSIST");
     return !(e && *e && atoi(e) == 0);
 }
 
@@ -432,6 +439,9 @@ static inline bool gemm_epi_stream() {
 //       from mid-tile kt on (two barriers per K tile, gemm_4w16.h SCHED 2; A/B)
 //       14 = id 12 with the one-phase 16-bit epilogue (the whole tile staged behind a workgroup barrier, then stored) that ids 12 / 13 had before
 //       theirs was streamed; AMDS_GEMM_EPI_STREAM=0, read at every call, turns 12 / 13 back to it as well (A/B)
+//       16 = id 12 in its persistent form wherever that exists (gemm_4w16.h PERSIST: streamed 16-bit epilogue, one batch): min(tiles, CUs) workgroups walk
+//       the output tiles and prefetch the next tile's first operands under the epilogue; same bits as 12.  Id 12 itself runs that form unless
+//       AMDS_GEMM_PERSIST=0 (read at every call); AMDS_GEMM_EPI_STREAM=0 implies the one-tile form; AMDS_GEMM_PERSIST_WGS=<n> caps the grid (tests, A/B)
 //   8 = 256x256x64 eight-wave staggered two-group pipeline (gemm_8p64.h): the PATCH epilogue, batched fallback
 //  10 = the four-wave structure on v_mfma 32x32x16 (gemm_4w64.h): the one A/B sibling kept
 // (the BK = 32 predecessors 3 / 7 and the ping-pong experiment 9 of round 1 were removed; their measurements stay in profiles/r01_*)
@@ -440,27 +450,30 @@ static int launch_gemm(int cfg, const void* A, long lda, const void* W, long ldw
                        const EpiArgs& ep, hipStream_t st) {
     if (cfg == 10 && N % 256 == 0 && ep.nbatch == 1) return launch_gemm_4w64<T, EPI>(A, lda, W, ldw, M, N, K, ep, st);
     if (cfg == 10) cfg = 8;
-    if ((cfg == 12 || cfg == 13 || cfg == 14) && N % 256 == 0) {
+    if ((cfg == 12 || cfg == 13 || cfg == 14 || cfg == 16) && N % 256 == 0) {
         const bool stream = cfg != 14 && gemm_epi_stream();
         if (cfg == 13) {
-            if (stream) return launch_gemm_4w16<T, EPI, true, -2, 0, 0, 0, true, false>(A, lda, W, ldw, M, N, K, ep, st);
-            return launch_gemm_4w16<T, EPI, true, -2, 0, 0, 0, false, false>(A, lda, W, ldw, M, N, K, ep, st);
+            if (stream) return launch_gemm_4w16<T, EPI, true, -2, 0, 0, 0, true, false, false>(A, lda, W, ldw, M, N, K, ep, st);
+            return launch_gemm_4w16<T, EPI, true, -2, 0, 0, 0, false, false, false>(A, lda, W, ldw, M, N, K, ep, st);
         }
-        if (stream) return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 0, true, false>(A, lda, W, ldw, M, N, K, ep, st);
-        return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 0, false, false>(A, lda, W, ldw, M, N, K, ep, st);
+        if constexpr (EPI == AMDS_EPI_BIAS || EPI == AMDS_EPI_BIAS_GELU || EPI == AMDS_EPI_BIAS_RELU) {
+            if (stream && (cfg == 16 || gemm_persist())) return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 0, true, true, false>(A, lda, W, ldw, M, N, K, ep, st);
+        }
+        if (stream) return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 0, true, false, false>(A, lda, W, ldw, M, N, K, ep, st);
+        return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 0, false, false, false>(A, lda, W, ldw, M, N, K, ep, st);
     }
 #ifdef AMDS_GEMM_PROBE      // overlap probe of round 4 (gemm_4w16.h PRL / PRS; make PROBE=1): K-loop traffic of (0, 2) / (1, 1) / (4, 4) loads, stores per lane and K tile
     if constexpr (EPI == AMDS_EPI_BIAS || EPI == AMDS_EPI_BIAS_GELU || EPI == AMDS_EPI_RESIDUAL) {
-        if (cfg == 21 && N % 256 == 0) return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 2, false, false>(A, lda, W, ldw, M, N, K, ep, st);
-        if (cfg == 22 && N % 256 == 0) return launch_gemm_4w16<T, EPI, true, 6, 6, 1, 1, false, false>(A, lda, W, ldw, M, N, K, ep, st);
-        if (cfg == 23 && N % 256 == 0) return launch_gemm_4w16<T, EPI, true, 6, 6, 4, 4, false, false>(A, lda, W, ldw, M, N, K, ep, st);
+        if (cfg == 21 && N % 256 == 0) return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 2, false, false, false>(A, lda, W, ldw, M, N, K, ep, st);
+        if (cfg == 22 && N % 256 == 0) return launch_gemm_4w16<T, EPI, true, 6, 6, 1, 1, false, false, false>(A, lda, W, ldw, M, N, K, ep, st);
+        if (cfg == 23 && N % 256 == 0) return launch_gemm_4w16<T, EPI, true, 6, 6, 4, 4, false, false, false>(A, lda, W, ldw, M, N, K, ep, st);
     }
 #endif
     if constexpr (EPI == AMDS_EPI_BIAS_F32) {      // 15 = the token-major (TN) form of id 12: weight gradients straight from dY / X (gemm_4w16.h)
-        if (cfg == 15 && N % 256 == 0 && M % 256 == 0) return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 0, false, true>(A, lda, W, ldw, M, N, K, ep, st);
+        if (cfg == 15 && N % 256 == 0 && M % 256 == 0) return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 0, false, false, true>(A, lda, W, ldw, M, N, K, ep, st);
     }
     if (cfg == 15) { set_error("amds_gemm: kernel 15 (token-major operands) takes the BIAS_F32 epilogue and M, N multiples of 256"); return AMDS_ERR_INVALID; }
-    if (cfg == 12 || cfg == 13 || cfg == 14) cfg = 8;
+    if (cfg == 12 || cfg == 13 || cfg == 14 || cfg == 16) cfg = 8;
 
     if (cfg == 8 && N % 256 == 0) return launch_gemm_8p64<T, EPI>(A, lda, W, ldw, M, N, K, ep, st);
     if (cfg == 8) cfg = 0;
