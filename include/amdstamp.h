@@ -223,7 +223,13 @@ int amds_gemm_lnfold(const void* A, long lda, const void* W, long ldw, int M, in
  * proj / fc2 launches move 4 + 4 bytes per element instead of 4 + 4 + 2; x keeps ~22 mantissa bits (elements below 2^-13 |x|_row keep the
  * absolute resolution of fp16 subnormals, 6e-8).  fp16 operands only (a bf16 pair would hold 16 bits).  Tile encoder: the default on the
  * folded path (vit.hip); replaces the fp32 rows `x += ...` of `Block.forward` in timm's VisionTransformer behind
- * src/stamp/preprocessing/extractor/uni2.py:32-43, virchow2.py:29-30. */
+ * src/stamp/preprocessing/extractor/uni2.py:32-43, virchow2.py:29-30.
+ * Epilogue forms (N % 256 == 0 and a grid that fills the chip, i.e. kernel 12): streamed -- each wave drains its 128 x 128 quadrant block row by block row,
+ * old values requested two steps ahead, no workgroup barrier in front of the last store -- inside the persistent tile walk of kernel 16.  hi and lo carry
+ * the same bits in every form; rowpart is summed in another order than in the one-phase form (rounding only) and in a fixed order (no atomics: repeated
+ * calls give the same bits).  Switches, read at every call: AMDS_GEMM_RESID_STREAM=0 = the one-phase form (the tile staged in LDS behind workgroup
+ * barriers, two passes); AMDS_GEMM_RESID_PERSIST=0 = streamed with one output tile per workgroup; AMDS_GEMM_PERSIST=0 and AMDS_GEMM_PERSIST_WGS=<n> act on
+ * this launch as on kernel 16, and amds_gemm_persist_launches counts it. */
 int amds_gemm_lnfold_planes(const void* A, long lda, const void* W, long ldw, int M, int N, int K, void* hi, void* lo, long ld,
                             const float* bias, const float* scale, float* rowpart, void* stream);
 /* x fp32 [M][ldx] -> hi = fp16(x), lo = fp16(x - hi) [M][ld] + (rstd, -mean * rstd) per row: amds_ln_stats_cast for the plane form. */

@@ -395,6 +395,11 @@ extern "C" int amds_gemm_lnfold(const void* A, long lda, const void* W, long ldw
     return AMDS_ERR_INVALID;
 }
 
+#ifdef AMDS_GEMM_TRACE      // make TRACE=1, never the product: where the planes launch writes its per-tile stamps (nullptr = nowhere)
+static const float* g_gemm_trace_buffer = nullptr;
+extern "C" void amds_gemm_trace_buffer(void* p) { g_gemm_trace_buffer = reinterpret_cast<const float*>(p); }
+#endif
+
 // The RESIDUAL producer with the residual stream held as two fp16 planes (include/amdstamp.h): x = hi + lo;  x += scale * (A W^T + bias);
 // hi = fp16(x), lo = fp16(x - hi), rowpart = partial (sum, sum of squares) of the fp32 x.  In place; no fp32 rows exist.
 extern "C" int amds_gemm_lnfold_planes(const void* A, long lda, const void* W, long ldw, int M, int N, int K, void* hi, void* lo, long ld,
@@ -409,6 +414,9 @@ extern "C" int amds_gemm_lnfold_planes(const void* A, long lda, const void* W, l
     EpiArgs ep;
     ep.out = hi; ep.ldo = ld; ep.bias = bias; ep.scale = scale; ep.pos = nullptr; ep.np = ep.T = ep.P = 0; ep.acc_scale = 1.0f;
     ep.xh = hi; ep.xl = lo; ep.rowpart = rowpart;
+#ifdef AMDS_GEMM_TRACE
+    ep.pos = g_gemm_trace_buffer;       // this entry has no `pos`: tools/gemm_deadtime.py hands the stamp array in through amds_gemm_trace_buffer
+#endif
     hipStream_t st = (hipStream_t)stream;
     ProfScope prof(PROF_GEMM, 2.0 * M * (double)N * K, st);
     return gemm_dispatch<f16>(12, AMDS_EPI_RESIDUAL, A, lda, W, ldw, M, N, K, ep, st);

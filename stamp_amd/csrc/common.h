@@ -244,6 +244,37 @@ __device__ __forceinline__ f32x2 half_wave_sum8(const f32x2 (&v)[8], int lane) {
     return c;
 }
 
+// The same recursive halving inside one DPP row of 16 lanes (lane ^ 15, ^ 7, ^ 1 give rows away, ^ 2 completes; four independent masks, so again a fixed
+// coset tree: invariant under lane -> lane ^ c, c < 16).  Returns the pair of row  4 * bit3 + 2 * bit2 + bit0  of the lane index: the lanes with
+// (lane & 2) == 0 hold each of the 8 rows once per 16 lanes.  No cross-row instruction, no nops.
+__device__ __forceinline__ f32x2 row16_sum8(const f32x2 (&v)[8], int lane) {
+    auto dpp = [](float x, auto ctrl_c) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl_c)::value, 0xF, 0xF, true));
+    };
+    typedef std::integral_constant<int, 0x140> MIRROR;
+    typedef std::integral_constant<int, 0x141> HALF_MIRROR;
+    typedef std::integral_constant<int, 0xB1> XOR1;
+    typedef std::integral_constant<int, 0x4E> XOR2;
+    const bool b3 = lane & 8, b2 = lane & 4, b0 = lane & 1;
+    f32x2 a[4], b[2], c;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const f32x2 keep = b3 ? v[4 + j] : v[j], send = b3 ? v[j] : v[4 + j];
+        a[j] = keep + f32x2{dpp(send[0], MIRROR{}), dpp(send[1], MIRROR{})};
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const f32x2 keep = b2 ? a[2 + j] : a[j], send = b2 ? a[j] : a[2 + j];
+        b[j] = keep + f32x2{dpp(send[0], HALF_MIRROR{}), dpp(send[1], HALF_MIRROR{})};
+    }
+    {
+        const f32x2 keep = b0 ? b[1] : b[0], send = b0 ? b[0] : b[1];
+        c = keep + f32x2{dpp(send[0], XOR1{}), dpp(send[1], XOR1{})};
+    }
+    c += f32x2{dpp(c[0], XOR2{}), dpp(c[1], XOR2{})};
+    return c;
+}
+
 // maximum over the 32 lanes that share lane >> 5 (the butterfly of half_wave_sum: four DPP steps and one ds_swizzle, no ds_bpermute round trips)
 __device__ __forceinline__ float half_wave_max(float v) {
     v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)));

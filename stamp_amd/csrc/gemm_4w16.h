@@ -48,7 +48,9 @@ __device__ __forceinline__ f32x4 agpr_read(const f32x4& a) {
 // the matrix pipe, on top of the unchanged real epilogue.  T(probe) - T(id 12) = what overlapped epilogue bytes would still cost.
 // STREAM (16-bit-output epilogues only; kernel id 14 = id 12 with STREAM = false, AMDS_GEMM_EPI_STREAM=0 for ids 12 / 13): the epilogue is streamed
 // block row by block row through wave-private LDS slabs instead of staged as a whole tile behind a workgroup barrier (see the epilogue).
-// PERSIST (kernel id 16, and id 12 unless AMDS_GEMM_PERSIST=0; STREAM with a 16-bit epilogue, SCHED 0, one batch, not TN, no probe): a one-dimensional grid
+//   STREAM with the RESIDUAL epilogue (f16, SCHED 0): the producer on two fp16 planes streamed the same way, fp32 through the slabs (see the epilogue;
+//   AMDS_GEMM_RESID_STREAM=0 restores the one-phase form).
+// PERSIST (kernel id 16, and id 12 unless AMDS_GEMM_PERSIST=0; STREAM with a 16-bit epilogue or the RESIDUAL planes producer, SCHED 0, one batch, not TN, no probe): a one-dimensional grid
 // of G = min(tiles, CUs rounded down to a multiple of 8) workgroups; workgroup b computes output tiles b, b + G, b + 2 G, ... (a tile index maps to (tm, tn)
 // by the XCD / GROUP_M formula with the tile count in place of the grid size; G % 8 == 0 keeps every tile on the XCD it has today).  The K loop runs on
 // across output tiles: the last K tile of a tile, whose LDS-DMA slots are empty otherwise, requests all 16 pieces of K tile 0 of the workgroup's NEXT tile
@@ -123,8 +125,9 @@ gemm_4w16_kernel(const T* __restrict__ A, long lda, const T* __restrict__ W, lon
     const int l15 = lane & 15, kb = lane >> 4;
     const int l31 = lane & 31, hi = lane >> 5;      // read-back of the staged tile (row-wise, as in gemm_4w64.h)
 
-    static_assert(!PERSIST || (STREAM && !TN && P3 >= 0 && PRL + PRS == 0 && (EPI == AMDS_EPI_BIAS || EPI == AMDS_EPI_BIAS_GELU || EPI == AMDS_EPI_BIAS_RELU)),
-                  "gemm_4w16: the persistent form is the streamed 16-bit epilogue on SCHED 0");
+    static_assert(!PERSIST || (STREAM && !TN && P3 >= 0 && PRL + PRS == 0 &&
+                               (EPI == AMDS_EPI_BIAS || EPI == AMDS_EPI_BIAS_GELU || EPI == AMDS_EPI_BIAS_RELU || EPI == AMDS_EPI_RESIDUAL)),
+                  "gemm_4w16: the persistent form is a streamed epilogue on SCHED 0");
     int tm, tn;
     auto tile_of = [&](int bid, int nwg, int& tm_, int& tn_) {
         const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
@@ -582,6 +585,184 @@ next_tile:
         }
         return;
     }
+    if constexpr (EPI == AMDS_EPI_RESIDUAL && STREAM) {
+        // Streamed residual epilogue on the two fp16 planes (the host launches this instantiation only for ep.xh && ep.xl && ep.rowpart, acc_scale == 1, one
+        // batch: amds_gemm_lnfold_planes).  The one-phase form below stages 64 columns of all four quadrants, crosses a workgroup barrier, lets every wave
+        // update 64 whole rows, and does that twice: every wave's loads, value math and stores come in the same four bursts.  Here every wave drains its own
+        // 128 x 128 quadrant in eight steps of one 16-row block row, with no workgroup barrier in front of the last store:
+        //   write   32 accumulators per lane (x LayerScale) as fp32 into a wave-private slab of 16 rows x 512 B (two slabs of 8 KB per wave = one stage);
+        //   read    the slab back row-wise: 8 ds_read_b128, lane (l31, hi) gets 4 columns of rows 2 u + hi, u = 0..7 (32 lanes = one row's 128 columns);
+        //   add     the old value hi + lo of the same 4 columns (two buffer_load_dwordx2, requested TWO steps earlier: the loads of step s + 1 are issued
+        //           before the stores of step s - 1, so three steps' old values -- 96 registers -- are in flight or in use);
+        //   store   the new hi and lo (two buffer_store_dwordx2): the same operations in the same order on every element as the one-phase form -- same bits.
+        // All waits are the compiler's (an older load counted past younger loads and stores; loads and stores are plain buffer builtins it can see).
+        // Slab image: 16-byte chunk c (4 columns) of row r sits at chunk c ^ r (r < 16: bit 4 of c, the 64-column half, stays).  Writes (ds_write_b128,
+        //   8 contiguous lanes = 8 rows of one chunk, banks of 128 B): 8 distinct slots; reads (16 lanes of one row, consecutive chunks): 16 distinct slots.
+        // Rows past M lie beyond num_records of the plane descriptors: their loads return 0 and their stores are dropped (all of the offset is in the VGPR).
+        // Row sums: slot rowpart[row][tn * 2 + p] sums columns [64 p, 64 p + 64) of BOTH 128-column halves of the tile, i.e. of two waves.  A DPP row of 16
+        //   lanes holds exactly one (hi, p) of the read-back, so row16_sum8 reduces each wave's 64 columns in registers (fixed tree, invariant under the
+        //   slab's chunk XOR); the two waves' halves meet in 8 KB of LDS behind both stages ([row][p][wn] pairs), are added as (wn 0) + (wn 1) behind the
+        //   ONE barrier that ends the tile and leave as 8-byte stores.  No atomics; the order of additions is fixed.
+        static_assert(std::is_same<T, f16>::value && !TN && PRL + PRS == 0, "gemm_4w16: the streamed residual epilogue is the fp16 planes producer");
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0), in the compiler's sight: no LDS-DMA is outstanding when the first slab write is placed
+        __builtin_amdgcn_sched_barrier(0);
+        const int rows_o = min(BM, M - m0);
+        int ldo2 = (int)ep.ldo * 2;
+        if constexpr (PERSIST) asm volatile("" : "+s"(ldo2));      // (the 8 lane offsets below are formed per tile, not carried through the K loop)
+        const __amdgpu_buffer_rsrc_t rsrc_h = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<T*>(ep.xh) + (long)m0 * ep.ldo + n0, 0,
+                                                                                (int)((((long)rows_o - 1) * ep.ldo + BN) * 2), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc_l = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<T*>(ep.xl) + (long)m0 * ep.ldo + n0, 0,
+                                                                                (int)((((long)rows_o - 1) * ep.ldo + BN) * 2), 0x00020000);
+        char* slab = smem + (PERSIST ? ((nk - 1 + par) & 1) * STAGE : 0) + wave * 16384;      // PERSIST: in the stage of the last K tile
+        float* part = reinterpret_cast<float*>(smem + 2 * STAGE);            // [256 rows][2 column parts][2 halves wn] x (sum, sum of squares)
+        int wr_base = l15 * 512;
+        int rd_base = hi * 512 + l31 * 16;
+        if constexpr (PERSIST) asm volatile("" : "+v"(wr_base), "+v"(rd_base));      // (formed per tile: hoisted, the derived addresses would live through the K loop)
+        int offp[8];            // byte offset of row wm*128 + 2 u + hi, columns wn*128 + 4 chunk .. + 3 in a plane; chunk = l31 ^ (2 u + hi) on its low 4 bits
+#pragma unroll
+        for (int u = 0; u < 8; ++u) offp[u] = (wm * 128 + 2 * u + hi) * ldo2 + wn * 256 + ((l31 ^ (2 * u + hi)) << 3);
+        const int np_part = N / 128;
+        auto run = [&](auto has_scale_c) {
+            constexpr bool HS = decltype(has_scale_c)::value;
+            f32x4 sc[HS ? FJ : 1];
+            if constexpr (HS) {
+#pragma unroll
+                for (int j = 0; j < FJ; ++j) sc[j] = *reinterpret_cast<const f32x4*>(ep.scale + n0 + wn * 128 + j * 16 + 4 * kb);
+            }
+            // PERSIST: the next tile's accumulator-initial bias.  Three steps' old values leave no room for it at the start of the epilogue (scratch): it is
+            // requested in step FI - 1, into the registers the old values of step FI - 3 have left, in front of the stores of the last two block rows --
+            // the counted wait for it behind the epilogue leaves those 32 stores per lane in flight
+            f32x4 b0n[PERSIST ? FJ : 1];
+            u32x4 prev[3][8];       // old (hi.x, hi.y, lo.x, lo.y) of step s in prev[s % 3]
+            auto load_prev = [&](int s) {
+                int rowoff = s * 16 * ldo2;
+                asm volatile("" : "+s"(rowoff));          // keep the 8 lane offsets, not 64 sums, in registers
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const u32x2 ph = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rsrc_h, offp[u] + rowoff, 0, 0));
+                    const u32x2 pl = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rsrc_l, offp[u] + rowoff, 0, 0));
+                    prev[s % 3][u] = u32x4{ph[0], ph[1], pl[0], pl[1]};
+                }
+            };
+            load_prev(0);
+            load_prev(1);
+            f32x4 v[8];
+#pragma unroll
+            for (int s = 0; s <= FI; ++s) {
+                if (s < FI) {
+                    char* wp = slab + (s & 1) * 8192 + wr_base;
+#pragma unroll
+                    for (int j = 0; j < FJ; ++j) {
+                        f32x4 a = agpr_read(acc[s][j]);
+                        if constexpr (HS) a *= sc[j];
+                        *reinterpret_cast<f32x4*>(wp + (((j * 4 + kb) ^ l15) << 4)) = a;
+                    }
+                    if (s >= 1 && s + 1 < FI) load_prev(s + 1);     // into the registers step s - 2 has left; the stores of step s - 1 follow below
+                    if constexpr (PERSIST) {
+                        if (s == FI - 1) {
+#pragma unroll
+                            for (int j = 0; j < FJ; ++j) b0n[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+                            if (bias_in_acc) {
+#pragma unroll
+                                for (int j = 0; j < FJ; ++j) b0n[j] = *reinterpret_cast<const f32x4*>(ep.bias + n0n + wn * 128 + j * 16 + 4 * kb);
+                            }
+                        }
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                if (s > 0) {                              // block row s - 1: read back below in the previous round
+                    const int t = s - 1;
+                    int rowoff = t * 16 * ldo2;
+                    asm volatile("" : "+s"(rowoff));
+                    f32x2 ss[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const u32x4 o = prev[t % 3][u];
+                        const f32x4 old4 = f32x4{mix_add_hh<0, 0>(o[0], o[2]), mix_add_hh<1, 1>(o[0], o[2]), mix_add_hh<0, 0>(o[1], o[3]), mix_add_hh<1, 1>(o[1], o[3])};
+                        v[u] += old4;
+                        const vec4 c = Act<T>::from_f32x4(v[u]);
+                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, c), rsrc_h, offp[u] + rowoff, 0, 0);
+                        const u32x2 cu = __builtin_bit_cast(u32x2, c);
+                        const f32x4 rest = f32x4{mix_sub_fh<0>(v[u][0], cu[0]), mix_sub_fh<1>(v[u][1], cu[0]), mix_sub_fh<0>(v[u][2], cu[1]), mix_sub_fh<1>(v[u][3], cu[1])};
+                        const vec4 cl = Act<T>::from_f32x4(rest);
+                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, cl), rsrc_l, offp[u] + rowoff, 0, 0);
+                        ss[u] = f32x2{(v[u][0] + v[u][1]) + (v[u][2] + v[u][3]),
+                                      fmaf(v[u][0], v[u][0], v[u][1] * v[u][1]) + fmaf(v[u][2], v[u][2], v[u][3] * v[u][3])};
+                    }
+                    const f32x2 tot = row16_sum8(ss, lane);          // row u = 4 bit3 + 2 bit2 + bit0 of the lane, over the 16 lanes of (hi, column part)
+                    const int urow = ((lane >> 3) & 1) * 4 + ((lane >> 2) & 1) * 2 + (lane & 1);
+                    const int prow = wm * 128 + t * 16 + 2 * urow + hi;
+                    if ((lane & 2) == 0) *reinterpret_cast<f32x2*>(part + ((prow * 2 + ((lane >> 4) & 1)) * 2 + wn) * 2) = tot;
+                }
+                if (s < FI) {
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // (no code: the lanes of a wave exchange data through the slab)
+                    __builtin_amdgcn_wave_barrier();
+                    const char* rp = slab + (s & 1) * 8192 + rd_base;
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const f32x4*>(rp + u * 1024);
+                    __builtin_amdgcn_wave_barrier();
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if constexpr (PERSIST) {        // the next tile's accumulators, written behind the epilogue's last reads of them
+#pragma unroll
+                for (int i = 0; i < FI; ++i)
+#pragma unroll
+                    for (int j = 0; j < FJ; ++j) acc[i][j] = b0n[PERSIST ? j : 0];
+            }
+        };
+        if (ep.scale) run(std::true_type{}); else run(std::false_type{});
+        if constexpr (PERSIST) {            // pinned and padded like the first tile's
+#pragma unroll
+            for (int i = 0; i < FI; ++i) {
+                if (i == FI - 1)
+                    asm volatile("s_nop 7" : "+a"(acc[i][0]), "+a"(acc[i][1]), "+a"(acc[i][2]), "+a"(acc[i][3]), "+a"(acc[i][4]), "+a"(acc[i][5]),
+                                 "+a"(acc[i][6]), "+a"(acc[i][7]));
+                else
+                    asm volatile("" : "+a"(acc[i][0]), "+a"(acc[i][1]), "+a"(acc[i][2]), "+a"(acc[i][3]), "+a"(acc[i][4]), "+a"(acc[i][5]),
+                                 "+a"(acc[i][6]), "+a"(acc[i][7]));
+            }
+        }
+        // the two halves of every slot: raw s_barrier, not __syncthreads() -- its fence would wait for the stores in flight.  PERSIST: this is also the
+        // one barrier per tile of hazard 1 (no wave requests into the slab stage before every wave has read its slabs back); the next tile's epilogue
+        // writes `part` again at least one K-tile barrier behind these reads
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int idx = e * NT + tid, row = idx >> 1;
+            const f32x4 p4 = *reinterpret_cast<const f32x4*>(part + idx * 4);
+            if (m0 + row < M)
+                *reinterpret_cast<f32x2*>(ep.rowpart + ((long)(m0 + row) * np_part + tn * 2 + (idx & 1)) * 2) = f32x2{p4[0] + p4[2], p4[1] + p4[3]};
+        }
+        if constexpr (PERSIST) {
+            AMDS_GEMM_STAMP(3);
+            AMDS_GEMM_TRACE_WRITE();
+            if (!has_next) return;
+            ti += (int)gridDim.x;
+            tn = n0n / BN;
+            m0 = m0n;
+            n0 = n0n;
+            rsrc_a = rsrc_an;
+            rsrc_w = rsrc_wn;
+            par = (par + nk) & 1;
+            AMDS_GEMM_STAMP(0);
+            AMDS_GEMM_STAMP(1);
+            load_frags(0, 0, 0, 0, 16);         // hazard 2: one phase behind the wait that retired the prefetch
+            if (nk > 1) issue_pieces(1, 0, Q3);
+            __builtin_amdgcn_sched_barrier(0);
+            goto next_tile;
+        }
+#ifdef AMDS_GEMM_TRACE
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // as in the one-phase form: the exit stamp is taken when the last store has completed
+#endif
+        AMDS_GEMM_STAMP(3);
+        AMDS_GEMM_TRACE_WRITE();
+        return;
+    }
     if constexpr (EPI == AMDS_EPI_RESIDUAL) {
         // Fast read-modify-write (bias already in the accumulators or absent, acc_scale == 1 -- every call of the tile encoder).
         // The OLD values of a whole pass (this wave's 64 rows x 128 columns = 32 x 16 bytes per lane) are requested BEFORE the
@@ -731,6 +912,11 @@ next_tile:
             } else {
                 if (ep.scale) run(std::true_type{}, std::false_type{}, std::false_type{}); else run(std::false_type{}, std::false_type{}, std::false_type{});
             }
+#ifdef AMDS_GEMM_TRACE
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the exit stamp of this form is taken when its last store has completed
+#endif
+            AMDS_GEMM_STAMP(3);
+            AMDS_GEMM_TRACE_WRITE();
             return;
         }
     }
@@ -992,18 +1178,23 @@ static int launch_gemm_4w16(const void* A, long lda, const void* W, long ldw, in
     if constexpr (!epi_is_staged<EPI>() && EPI != AMDS_EPI_SWIGLU) {
         return launch_gemm_4w64<T, EPI>(A, lda, W, ldw, M, N, K, ep, st);
     } else {
-        constexpr int LDS = 2 * (256 + 256) * 128;
-        // (only the 16-bit-output epilogues have a streamed form: every other epilogue has one instantiation)
+        // (only the 16-bit-output epilogues and the RESIDUAL producer on two fp16 planes have a streamed form: every other epilogue has one instantiation)
         constexpr bool STR = STREAM && (EPI == AMDS_EPI_BIAS || EPI == AMDS_EPI_BIAS_GELU || EPI == AMDS_EPI_BIAS_RELU);
+        constexpr bool RSTR = STREAM && EPI == AMDS_EPI_RESIDUAL && std::is_same<T, f16>::value && !TN && P3 >= 0 && PRL + PRS == 0;
+        constexpr int LDS = 2 * (256 + 256) * 128 + (RSTR ? 8192 : 0);      // RSTR: the two halves of the row sums meet behind the stages
+        if constexpr (RSTR) {               // the planes producer of the tile encoder; bf16, fp32 rows and the 16-bit copy keep the one-phase form
+            if (!(ep.xh && ep.xl && ep.rowpart && ep.acc_scale == 1.0f && ep.rowstat == nullptr && ep.nbatch == 1 && ep.ldo * 512 < (1L << 31)))
+                return launch_gemm_4w16<T, EPI, SPREAD, P3, P0, PRL, PRS, false, false, TN>(A, lda, W, ldw, M, N, K, ep, st);
+        }
         if constexpr (STR) {                // the streamed epilogue addresses a tile's 256 output rows with 32-bit byte offsets; the one-phase form has no such limit
             if (ep.ldo * 512 >= (1L << 31)) return launch_gemm_4w16<T, EPI, SPREAD, P3, P0, PRL, PRS, false, false, TN>(A, lda, W, ldw, M, N, K, ep, st);
         }
-        // the persistent form: streamed 16-bit epilogue on SCHED 0, one batch (everything else keeps one tile per workgroup)
-        constexpr bool PER = PERSIST && STR && !TN && P3 >= 0 && PRL + PRS == 0;
+        // the persistent form: a streamed epilogue (16-bit, or RESIDUAL on the planes) on SCHED 0, one batch (everything else keeps one tile per workgroup)
+        constexpr bool PER = PERSIST && (STR || RSTR) && !TN && P3 >= 0 && PRL + PRS == 0;
         if constexpr (PER) {
             if (ep.nbatch != 1) return launch_gemm_4w16<T, EPI, SPREAD, P3, P0, PRL, PRS, STREAM, false, TN>(A, lda, W, ldw, M, N, K, ep, st);
         }
-        constexpr auto kern = gemm_4w16_kernel<T, EPI, P3, P0, SPREAD, PRL, PRS, STR, PER, TN>;
+        constexpr auto kern = gemm_4w16_kernel<T, EPI, P3, P0, SPREAD, PRL, PRS, STR || RSTR, PER, TN>;
         EpiArgs epp = ep;
         if constexpr (PRL + PRS > 0) {      // probe scratch: one region per workgroup, never read by anything real
             static char* scratch = nullptr;

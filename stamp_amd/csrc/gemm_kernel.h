@@ -425,6 +425,17 @@ static inline bool gemm_epi_stream() {
     const char* e = getenv("AMDS_GEMM_EPI_STREAM");
     return !(e && *e && atoi(e) == 0);
 }
+// AMDS_GEMM_RESID_STREAM=0: the one-phase RESIDUAL epilogue on the two fp16 planes (amds_gemm_lnfold_planes) instead of the streamed one (A/B; read at every call)
+static inline bool gemm_resid_stream() {
+    const char* e = getenv("AMDS_GEMM_RESID_STREAM");
+    return !(e && *e && atoi(e) == 0);
+}
+// AMDS_GEMM_RESID_PERSIST=0: the streamed RESIDUAL epilogue keeps one output tile per workgroup while the 16-bit epilogues stay persistent (A/B of the two
+// steps separately; read at every call).  AMDS_GEMM_PERSIST=0 turns every persistent form off, this one included.
+static inline bool gemm_resid_persist() {
+    const char* e = getenv("AMDS_GEMM_RESID_PERSIST");
+    return !(e && *e && atoi(e) == 0);
+}
 inline std::atomic<long> g_gemm_persist_launches{0};      // launches of a persistent instantiation by this process (amds_gemm_persist_launches)
 // AMDS_GEMM_PERSIST=0: kernel id 12 keeps one output tile per workgroup where its persistent form (id 16) would run (A/B; read at every call)
 static inline bool gemm_persist() {
@@ -442,6 +453,10 @@ static inline bool gemm_persist() {
 //       16 = id 12 in its persistent form wherever that exists (gemm_4w16.h PERSIST: streamed 16-bit epilogue, one batch): min(tiles, CUs) workgroups walk
 //       the output tiles and prefetch the next tile's first operands under the epilogue; same bits as 12.  Id 12 itself runs that form unless
 //       AMDS_GEMM_PERSIST=0 (read at every call); AMDS_GEMM_EPI_STREAM=0 implies the one-tile form; AMDS_GEMM_PERSIST_WGS=<n> caps the grid (tests, A/B)
+//       RESIDUAL on two fp16 planes (amds_gemm_lnfold_planes, f16): ids 12 / 16 run the streamed residual epilogue of gemm_4w16.h, in the persistent tile walk
+//       like the 16-bit epilogues (id 16 always, id 12 unless AMDS_GEMM_PERSIST=0 or AMDS_GEMM_RESID_PERSIST=0), unless AMDS_GEMM_RESID_STREAM=0 (all read at
+//       every call); ids 13 / 14, bf16, fp32 rows and the 16-bit copy keep the one-phase form.  (The entry takes no kernel id: its forms are chosen by these
+//       switches, tools/gemm_sched_ab.py `planes` times all three.)
 //   8 = 256x256x64 eight-wave staggered two-group pipeline (gemm_8p64.h): the PATCH epilogue, batched fallback
 //  10 = the four-wave structure on v_mfma 32x32x16 (gemm_4w64.h): the one A/B sibling kept
 // (the BK = 32 predecessors 3 / 7 and the ping-pong experiment 9 of round 1 were removed; their measurements stay in profiles/r01_*)
@@ -451,13 +466,13 @@ static int launch_gemm(int cfg, const void* A, long lda, const void* W, long ldw
     if (cfg == 10 && N % 256 == 0 && ep.nbatch == 1) return launch_gemm_4w64<T, EPI>(A, lda, W, ldw, M, N, K, ep, st);
     if (cfg == 10) cfg = 8;
     if ((cfg == 12 || cfg == 13 || cfg == 14 || cfg == 16) && N % 256 == 0) {
-        const bool stream = cfg != 14 && gemm_epi_stream();
+        const bool stream = cfg != 14 && (EPI == AMDS_EPI_RESIDUAL ? gemm_resid_stream() : gemm_epi_stream());
         if (cfg == 13) {
             if (stream) return launch_gemm_4w16<T, EPI, true, -2, 0, 0, 0, true, false, false>(A, lda, W, ldw, M, N, K, ep, st);
             return launch_gemm_4w16<T, EPI, true, -2, 0, 0, 0, false, false, false>(A, lda, W, ldw, M, N, K, ep, st);
         }
-        if constexpr (EPI == AMDS_EPI_BIAS || EPI == AMDS_EPI_BIAS_GELU || EPI == AMDS_EPI_BIAS_RELU) {
-            if (stream && (cfg == 16 || gemm_persist())) return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 0, true, true, false>(A, lda, W, ldw, M, N, K, ep, st);
+        if constexpr (EPI == AMDS_EPI_BIAS || EPI == AMDS_EPI_BIAS_GELU || EPI == AMDS_EPI_BIAS_RELU || EPI == AMDS_EPI_RESIDUAL) {
+            if (stream && (cfg == 16 || (gemm_persist() && (EPI != AMDS_EPI_RESIDUAL || gemm_resid_persist())))) return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 0, true, true, false>(A, lda, W, ldw, M, N, K, ep, st);
         }
         if (stream) return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 0, true, false, false>(A, lda, W, ldw, M, N, K, ep, st);
         return launch_gemm_4w16<T, EPI, true, 6, 6, 0, 0, false, false, false>(A, lda, W, ldw, M, N, K, ep, st);

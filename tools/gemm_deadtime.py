@@ -10,7 +10,12 @@ median and p90 of
     (a) last MFMA -> exit of a workgroup          (b) exit of workgroup i -> K tile 0 landed of workgroup i + 1
   persistent (kernel id 16), successive tiles of a workgroup:
     (a') last MFMA -> the epilogue's last store issued          (c) last MFMA of tile i -> first fragment read of tile i + 1 (= (a) + (b) of this form)
+For the RESIDUAL planes launch (amds_gemm_lnfold_planes: proj N 1024 K 1024, fc2 N 1024 K 4096, LayerScale, one tile per workgroup; `resid` as the
+second argument runs only these; AMDS_GEMM_RESID_STREAM=0 in the environment for the one-phase epilogue) the exit stamp is taken when the tile's last store
+has COMPLETED, and besides (a) and (b) this prints
+    (s) the spread of the epilogue's start (last MFMA, on the 100 MHz s_memrealtime clock all XCDs share) across the CUs of one round of tiles.
 The stamps are scalar-memory clock reads kept in registers and written once per tile; a TRACE build is never the product."""
+import ctypes
 import os
 import sys
 from pathlib import Path
@@ -23,6 +28,9 @@ from stamp_amd import _lib, ops  # noqa: E402
 
 M = int(sys.argv[1]) if len(sys.argv) > 1 else 262140
 SHAPES = (("qkv", 3072, 1024, _lib.EPI_BIAS), ("fc1", 4096, 1024, _lib.EPI_BIAS_GELU))
+RESID_SHAPES = (("proj", 1024, 1024), ("fc2", 1024, 4096))
+if len(sys.argv) > 2 and sys.argv[2] == "resid":
+    SHAPES = ()
 
 
 def records(cfg, a, w, b, epi, persist):
@@ -85,3 +93,51 @@ for name, N, K, epi in SHAPES:
     print(f"    (c) last MFMA -> first read of the next tile  {stats(c)}")
     print(f"    whole tile, first read -> first read          {stats((rr[:, 1:, 1].astype(np.int64) - rr[:, :-1, 1].astype(np.int64))[ok].astype(np.float64) * us)}")
     del a, w, b
+
+
+def resid_records(a, w, hi, lo, b, sc):
+    tiles = -(-a.shape[0] // 256) * (w.shape[0] // 256)
+    buf = torch.zeros(tiles * 8 + 2048 * 8, dtype=torch.int64, device="cuda")
+    set_buf = _lib.lib().amds_gemm_trace_buffer          # TRACE builds only
+    set_buf.restype, set_buf.argtypes = None, [ctypes.c_void_p]
+    for _ in range(20):
+        ops.gemm_lnfold_planes(a, w, hi, lo, bias=b, scale=sc)
+    set_buf(buf.data_ptr())
+    ops.gemm_lnfold_planes(a, w, hi, lo, bias=b, scale=sc)
+    torch.cuda.synchronize()
+    set_buf(None)
+    r = buf.cpu().numpy().astype(np.uint64).reshape(-1, 8)
+    return r[r[:, 0] != 0]
+
+
+for name, N, K in RESID_SHAPES:
+    a = torch.randn(M, K, device="cuda").half()
+    w = (torch.randn(N, K, device="cuda") / K ** 0.5).half()
+    b = torch.randn(N, device="cuda")
+    sc = torch.full((N,), 0.1, device="cuda")
+    hi, lo, _ = ops.ln_stats_split(torch.randn(M, N, device="cuda"), 1e-6)
+    form = "one-phase" if os.environ.get("AMDS_GEMM_RESID_STREAM", "1") == "0" else "streamed"
+    print(f"{name}: M={M} N={N} K={K}  RESIDUAL on two fp16 planes, LayerScale, {form} epilogue")
+    os.environ["AMDS_GEMM_RESID_PERSIST"] = "0"          # one tile per workgroup: the pairing below is by CU
+    r = resid_records(a, w, hi, lo, b, sc)
+    mhz = float(np.median((r[:, 3] - r[:, 0]).astype(np.float64) / np.maximum((r[:, 7] - r[:, 6]).astype(np.float64), 1.0))) * 100.0
+    us = 1.0 / mhz
+    cu = (r[:, 4] >> np.uint64(8)) & np.uint64(0xFF) | ((r[:, 4] >> np.uint64(32)) & np.uint64(0xF)) << np.uint64(8)
+    a_int, b_int, starts = [], [], {}
+    for key in np.unique(cu):
+        q = r[cu == key]
+        q = q[np.argsort(q[:, 0])]
+        epi = (q[:, 3] - q[:, 2]).astype(np.float64) * us
+        a_int += list(epi)
+        b_int += list((q[1:, 1].astype(np.int64) - q[:-1, 3].astype(np.int64)).astype(np.float64) * us)
+        for rnd, t in enumerate(q[:, 7].astype(np.float64) * 0.01 - epi):      # exit on the shared clock, less the epilogue
+            starts.setdefault(rnd, []).append(t)
+    full = [np.array(v) for v in starts.values() if len(v) == len(np.unique(cu))]
+    print(f"  one tile per workgroup ({len(r)} workgroups on {len(np.unique(cu))} CUs, {mhz:.0f} MHz in the kernel)")
+    print(f"    (a) last MFMA -> last store completed          {stats(np.array(a_int))}")
+    print(f"    (b) exit -> K tile 0 of the next workgroup    {stats(np.array(b_int))}")
+    print(f"    K loop, K tile 0 landed -> last MFMA          {stats((r[:, 2] - r[:, 1]).astype(np.float64) * us)}")
+    print(f"    whole tile, entry -> exit                     {stats((r[:, 3] - r[:, 0]).astype(np.float64) * us)}")
+    print(f"    (s) epilogue start over the CUs of a round: p90 - p10 {stats(np.array([np.percentile(v, 90) - np.percentile(v, 10) for v in full]))}")
+    print(f"        max - min                                        {stats(np.array([v.max() - v.min() for v in full]))}")
+    del a, w, b, hi, lo
