@@ -1039,6 +1039,37 @@ int amds_softmax_over_tiles(const float* in, float* out, int classes, long n, vo
 int amds_scatter_grid(const float* vals, const int64_t* xy, float* out, int* cell_ws, long n, int k, int h, int w, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Rank metrics: exact pair counts of the concordance statistic.  Items i have a risk score_i (higher = worse), a time_i and an event_i in {0, 1}.  The
+ * ordered pair (i, j) is PERMISSIBLE when event_i == 1 and (time_i < time_j or (time_i == time_j and event_j == 0)); a permissible pair is CONCORDANT when
+ * score_i > score_j and TIED when score_i == score_j; C = (concordant + tied / 2) / permissible.  This is the number the reference selects every survival
+ * run on -- `val_cindex`, mode max (src/stamp/modeling/train.py:521-540), computed over the WHOLE validation set by `LitSurvivalBase.on_validation_epoch_end`
+ * (src/stamp/modeling/models/__init__.py:696-715) through `c_index` (:662-694) = lifelines.utils.concordance_index(time, -score, event), also
+ * src/stamp/statistics/survival.py:32.  With event = (y == c), time = (y != c), score = p[:, c] the permissible pairs are the (positive, negative) pairs and
+ * C is the one-vs-rest AUROC `roc_auc_score(y == c, p[:, c])` (src/stamp/statistics/categorical.py:65-68; logged per classification run,
+ * models/__init__.py:217, 270-277).  Batched over problems: the reference's intervals are 1000 bootstrap resamples of the statistic
+ * (src/stamp/statistics/roc.py:161-214).
+ *
+ * score: fp32, item k of problem p at score[p * score_problem_stride + k * score_item_stride] (elements; the classes of a row-major [n][C] probability
+ * matrix are C problems with item stride C, problem stride 1).  time fp32 / event u8: item k of problem p at [p * problem_stride + k]; a problem stride 0
+ * shares one array between the problems.  idx (may be NULL): int32 [n_problems][n_items]; problem p then is the MULTISET of items idx[p][0..n_items) of ONE
+ * base problem of n_base items (problem 0 of the three arrays; the problem strides are not used) -- bootstrap resamples; a duplicated item is two items.
+ * counts: int64 [n_problems][4] = {concordant, tied, permissible, valid items}.  An item whose score or time is NaN, or whose event byte is neither 0 nor 1,
+ * is INVALID: it takes part in no pair.  Compares are fp32's (-0 == +0, denormals kept).
+ *
+ * Exact and bitwise reproducible: integer counts, no atomics -- one workgroup holds 256 i items in registers and streams a chunk of the j items through LDS
+ * (with idx each tile is gathered once), workgroups store partial counts to `ws`, a second launch sums them in a fixed order; no N x N tensor.
+ * 1 <= n_items < 2^31 (counts < 2^62), n_problems >= 1, score_item_stride >= 1, problem strides >= 0 (AMDS_ERR_INVALID otherwise, also for a NULL pointer
+ * or a `ws` not 256-byte aligned); ws_bytes < amds_concordance_workspace_bytes -> AMDS_ERR_WORKSPACE (the size is 0 for a bad shape).  An index outside
+ * [0, n_base) is never dereferenced (the item is invalid); the call counts them, and ONLY with idx it SYNCHRONISES `stream` (one 8-byte read) and returns
+ * AMDS_ERR_INVALID if there was one (`counts` is then unspecified).  Without idx: launches only, on `stream`. */
+size_t amds_concordance_workspace_bytes(long n_items, int n_problems);
+int amds_concordance_counts(const float* score, long score_item_stride, long score_problem_stride, const float* time, long time_problem_stride,
+                            const uint8_t* event, long event_problem_stride, const int32_t* idx, long n_base, long n_items, int n_problems, int64_t* counts,
+                            void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_concordance_workspace_bytes) and `counts` is written. */
+
+/* ------------------------------------------------------------------------------------------------
  * barspoon head, deploy / validation forward as one call (reference src/stamp/modeling/models/barspoon.py:27-205
  * `EncDecTransformer` in eval mode: projector, sinusoidal position encoding, pre-norm transformer encoder over the tiles, one class
  * token per target decoded against the tiles by a pre-norm transformer decoder, one Linear head per target)

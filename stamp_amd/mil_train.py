@@ -17,7 +17,8 @@ Mirrors what `stamp train` does for tile-level models:
   `sched_interval="step"` is the per-step OneCycle the schedule's size suggests was intended (SURVEY.md 8c);
 * epochs -- src/stamp/modeling/train.py:504-564: validation after every epoch (the caller's validation loader: full bags,
   batch size 1, :467-477), early stopping with `patience` on the validation loss (mode min), the best epoch's weights restored
-  at the end (`shutil.copy(best_model_path)` + reload).
+  at the end (`shutil.copy(best_model_path)` + reload).  Survival runs are monitored on `val_cindex`, mode max, instead (train.py:521-540):
+  `fit(monitor="val_cindex")`, computed over the whole validation set by `stamp_amd.metrics`.
 
 Mixed precision (stated, not hidden): 16-bit MFMA operands for activations, weights and gradients, fp32 accumulation, fp32 residual
 stream and its gradient, fp32 LayerNorm / softmax statistics, fp32 master weights, gradients and Adam moments.  WHICH 16-bit type
@@ -38,10 +39,12 @@ The loss on the [batch, classes] logits is the one tiny piece left to torch (SUR
 """
 from __future__ import annotations
 
+import math
+
 import torch
 import torch.nn.functional as F
 
-from . import mil_core
+from . import losses, metrics, mil_core
 from . import train_ops as T
 from .distributed import average_buffers, average_gradients
 from .mil import VisionTransformer
@@ -326,10 +329,11 @@ def _valid_loss(lg, targets, dev, class_weights, loss_fn):
     return loss_fn(lg, targets.to(dev))
 
 
-def _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, per_call: int) -> tuple[float, int]:
+def _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, per_call: int, keep: list | None = None, with_loss: bool = True) -> tuple[float, int]:
     """The validation sum of `fit` with consecutive one-bag batches run `per_call` at a time through `predict_ragged` (mil_core.group_bags decides the
     groups): each batch's loss comes from its own logits row(s) exactly as in the one-bag loop, the group's losses reach the host in one read, and the
-    sum runs in batch order.  Batches of several bags keep the one-call `predict` of the default loop."""
+    sum runs in batch order.  Batches of several bags keep the one-call `predict` of the default loop.
+    keep: a list that receives every batch's (logits, targets) in batch order, both left on the device; with_loss=False: no per-batch loss and no host read."""
     vtot, vcnt = 0.0, 0
     pend: list = []
 
@@ -351,8 +355,11 @@ def _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, per_ca
         losses = []
         for i, (bags, coords, targets) in enumerate(pend):
             lg = rows[i] if i in rows else trainer.predict(bags.to(dev), None if coords is None else coords.to(dev))
-            losses.append(_valid_loss(lg, targets, dev, class_weights, loss_fn).reshape(()))
-        for (bags, _c, _t), v in zip(pend, torch.stack(losses).tolist()):
+            if keep is not None:
+                keep.append((lg, targets.to(dev)))
+            if with_loss:
+                losses.append(_valid_loss(lg, targets, dev, class_weights, loss_fn).reshape(()))
+        for (bags, _c, _t), v in zip(pend, torch.stack(losses).tolist() if losses else ()):
             vtot += float(v) * bags.shape[0]
             vcnt += bags.shape[0]
         pend.clear()
@@ -366,7 +373,7 @@ def _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, per_ca
 
 
 def fit(trainer: HipMilVitTrainer, train_batches, valid_batches, *, max_epochs: int, patience: int = 16, class_weights=None,
-        loss_fn=None, log=None, valid_bags_per_call: int = 1) -> dict:
+        loss_fn=None, log=None, valid_bags_per_call: int = 1, monitor: str = "validation_loss", valid_auroc: bool = False) -> dict:
     """The epoch loop of the reference's `train_model_` (src/stamp/modeling/train.py:504-564) around `HipMilVitTrainer.step`.
 
     train_batches / valid_batches: callables returning an iterable of (bags, coords, bag_sizes, targets) per epoch -- the
@@ -377,23 +384,56 @@ def fit(trainer: HipMilVitTrainer, train_batches, valid_batches, *, max_epochs: 
     it).  `num_sanity_val_steps=0` like the reference.  Returns the history; `skipped_steps` holds the optimiser steps per epoch the dynamic
     loss scale skipped (fp16 gradients not finite), and `log` is warned about each epoch that skipped any.
     valid_bags_per_call > 1: consecutive one-bag validation batches run that many at a time through ONE ragged call (`predict_ragged`), with one host
-    read of their losses per call instead of one per bag; the losses, and so the history and the restored epoch, are those of the default loop."""
+    read of their losses per call instead of one per bag; the losses, and so the history and the restored epoch, are those of the default loop.
+
+    monitor="val_cindex" -- what the reference monitors for EVERY survival run, mode max, for early stopping and for the kept checkpoint (train.py:521-540);
+    targets are [time, event], dim_output 1.  The per-batch validation loss is not evaluated (on the reference's one-bag validation batches the Cox partial
+    likelihood is the score minus the log-sum-exp over that same score: the same value every epoch).  Instead every validation bag's score
+    (``logits.squeeze(-1)``), time and event stay on the device -- through the one-bag loop, batches of several bags and the ragged path alike, no host read per
+    bag -- and after the epoch, as `LitSurvivalBase.on_validation_epoch_end` (models/__init__.py:696-715) does over the WHOLE validation set:
+    ``val_cox_loss = losses.cox_breslow_loss(all)`` and ``val_cindex = metrics.concordance_index(all)`` (exact pair counts, amds_concordance_counts).  The
+    history gains both lists and `validation_loss` holds val_cox_loss.  An epoch improves when its val_cindex is STRICTLY greater (Lightning's `torch.gt` at
+    min_delta 0: the first maximum wins); `patience` counts from the best epoch.  A validation set without any event raises RuntimeError (the reference logs
+    nothing there and Lightning's EarlyStopping raises on the missing val_cindex).  A non-finite val_cindex ends the loop at that epoch (EarlyStopping's
+    check_finite) and the best finite epoch is restored; if no epoch had a finite value the weights of the last trained epoch stay.  Also, as
+    `on_train_epoch_end` (:717-728): `train_pred_median` = torch.median over all training-step scores of the epoch (kept on the device, concatenated once per
+    epoch) goes into hist["train_pred_median"] and, the last epoch's, into `trainer.train_pred_median` -- the cut-off `deploy.to_survival_prediction_df(cut_off=)`
+    takes.  WHICH epoch's median Lightning writes into the kept checkpoint is not reproduced: the history has them all.
+
+    valid_auroc=True (classification, loss_fn=None): hist["validation_auroc"] holds, per epoch, the mean one-vs-rest AUROC
+    ``metrics.multiclass_auroc(softmax(logits), argmax(targets))`` over the validation set (the reference logs it for every classification run,
+    models/__init__.py:217, 270-277); selection is unchanged."""
     if valid_bags_per_call < 1:
         raise ValueError("valid_bags_per_call must be >= 1")
+    if monitor not in ("validation_loss", "val_cindex"):
+        raise ValueError(f"monitor must be 'validation_loss' or 'val_cindex', got {monitor!r}")
+    if valid_auroc and (loss_fn is not None or monitor != "validation_loss"):
+        raise ValueError("valid_auroc=True applies to classification: loss_fn=None, monitor='validation_loss'")
+    cindex = monitor == "val_cindex"
     dev = trainer.dev
-    best = {"loss": float("inf"), "epoch": -1, "P": None}
+    best = {"loss": float("-inf") if cindex else float("inf"), "epoch": -1, "P": None}
     hist = {"train_loss": [], "validation_loss": [], "skipped_steps": [], "best_epoch": -1, "stopped_epoch": None}
+    if cindex:
+        hist.update(val_cox_loss=[], val_cindex=[], train_pred_median=[])
+    if valid_auroc:
+        hist["validation_auroc"] = []
     wait = 0
     skipped = getattr(trainer, "skipped_steps", 0)          # (any object with the trainer's step / predict / epoch_end drives this loop)
     for epoch in range(max_epochs):
         tot, cnt, steps = 0.0, 0, 0
+        train_scores = []
         for bags, coords, _sizes, targets in train_batches():
-            loss, _ = trainer.step(bags.to(dev), targets, class_weights, coords=None if coords is None else coords.to(dev), loss_fn=loss_fn)
+            loss, step_logits = trainer.step(bags.to(dev), targets, class_weights, coords=None if coords is None else coords.to(dev), loss_fn=loss_fn)
+            if cindex:
+                train_scores.append(step_logits.detach().reshape(-1))
             tot += float(loss) * bags.shape[0]
             cnt += bags.shape[0]
             steps += 1
         trainer.epoch_end()
         hist["train_loss"].append(tot / max(cnt, 1))
+        if cindex and train_scores:
+            trainer.train_pred_median = float(torch.cat(train_scores).median())
+            hist["train_pred_median"].append(trainer.train_pred_median)
         now = getattr(trainer, "skipped_steps", 0)
         hist["skipped_steps"].append(now - skipped)
         if log and now > skipped:
@@ -401,10 +441,15 @@ def fit(trainer: HipMilVitTrainer, train_batches, valid_batches, *, max_epochs: 
                 f"loss scale now {trainer.current_loss_scale:g}")
         skipped = now
         vtot, vcnt = 0.0, 0
+        kept = [] if cindex or valid_auroc else None          # every validation batch's (logits, targets), on the device
         if valid_bags_per_call > 1:
-            vtot, vcnt = _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, valid_bags_per_call)
+            vtot, vcnt = _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, valid_bags_per_call, kept, not cindex)
         for bags, coords, _sizes, targets in (valid_batches() if valid_bags_per_call == 1 else ()):
             lg = trainer.predict(bags.to(dev), None if coords is None else coords.to(dev))
+            if kept is not None:
+                kept.append((lg, targets.to(dev)))
+            if cindex:
+                continue
             if loss_fn is None:
                 vl = F.cross_entropy(lg, targets.to(dev, torch.float32), weight=None if class_weights is None else class_weights.to(dev, torch.float32))
             else:
@@ -412,11 +457,27 @@ def fit(trainer: HipMilVitTrainer, train_batches, valid_batches, *, max_epochs: 
             vtot += float(vl) * bags.shape[0]
             vcnt += bags.shape[0]
         vloss = vtot / max(vcnt, 1)
+        if valid_auroc:
+            lg_all, y_all = torch.cat([lg.float() for lg, _ in kept]), torch.cat([t.float() for _, t in kept])
+            hist["validation_auroc"].append(float(metrics.multiclass_auroc(torch.softmax(lg_all, dim=1), y_all.argmax(dim=1))[1]))
+        score = vloss
+        if cindex:
+            y = torch.cat([t.float().reshape(-1, 2) for _, t in kept]) if kept else torch.zeros(0, 2, device=dev)
+            if not bool((y[:, 1] == 1).any()):
+                raise RuntimeError(f"epoch {epoch}: the validation set holds no event, so there is no val_cindex to monitor")
+            s_all = torch.cat([lg.float().reshape(-1) for lg, _ in kept])
+            vloss, score = torch.stack([losses.cox_breslow_loss(s_all, y[:, 0], y[:, 1]).double(),
+                                        metrics.concordance_index(s_all, y[:, 0], y[:, 1]).double()]).tolist()
+            hist["val_cox_loss"].append(vloss)
+            hist["val_cindex"].append(score)
         hist["validation_loss"].append(vloss)
         if log:
-            log(f"epoch {epoch}: train {hist['train_loss'][-1]:.5f} validation {vloss:.5f}")
-        if vloss < best["loss"]:
-            best.update(loss=vloss, epoch=epoch, P=trainer.P.clone())
+            log(f"epoch {epoch}: train {hist['train_loss'][-1]:.5f} validation {vloss:.5f}" + (f" val_cindex {score:.4f}" if cindex else ""))
+        if cindex and not math.isfinite(score):          # EarlyStopping(check_finite=True): the monitored value left the numbers
+            hist["stopped_epoch"] = epoch
+            break
+        if (score > best["loss"]) if cindex else (score < best["loss"]):
+            best.update(loss=score, epoch=epoch, P=trainer.P.clone())
             wait = 0
         else:
             wait += 1
