@@ -1412,6 +1412,13 @@ size_t amds_ppeg_wgrad_workspace_bytes(int B, int C);
 int amds_ppeg_wgrad(const float* x, const float* dy, float* dcorr, int B, int H, int W, int C, void* ws, size_t ws_bytes, void* stream);
 /* ws: contents on entry are ignored (the call initialises every byte it reads);
  *     nothing outside [ws, ws + amds_ppeg_wgrad_workspace_bytes) is written. */
+/* The table of amds_ppeg_wgrad (and amds_transmil_grads.ppeg_corr) cut into the gradients of PPEG's six parameters, in the reference's layouts
+ * (trans_mil.py:269-271: proj = Conv2d(dim, dim, 7, groups=dim), proj1 the 5x5, proj2 the 3x3 one; autograd's .grad of each through :280), ONE launch:
+ *   w7 [C][1][7][7]  w7[c][r][q] = corr[r*7+q][c]              b7 [C] = b5 [C] = b3 [C] = corr[49]
+ *   w5 [C][1][5][5]  w5[c][r][q] = corr[(r+1)*7+q+1][c]        w3 [C][1][3][3]  w3[c][r][q] = corr[(r+2)*7+q+2][c]
+ * Copies only: the bits of slicing the table.  C a multiple of 4; corr and the six outputs 16-byte aligned and distinct (a trainer passes views of its flat
+ * gradient buffer); a null pointer returns AMDS_ERR_INVALID.  No workspace, no atomics. */
+int amds_ppeg_grads_unpack(const float* corr, int C, float* w7, float* w5, float* w3, float* b7, float* b5, float* b3, void* stream);
 int amds_relu_bwd(const float* h, const float* dh, float* dz, long n, void* stream);
 size_t amds_pinv_init_bwd_workspace_bytes(int nmat);
 int amds_pinv_init_bwd(const float* x, const float* dz0, float* dx, int nmat, int n, void* ws, size_t ws_bytes, void* stream);

@@ -361,6 +361,7 @@ PROTOTYPES = {
     "amds_dwconv_seq_wgrad": (_i, [_vp, _l, _l, _i, _vp, _l, _l, _i, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "amds_ppeg_wgrad_workspace_bytes": (_sz, [_i, _i]),
     "amds_ppeg_wgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "amds_ppeg_grads_unpack": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "amds_relu_bwd": (_i, [_vp, _vp, _vp, _l, _vp]),
     "amds_mean_pool_bwd": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "amds_topk_rows_mean": (_i, [_vp, _i, _i, _vp, _l, _i, _i, _vp, _vp, _vp]),

@@ -1282,6 +1282,58 @@ extern "C" int amds_ppeg_wgrad(const float* x, const float* dy, float* dcorr, in
     return amds_colsum(part, 50L * C, dcorr, nchunk, 50 * C, AMDS_F32, 0, cws, amds_colsum_workspace_bytes(nchunk, 50 * C), stream);
 }
 
+// The tap-correlation table -> the six PPEG gradients in the reference's layouts.  One workgroup per PPEG_UNPACK_CH channels: the [50][channels] slab of the
+// table goes to LDS by rows (float4 loads), and since w7 / w5 / w3 are [C][taps] the workgroup's share of each output is ONE contiguous span, written with
+// float4 stores (channel spans start at multiples of 64 channels and hold a multiple of 4 channels: every span is 16-byte aligned and a whole number of float4).
+constexpr int PPEG_UNPACK_CH = 64;
+namespace {
+template <int TAPS>
+__device__ __forceinline__ void ppeg_unpack_span(const float (*t)[PPEG_UNPACK_CH + 1], float* __restrict__ out, int cn) {
+    constexpr int KS = TAPS == 49 ? 7 : TAPS == 25 ? 5 : 3, OFF = (7 - KS) / 2;          // the KS x KS window in the middle of the 7 x 7 table
+    const int n4 = cn * TAPS / 4;
+    for (int j = threadIdx.x; j < n4; j += 256) {
+        float v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int e = 4 * j + u, cl = e / TAPS, k = e - cl * TAPS;
+            v[u] = t[(k / KS + OFF) * 7 + k % KS + OFF][cl];
+        }
+        reinterpret_cast<float4*>(out)[j] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+__global__ void __launch_bounds__(256) ppeg_grads_unpack_kernel(const float* __restrict__ corr, int C, float* __restrict__ w7, float* __restrict__ w5,
+                                                                float* __restrict__ w3, float* __restrict__ b7, float* __restrict__ b5, float* __restrict__ b3) {
+    __shared__ float t[50][PPEG_UNPACK_CH + 1];
+    const int c0 = blockIdx.x * PPEG_UNPACK_CH, cn = min(PPEG_UNPACK_CH, C - c0);          // C % 4 == 0, so cn % 4 == 0
+    for (int i = threadIdx.x; i < 50 * (cn / 4); i += 256) {
+        const int r = i / (cn / 4), q = i - r * (cn / 4);
+        const float4 v = *reinterpret_cast<const float4*>(corr + (long)r * C + c0 + 4 * q);
+        t[r][4 * q] = v.x; t[r][4 * q + 1] = v.y; t[r][4 * q + 2] = v.z; t[r][4 * q + 3] = v.w;
+    }
+    __syncthreads();
+    ppeg_unpack_span<49>(t, w7 + (long)c0 * 49, cn);
+    ppeg_unpack_span<25>(t, w5 + (long)c0 * 25, cn);
+    ppeg_unpack_span<9>(t, w3 + (long)c0 * 9, cn);
+    if ((int)threadIdx.x < cn / 4) {
+        const int q = threadIdx.x;
+        const float4 v = make_float4(t[49][4 * q], t[49][4 * q + 1], t[49][4 * q + 2], t[49][4 * q + 3]);
+        reinterpret_cast<float4*>(b7 + c0)[q] = v;
+        reinterpret_cast<float4*>(b5 + c0)[q] = v;
+        reinterpret_cast<float4*>(b3 + c0)[q] = v;
+    }
+}
+}  // namespace
+
+extern "C" int amds_ppeg_grads_unpack(const float* corr, int C, float* w7, float* w5, float* w3, float* b7, float* b5, float* b3, void* stream) {
+    AMDS_REQUIRE(corr && w7 && w5 && w3 && b7 && b5 && b3, "amds_ppeg_grads_unpack: null pointer");
+    AMDS_REQUIRE(C > 0 && C % 4 == 0, "amds_ppeg_grads_unpack: channels %d must be a positive multiple of 4", C);
+    AMDS_REQUIRE((((uintptr_t)corr | (uintptr_t)w7 | (uintptr_t)w5 | (uintptr_t)w3 | (uintptr_t)b7 | (uintptr_t)b5 | (uintptr_t)b3) & 15) == 0,
+                 "amds_ppeg_grads_unpack: corr and the six outputs must be 16-byte aligned");
+    hipLaunchKernelGGL(ppeg_grads_unpack_kernel, dim3(cdiv(C, PPEG_UNPACK_CH)), dim3(256), 0, (hipStream_t)stream, corr, C, w7, w5, w3, b7, b5, b3);
+    AMDS_LAUNCH_CHECK("ppeg_grads_unpack_kernel");
+    return AMDS_OK;
+}
+
 extern "C" int amds_relu_bwd(const float* h, const float* dh, float* dz, long n, void* stream) {
     AMDS_REQUIRE(h && dh && dz && n >= 0, "amds_relu_bwd: bad arguments");
     if (n == 0) return AMDS_OK;

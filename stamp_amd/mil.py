@@ -624,26 +624,10 @@ class TransMIL(nn.Module):
         return transmil_core.forward_infer_ragged(self._c_weights(rb.feats.device), dims, rb)
 
     def _forward_c(self, h: torch.Tensor) -> torch.Tensor:
-        import ctypes as C
-        Bb, T, F = h.shape
-        dev = h.device
-        if h.dtype not in ops._DT:
-            h = h.float()
-        h = h.contiguous()
-        cfg = _lib.TransMilCfg(F, self.dim_hidden, self.n_classes)
-        if self._fc1[0].in_features != F:
+        from . import transmil_core
+        if self._fc1[0].in_features != h.shape[-1]:
             raise ValueError(f"bags must be [batch, tile, {self._fc1[0].in_features}], got {tuple(h.shape)}")
-        w = self._c_weights(dev)
-        lib = _lib.lib()
-        need = lib.amds_transmil_workspace_bytes(C.byref(cfg), Bb, T)
-        if need == 0:
-            _lib.check(-1, "transmil_workspace_bytes")
-        ws = ops.scratch("transmil", dev, need)
-        logits = torch.empty(Bb, self.n_classes, dtype=torch.float32, device=dev)
-        ops.sync_float32_matmul_precision()
-        _lib.check(lib.amds_transmil_forward(C.byref(cfg), C.byref(w), h.data_ptr(), ops._DT[h.dtype], logits.data_ptr(), Bb, T, ws.data_ptr(), ws.numel(),
-                                             torch.cuda.current_stream().cuda_stream), "transmil_forward")
-        return logits
+        return transmil_core.forward_infer(self._c_weights(h.device), (self._fc1[0].in_features, self.dim_hidden, self.n_classes), h)
 
 
 class _TransMilBackward(torch.autograd.Function):

@@ -40,6 +40,7 @@ The loss on the [batch, classes] logits is the one tiny piece left to torch (SUR
 from __future__ import annotations
 
 import math
+from typing import TYPE_CHECKING
 
 import torch
 import torch.nn.functional as F
@@ -49,6 +50,9 @@ from . import train_ops as T
 from .distributed import average_buffers, average_gradients
 from .mil import VisionTransformer
 from .mil_core import PackedVit
+
+if TYPE_CHECKING:
+    from .transmil_train import HipTransMilTrainer
 
 BF = torch.bfloat16
 
@@ -331,7 +335,7 @@ def _valid_loss(lg, targets, dev, class_weights, loss_fn):
 
 def _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, per_call: int, keep: list | None = None, with_loss: bool = True) -> tuple[float, int]:
     """The validation sum of `fit` with consecutive one-bag batches run `per_call` at a time through `predict_ragged` (mil_core.group_bags decides the
-    groups): each batch's loss comes from its own logits row(s) exactly as in the one-bag loop, the group's losses reach the host in one read, and the
+    groups, or the trainer's `group_valid_bags(lengths, per_call) -> [(start, end)]` if it has one): each batch's loss comes from its own logits row(s) exactly as in the one-bag loop, the group's losses reach the host in one read, and the
     sum runs in batch order.  Batches of several bags keep the one-call `predict` of the default loop.
     keep: a list that receives every batch's (logits, targets) in batch order, both left on the device; with_loss=False: no per-batch loss and no host read."""
     vtot, vcnt = 0.0, 0
@@ -344,9 +348,13 @@ def _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, per_ca
         one = [i for i, (b, *_rest) in enumerate(pend) if b.shape[0] == 1]
         rows: dict = {}
         if one:
-            limit = trainer.max_shared_tiles() if hasattr(trainer, "max_shared_tiles") else mil_core.MAX_SOLO_TILES
             lens = [pend[i][0].shape[1] for i in one]
-            for a, e in mil_core.group_bags(lens, per_call, 1 << 62, limit):
+            if hasattr(trainer, "group_valid_bags"):          # the trainer's own grouping rule (TransMIL: by padded token rows)
+                groups = trainer.group_valid_bags(lens, per_call)
+            else:
+                limit = trainer.max_shared_tiles() if hasattr(trainer, "max_shared_tiles") else mil_core.MAX_SOLO_TILES
+                groups = mil_core.group_bags(lens, per_call, 1 << 62, limit)
+            for a, e in groups:
                 idx = one[a:e]
                 cs = None if pend[idx[0]][1] is None else [pend[i][1][0].to(dev) for i in idx]
                 lg = trainer.predict_ragged([pend[i][0][0].to(dev) for i in idx], cs)
@@ -372,9 +380,10 @@ def _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, per_ca
     return vtot, vcnt
 
 
-def fit(trainer: HipMilVitTrainer, train_batches, valid_batches, *, max_epochs: int, patience: int = 16, class_weights=None,
+def fit(trainer: "HipMilVitTrainer | HipTransMilTrainer", train_batches, valid_batches, *, max_epochs: int, patience: int = 16, class_weights=None,
         loss_fn=None, log=None, valid_bags_per_call: int = 1, monitor: str = "validation_loss", valid_auroc: bool = False) -> dict:
-    """The epoch loop of the reference's `train_model_` (src/stamp/modeling/train.py:504-564) around `HipMilVitTrainer.step`.
+    """The epoch loop of the reference's `train_model_` (src/stamp/modeling/train.py:504-564) around `HipMilVitTrainer.step` or
+    `transmil_train.HipTransMilTrainer.step` (any object with their step / predict / predict_ragged / epoch_end / P drives it).
 
     train_batches / valid_batches: callables returning an iterable of (bags, coords, bag_sizes, targets) per epoch -- the
     reference's loaders (train: fixed-size bags, batch 64, shuffled; validation: full bags, batch 1, `bag_size=None`, train.py:455-477).

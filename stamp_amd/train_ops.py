@@ -189,6 +189,16 @@ def adamw(p, g, m, v, lr: float, step: int, betas=(0.9, 0.999), eps: float = 1e-
     _lib.check(_lib.lib().amds_adamw(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, betas[0], betas[1], eps, weight_decay, step, _stream()), "adamw")
 
 
+def ppeg_grads_unpack(corr: torch.Tensor, w7: torch.Tensor, w5: torch.Tensor, w3: torch.Tensor, b7: torch.Tensor, b5: torch.Tensor, b3: torch.Tensor) -> None:
+    """The [50, C] tap-correlation table of the TransMIL backward -> the gradients of PPEG's three depth-wise kernels ([C, 1, k, k]) and biases ([C]), written
+    into the given fp32 tensors by ONE launch (`amds_ppeg_grads_unpack`): the bits of the slicing in `transmil_core.backward`."""
+    _dev(corr, w7, w5, w3, b7, b5, b3)
+    Cd = corr.shape[1]
+    assert corr.shape == (50, Cd) and all(t.dtype == torch.float32 and t.is_contiguous() for t in (corr, w7, w5, w3, b7, b5, b3))
+    assert w7.numel() == 49 * Cd and w5.numel() == 25 * Cd and w3.numel() == 9 * Cd and b7.numel() == b5.numel() == b3.numel() == Cd
+    _lib.check(_lib.lib().amds_ppeg_grads_unpack(_p(corr), Cd, _p(w7), _p(w5), _p(w3), _p(b7), _p(b5), _p(b3), _stream()), "ppeg_grads_unpack")
+
+
 # ---- dynamic loss scaling (amds_loss_scale_state, include/amdstamp.h): the state is a 12-word int32 device tensor ----------------------------
 LS_WORDS = 12
 LS_SCALE, LS_INV_SCALE, LS_NONFINITE, LS_LAST_NONFINITE, LS_CLEAN_STEPS, LS_SKIPPED, LS_GROWTH_INTERVAL = range(7)

@@ -175,9 +175,10 @@ def _c_weights(get, Cd: int):
     return w, keep
 
 
-def forward_train(get, bags: torch.Tensor, dims: tuple[int, int, int], *, training: bool, seed: int = 0):
+def forward_train(get, bags: torch.Tensor, dims: tuple[int, int, int], *, training: bool, seed: int = 0, weights=None):
     """-> (logits [Bb, C], saved).  dims = (dim_input, dim_hidden, dim_output).  ONE library call (amds_transmil_train_forward,
-    csrc/transmil_train.hip); `saved` holds the activation arena the backward reads."""
+    csrc/transmil_train.hip); `saved` holds the activation arena the backward reads.  weights: a `_c_weights` pair built earlier (the trainer's, over its
+    flat master buffer) instead of one built from `get` for this call."""
     import ctypes as C
     Fd, Cd, Cc = dims
     Bb, Tn, _ = bags.shape
@@ -188,7 +189,7 @@ def forward_train(get, bags: torch.Tensor, dims: tuple[int, int, int], *, traini
     lib = _lib.lib()
     # resolved HERE so that the backward of this step reads the arena the way this forward wrote it, whatever the context says by then
     cfg = _lib.TransMilCfg(Fd, Cd, Cc, 1 if lib.amds_get_mil_cls_tail(_lib.ctx_of(dev)) else 0)
-    w, keep = _c_weights(get, Cd)
+    w, keep = weights if weights is not None else _c_weights(get, Cd)
     need = lib.amds_transmil_train_saved_bytes(C.byref(cfg), Bb, Tn)
     if need == 0:
         _lib.check(-1, "transmil_train_saved_bytes")
@@ -201,8 +202,10 @@ def forward_train(get, bags: torch.Tensor, dims: tuple[int, int, int], *, traini
     return logits, dict(arena=arena, cfg=cfg, w=w, keep=keep, shape=(Bb, Tn, Fd), dims=dims, p_out=p_out, seed=seed)
 
 
-def backward(saved: dict, dlogits: torch.Tensor, *, need_params: bool = True, need_bags: bool = False):
-    """-> (grads keyed by the reference's state_dict names, dbags or None).  ONE library call (amds_transmil_train_backward)."""
+def backward(saved: dict, dlogits: torch.Tensor, *, need_params: bool = True, need_bags: bool = False, grads: "_lib.TransMilGrads | None" = None):
+    """-> (grads keyed by the reference's state_dict names, dbags or None).  ONE library call (amds_transmil_train_backward).
+    grads: an `amds_transmil_grads` over buffers the caller owns (the trainer's flat gradient buffer and its correlation table): the library writes there,
+    nothing is allocated or sliced here and the returned dict is empty."""
     import ctypes as C
     Fd, Cd, Cc = saved["dims"]
     Bb, Tn, _ = saved["shape"]
@@ -215,7 +218,8 @@ def backward(saved: dict, dlogits: torch.Tensor, *, need_params: bool = True, ne
         _lib.check(-1, "transmil_train_workspace_bytes")
     ws = ops.scratch("transmil_train", dev, need)
     G: dict[str, torch.Tensor] = {}
-    gc = corr = None
+    gc, corr = grads, None
+    need_params = need_params and grads is None
     if need_params:
         G = {"_fc1.0.weight": torch.empty(Cd, Fd, **f32), "_fc1.0.bias": torch.empty(Cd, **f32), "cls_token": torch.empty(1, 1, Cd, **f32),
              "norm.weight": torch.empty(Cd, **f32), "norm.bias": torch.empty(Cd, **f32), "_fc2.weight": torch.empty(Cc, Cd, **f32), "_fc2.bias": torch.empty(Cc, **f32)}
@@ -243,6 +247,31 @@ def backward(saved: dict, dlogits: torch.Tensor, *, need_params: bool = True, ne
         for c in ("proj", "proj1", "proj2"):
             G[f"pos_layer.{c}.bias"] = corr[49].clone()
     return G, (dbags.view(Bb, Tn, Fd) if need_bags else None)
+
+
+def forward_infer(w: "_lib.TransMilWeights", dims: tuple[int, int, int], h: torch.Tensor) -> torch.Tensor:
+    """Bags [Bb, T, dim_input] -> logits [Bb, dim_output]: the deploy / validation forward, ONE library call (amds_transmil_forward, csrc/transmil_fwd.hip)
+    on the fp32 weights `w` points to (`TransMIL.forward` in eval mode, and `HipTransMilTrainer.predict` on its flat master buffer)."""
+    import ctypes as C
+    Fd, Cd, Cc = dims
+    Bb, Tn, F = h.shape
+    if F != Fd:
+        raise ValueError(f"bags must be [batch, tile, {Fd}], got {tuple(h.shape)}")
+    dev = h.device
+    if h.dtype not in ops._DT:
+        h = h.float()
+    h = h.contiguous()
+    cfg = _lib.TransMilCfg(Fd, Cd, Cc)
+    lib = _lib.lib()
+    need = lib.amds_transmil_workspace_bytes(C.byref(cfg), Bb, Tn)
+    if need == 0:
+        _lib.check(-1, "transmil_workspace_bytes")
+    ws = ops.scratch("transmil", dev, need)
+    logits = torch.empty(Bb, Cc, dtype=torch.float32, device=dev)
+    ops.sync_float32_matmul_precision()
+    _lib.check(lib.amds_transmil_forward(C.byref(cfg), C.byref(w), h.data_ptr(), ops._DT[h.dtype], logits.data_ptr(), Bb, Tn, ws.data_ptr(), ws.numel(), ops._stream()),
+               "transmil_forward")
+    return logits
 
 
 # ---- ragged inference: bags of different lengths in one library call (amds_transmil_forward_ragged, csrc/transmil_ragged.hip) ------------------
