@@ -1313,6 +1313,21 @@ int amds_transmil_forward(const amds_transmil_cfg* cfg_host, const amds_transmil
 /* ws: contents on entry are ignored (the call initialises every byte it reads);
  *     nothing outside [ws, ws + amds_transmil_workspace_bytes) is written. */
 
+/* amds_transmil_forward of a GROUP of bags in several calls of fewer bags, with the bits of one call over the whole group.  The bags of one call are coupled
+ * in one place only: each layer's pseudo-inverse starts from z0 = attn2^T / (max row sum * max column sum) with the maxima over ALL bags and heads of the
+ * call (trans_mil.py:26-28).  `maxima`: 16 bytes of device memory (layer1's pair, layer2's pair; fp32 bit patterns), zeroed by the caller once per group.
+ *   stage 0   every sub-call: the forward up to layer1's attn2; raises maxima[0..1] to this sub-call's maxima (atomic max: exact, order-free).  logits may be NULL.
+ *   stage 1   every sub-call, after ALL stage-0 calls of the group: layer1 from maxima[0..1], on to layer2's attn2; raises maxima[2..3].  logits may be NULL.
+ *   stage 2   every sub-call, after ALL stage-1 calls: the whole forward from both pairs -> logits of this sub-call's bags.
+ * Two products run over the rows of all bags of a call (_fc1: bags x tiles rows, to_qkv: bags x padded tokens) and choose their kernel -- for _fc1 below
+ * "highest": whether it is an amds_bgemm_f32 product at all -- by that row count.  `group_bags` is the group's bag count: it decides _fc1's path as the one
+ * call would, and a sub-call must keep both row counts in the group's class (same side of 64 and 96 rows, the same whole tiles of 64 / 128 / 256 rows):
+ * amds_transmil_staged_compatible(cfg, group_bags, n_bags, n_tiles) says so (1 / 0; host only), and a sub-call that does not is AMDS_ERR_INVALID, nothing
+ * launched.  Same kernels, workspace (amds_transmil_workspace_bytes of the sub-call) and checks as amds_transmil_forward; launches only, on `stream`. */
+int amds_transmil_staged_compatible(const amds_transmil_cfg* cfg_host, int group_bags, int n_bags, int n_tiles);
+int amds_transmil_forward_staged(const amds_transmil_cfg* cfg_host, const amds_transmil_weights* w_host, const void* bags, int bags_dtype, float* logits,
+                                 int n_bags, int n_tiles, int group_bags, int stage, void* maxima, void* ws, size_t ws_bytes, void* stream);
+
 /* The same forward over RAGGED bags: n_bags bags of different tile counts packed without padding, one call, every bag computed as the reference computes it
  * at batch 1 (validation and deploy: modeling/train.py:467-477 `bag_size=None, batch_size=1`; deploy.py:390-456).  Per bag of T tiles (m = dim / 2):
  *   side = ceil(sqrt(T)), n = side^2 + 1 token rows (class token, the tiles, the FIRST tiles again)                         trans_mil.py:306-314
@@ -1386,6 +1401,27 @@ int amds_transmil_train_backward(const amds_transmil_cfg* cfg_host, const amds_t
                                  size_t ws_bytes, void* stream);
 /* ws: contents on entry are ignored (the call initialises every byte it reads);
  *     nothing outside [ws, ws + amds_transmil_train_workspace_bytes) is written. */
+
+/* Grad-CAM scores of every tile for every class of the TransMIL head from ONE call (reference src/stamp/heatmaps/__init__.py: `_gradcam_per_category` :36-56
+ * up to and including line 54, `_gradcam_single` :115-139 line 137; the reference builds the [classes][tiles][n_feats] Jacobian with torch.func.jacrev):
+ *   cam_raw[c][b * n_tiles + t] = | (1 / n_feats) * sum_f bags[b][t][f] * d logit_c[b] / d bags[b][t][f] |,     fp32 [classes][n_bags * n_tiles], before any softmax.
+ * `saved`: the arena of an amds_transmil_train_forward call made with p_drop = 0, read exactly as that forward wrote it: `cfg_host` must be the configuration that
+ * forward was given (train_cls_tail decides which of layer2's rows the arena holds).  The class loop runs inside: for each class one small kernel fills
+ * dlogits = e_c for every bag, then the backward's launch sequence runs with no gradient buffers (no weight-gradient products, no PPEG correlation table, no column
+ * sums; p_drop = 0, seed = 0) down to layer1's LayerNorm backward, and ONE row-dot kernel takes the place of the tile-row copy, the wrap-padding add, the ReLU
+ * backward and the product with W_fc1.  _fc1 is Linear + ReLU, z = bags W^T + b, and the arena's h equals z wherever the ReLU passes, so with dx [n_bags][n][dim]
+ * the gradient of the wrapped token sequence (row 0 = class token, rows 1 .. n_tiles = the tiles, rows n_tiles + 1 .. side^2 = the first add = side^2 - n_tiles
+ * tiles AGAIN, trans_mil.py:306-309)
+ *   cam = | sum_d [h[b][t][d] > 0] * (dx[b][1 + t][d] + (t < add ? dx[b][1 + n_tiles + t][d] : 0)) * (h[b][t][d] - fc1_b[d]) | / n_feats:
+ * a wrapped tile's two copies add their gradients.  fp32 throughout, one wave per tile row, a fixed-order reduction: deterministic.  Neither dbags nor anything
+ * else of size [tiles][n_feats] is written.  All classes share `ws` (amds_transmil_gradcam_workspace_bytes <= amds_transmil_train_workspace_bytes for every shape;
+ * 256-byte aligned; 0 on a bad configuration); an arena or workspace that is too small is AMDS_ERR_WORKSPACE before anything is launched; n_bags == 0 is AMDS_OK.
+ * weights->fc1_b must be 16-byte aligned.  Launches only, on `stream`. */
+size_t amds_transmil_gradcam_workspace_bytes(const amds_transmil_cfg* cfg_host, int n_bags, int n_tiles);
+int amds_transmil_gradcam(const amds_transmil_cfg* cfg_host, const amds_transmil_weights* w_host, int n_bags, int n_tiles, const void* saved, size_t saved_bytes,
+                          float* cam_raw, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_transmil_gradcam_workspace_bytes) is written. */
 
 /* Backward pieces of the TransMIL head (training: the reference differentiates trans_mil.py with autograd inside
  * LitTileClassifier._step, src/stamp/modeling/models/__init__.py:239-279); fp32 like the forward.  The matrix products of the

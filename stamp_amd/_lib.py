@@ -332,7 +332,11 @@ PROTOTYPES = {
     "amds_nystrom_attn_workspace_bytes": (_sz, [_i, _i, _i]),
     "amds_nystrom_attn_fwd": (_i, [_vp, _i, _vp, _vp, _i, _i, _f, C.c_uint64, C.c_uint32, _vp, _sz, _vp]),
     "amds_nystrom_attn_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _f, C.c_uint64, C.c_uint32, _vp, _sz, _vp, _sz, _vp]),
+    "amds_transmil_gradcam_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "amds_transmil_gradcam": (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp, _vp, _sz, _vp]),
     "amds_transmil_forward": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _sz, _vp]),
+    "amds_transmil_staged_compatible": (_i, [_vp, _i, _i, _i]),
+    "amds_transmil_forward_staged": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "amds_transmil_ragged_plan": (_i, [_vp, _i, _vp, _vp]),
     "amds_transmil_ragged_workspace_bytes": (_sz, [_vp, _i, _vp]),
     "amds_transmil_forward_ragged": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),

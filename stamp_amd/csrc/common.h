@@ -385,6 +385,9 @@ int nystrom_attn_fwd_ex(const amds_transmil_layer* w_host, int dim, const float*
                         void* saved, size_t saved_bytes, int cls_only, void* stream);
 int nystrom_attn_bwd_ex(const amds_transmil_layer* w_host, int dim, const float* dx, float* dy, const amds_nystrom_grads* grads_host, int n_bags, int n_tokens, float p_drop,
                         uint64_t seed, uint32_t stream_id, const void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, int cls_only, void* stream);
+int pinv_absmax_accumulate(const float* x, int nmat, int n, unsigned* mx2, int group, void* stream);          // transmil.hip: the halves of amds_pinv_init
+int pinv_init_preset(const float* x, float* z, int nmat, int n, const unsigned* mx2, int group, void* stream);
+unsigned bgemm_f32_row_class(long M);          // transmil.hip: what amds_bgemm_f32's choice of kernel takes from the row count
 int layernorm_bwd_cast_dt(const float* dy, long dy_stride, const float* x, long x_stride, const float* mean, const float* rstd, const float* gamma, float* dx, long dx_stride,
                           int add_skip, float* dgamma, float* dbeta, int accumulate_params, int rows, int cols, void* ws, size_t ws_bytes, void* dx16, long dx16_stride,
                           int dx16_dtype, float p, uint64_t seed, uint32_t stream_id, void* stream);

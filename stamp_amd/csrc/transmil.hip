@@ -1522,18 +1522,37 @@ extern "C" int amds_landmark_mean(const float* x, long sxo, long sxi, int ld, fl
     return AMDS_OK;
 }
 
+// The two halves of amds_pinv_init.  pinv_absmax_accumulate raises the pairs of maxima mx2 (fp32 bit patterns, >= 0: unsigned order is float order; one pair per
+// `group` consecutive matrices) to the maxima of these matrices -- no memset: amds_transmil_forward_staged keeps ONE pair over the calls of a group of bags and
+// zeroes it once --; pinv_init_preset is z0 = x^T / (mx2[0] * mx2[1]) from the pairs as they stand.
+namespace amds {
+int pinv_absmax_accumulate(const float* x, int nmat, int n, unsigned* mx2, int group, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (n % 4 == 0 && n <= 256 && ((uintptr_t)x & 15) == 0) hipLaunchKernelGGL((absmax_kernel<2>), dim3(nmat), dim3(256), 0, st, x, n, mx2, group);
+    else if (n % 4 == 0 && n <= 1024 && ((uintptr_t)x & 15) == 0) hipLaunchKernelGGL((absmax_kernel<8>), dim3(nmat), dim3(256), 0, st, x, n, mx2, group);
+    else hipLaunchKernelGGL(absmax_any_kernel, dim3(nmat), dim3(256), 0, st, x, n, mx2, group);
+    AMDS_LAUNCH_CHECK("absmax_kernel");
+    return AMDS_OK;
+}
+int pinv_init_preset(const float* x, float* z, int nmat, int n, const unsigned* mx2, int group, void* stream) {
+    hipLaunchKernelGGL(transpose_scale_kernel, dim3(cdiv(n, 32), cdiv(n, 32), nmat), dim3(256), 0, (hipStream_t)stream, x, z, n, mx2, group);
+    AMDS_LAUNCH_CHECK("transpose_scale_kernel");
+    return AMDS_OK;
+}
+// What bgemm_f32_at's choice of kernel takes from the row count M (the small kernel below 96 rows, the tile shape at 64, whole tiles of 64 / 128 / 256 rows for the
+// kernel that splits on the way into LDS): two products whose other arguments agree run the same kernel, and give a row the same bits, when this agrees.
+unsigned bgemm_f32_row_class(long M) {
+    return (unsigned)(M >= 96) | (unsigned)(M <= 64) << 1 | (unsigned)(M % 64 == 0) << 2 | (unsigned)(M % 128 == 0) << 3 | (unsigned)(M % 256 == 0) << 4;
+}
+}  // namespace amds
+
 // maxima per `group` consecutive matrices; scratch: 8 B per group
 static int pinv_init_at(const float* x, float* z, int nmat, int n, int group, void* scratch, void* stream) {
     using namespace amds;
-    hipStream_t st = (hipStream_t)stream;
-    AMDS_HIP(hipMemsetAsync(scratch, 0, (size_t)8 * (nmat / group), st));
-    if (n % 4 == 0 && n <= 256 && ((uintptr_t)x & 15) == 0) hipLaunchKernelGGL((absmax_kernel<2>), dim3(nmat), dim3(256), 0, st, x, n, (unsigned*)scratch, group);
-    else if (n % 4 == 0 && n <= 1024 && ((uintptr_t)x & 15) == 0) hipLaunchKernelGGL((absmax_kernel<8>), dim3(nmat), dim3(256), 0, st, x, n, (unsigned*)scratch, group);
-    else hipLaunchKernelGGL(absmax_any_kernel, dim3(nmat), dim3(256), 0, st, x, n, (unsigned*)scratch, group);
-    AMDS_LAUNCH_CHECK("absmax_kernel");
-    hipLaunchKernelGGL(transpose_scale_kernel, dim3(cdiv(n, 32), cdiv(n, 32), nmat), dim3(256), 0, st, x, z, n, (const unsigned*)scratch, group);
-    AMDS_LAUNCH_CHECK("transpose_scale_kernel");
-    return AMDS_OK;
+    AMDS_HIP(hipMemsetAsync(scratch, 0, (size_t)8 * (nmat / group), (hipStream_t)stream));
+    const int rc = pinv_absmax_accumulate(x, nmat, n, (unsigned*)scratch, group, stream);
+    if (rc != AMDS_OK) return rc;
+    return pinv_init_preset(x, z, nmat, n, (const unsigned*)scratch, group, stream);
 }
 
 extern "C" int amds_pinv_init(const float* x, float* z, int nmat, int n, void* scratch8, void* stream) {

@@ -106,7 +106,10 @@ int bg(const float* A, int lda, long sAo, long sAi, const float* B, int ldb, lon
 // cls_only: the caller reads the class token's row of x_res and nothing else (the second TransLayer: `self.norm(h)[:, 0]`, trans_mil.py:319-323) -- attn1, attn1 z,
 // (attn1 z)(attn3 v), the residual convolution and to_out are computed for that one row per bag (row `pad` of the front-padded sequence); landmarks, attn2 and its
 // pseudo-inverse, attn3 and attn3 v need every token and stay as they are.
-int nystrom(const TmPlan& p, const amds_transmil_layer& L, const float* y, float* x_res, int b, char* wk, void* stream, bool cls_only = false) {
+// mx / mode (amds_transmil_forward_staged): the pseudo-inverse's pair of maxima lives with the caller.  mode 0: the call's own maxima (mx unused); mode 1: raise
+// mx to the maxima of this call's attn2 and return right after (nothing else of the block is computed, x_res is not written); mode 2: z0 from mx as it stands.
+int nystrom(const TmPlan& p, const amds_transmil_layer& L, const float* y, float* x_res, int b, char* wk, void* stream, bool cls_only = false, unsigned* mx = nullptr,
+            int mode = 0) {
     hipStream_t st = (hipStream_t)stream;
     const int Cd = p.Cd, H = HEADS, m = p.m, d = p.d, n = p.n, np = p.np, pad = p.pad, l = p.l;
     const float* yp = y;
@@ -129,6 +132,11 @@ int nystrom(const TmPlan& p, const amds_transmil_layer& L, const float* y, float
     float *a1 = reinterpret_cast<float*>(wk + p.a1), *a2 = reinterpret_cast<float*>(wk + p.a2), *a3 = reinterpret_cast<float*>(wk + p.a3);
     const long md = (long)m * d, mm = (long)m * m, nm = (long)np * m;
     const long hm = (long)H * m;
+    if (mode == 1) {
+        RC(bg(ql, d, H * md, md, kl, d, H * md, md, 1, a2, m, H * mm, mm, b, H, m, m, d, 1.0f, 0.0f, nullptr, 0, stream));         // sim2 = ql kl^T, as below
+        RC(amds_softmax_rows(a2, (long)b * H * m, m, stream));
+        return pinv_absmax_accumulate(a2, b * H, m, mx, b * H, stream);
+    }
     if (cls_only) RC(bg(qp + (size_t)pad * ld, ld, sb, sh, kl, d, H * md, md, 1, a1, m, hm, m, b, H, 1, m, d, scale, 0.0f, nullptr, 0, stream));      // the class row of sim1
     else
     RC(bg(qp, ld, sb, sh, kl, d, H * md, md, 1, a1, m, H * nm, nm, b, H, np, m, d, scale, 0.0f, nullptr, 0, stream));              // sim1 = q kl^T (:126-128)
@@ -140,8 +148,11 @@ int nystrom(const TmPlan& p, const amds_transmil_layer& L, const float* y, float
     // Moore-Penrose iteration (:23-37): z <- 0.25 z (13 I - xz (15 I - xz (7 I - xz))),  xz = x z
     float *z = reinterpret_cast<float*>(wk + p.z), *z2 = reinterpret_cast<float*>(wk + p.z2), *xz = reinterpret_cast<float*>(wk + p.xz);
     float *t1 = reinterpret_cast<float*>(wk + p.t1), *t2 = reinterpret_cast<float*>(wk + p.t2);
-    AMDS_HIP(hipMemsetAsync(wk + p.scratch, 0, 8, st));
-    RC(amds_pinv_init(a2, z, b * H, m, wk + p.scratch, stream));
+    if (mode == 2) RC(pinv_init_preset(a2, z, b * H, m, mx, b * H, stream));
+    else {
+        AMDS_HIP(hipMemsetAsync(wk + p.scratch, 0, 8, st));
+        RC(amds_pinv_init(a2, z, b * H, m, wk + p.scratch, stream));
+    }
     // The chain runs chunk by chunk of the batch, 256 matrices (1024 workgroups per launch) at a time: the deploy forward keeps no iterate, so a chunk's five buffers
     // are re-used while parts of them are still in the Infinity Cache -- 6 540 -> 6 720 bags/s at 64 bags (512 matrices: two chunks; four chunks of 128: +1.8 %, eight:
     // -13 %: too few workgroups per launch).  The training forward keeps every iterate for the backward and gains nothing (profiles/r06_transmil_prefetch_ab.txt).
@@ -190,9 +201,21 @@ extern "C" size_t amds_transmil_workspace_bytes(const amds_transmil_cfg* cfg_hos
     return p.total;
 }
 
-extern "C" int amds_transmil_forward(const amds_transmil_cfg* cfg_host, const amds_transmil_weights* w_host, const void* bags, int bags_dtype, float* logits,
-                                     int n_bags, int n_tiles, void* ws, size_t ws_bytes, void* stream) {
-    AMDS_REQUIRE(cfg_host && w_host && bags && logits && ws, "amds_transmil_forward: null pointer");
+// Two products of the forward run over the rows of ALL bags of a call -- _fc1 over bags x tiles rows, to_qkv over bags x np rows -- and pick their kernel (for
+// _fc1 below "highest": whether it is an amds_bgemm_f32 product at all) by that row count.  A sub-call of `sub` bags repeats the choices of one call over `group`
+// bags when both row counts fall in the same class (bgemm_f32_row_class); everything else of the forward is per bag or per row.
+static bool staged_compatible(const amds_transmil_cfg* c, const TmPlan& p, int group, int sub, int T) {
+    if (sub < 1 || sub > group) return false;
+    if (bgemm_f32_row_class((long)sub * p.np) != bgemm_f32_row_class((long)group * p.np)) return false;
+    const bool fc1_bg = p.Cd % 128 == 0 && c->n_feats % 32 == 0;          // (_fc1 can be a bgemm product: at every precision, so that the answer does not move with it)
+    return !fc1_bg || bgemm_f32_row_class((long)sub * T) == bgemm_f32_row_class((long)group * T);
+}
+
+// stage < 0: amds_transmil_forward as declared.  stage 0 / 1 / 2: amds_transmil_forward_staged over `maxima` (two pairs: layer1's, layer2's), a sub-call of a group
+// of `group_bags` bags.
+static int transmil_forward_body(const amds_transmil_cfg* cfg_host, const amds_transmil_weights* w_host, const void* bags, int bags_dtype, float* logits, int n_bags,
+                                 int n_tiles, void* ws, size_t ws_bytes, void* stream, int stage, unsigned* maxima, int group_bags) {
+    AMDS_REQUIRE(cfg_host && w_host && bags && (logits || stage == 0 || stage == 1) && ws, "amds_transmil_forward: null pointer");
     TmPlan p;
     RC(tm_plan(cfg_host, n_bags, n_tiles, &p));
     const amds_transmil_weights& w = *w_host;
@@ -208,6 +231,9 @@ extern "C" int amds_transmil_forward(const amds_transmil_cfg* cfg_host, const am
     }
     AMDS_REQUIRE(((uintptr_t)ws & 255) == 0, "amds_transmil_forward: workspace must be 256-byte aligned");
     if (n_bags == 0) return AMDS_OK;
+    AMDS_REQUIRE(stage < 0 || staged_compatible(cfg_host, p, group_bags, n_bags, n_tiles),
+                 "amds_transmil_forward_staged: a sub-call of %d bags does not repeat the kernel choices of %d bags in one call (amds_transmil_staged_compatible)", n_bags,
+                 group_bags);
     hipStream_t st = (hipStream_t)stream;
     char* wk = reinterpret_cast<char*>(ws);
     const int Bb = n_bags, T = n_tiles, Cd = p.Cd, F = cfg_host->n_feats, n = p.n;
@@ -225,20 +251,43 @@ extern "C" int amds_transmil_forward(const amds_transmil_cfg* cfg_host, const am
     float* h1 = reinterpret_cast<float*>(wk + p.qkv);                                    // _fc1 output [Bb*T][Cd]: scratch (the qkv region is larger and free here)
     // _fc1 = Linear + ReLU (:303).  Below torch's "highest" the product is a product like the others (amds_bgemm_f32: bf16 x 3 at "high") and the ReLU rides on the
     // copy into the wrapped sequence; at "highest" the exact-fp32 Linear of the MLP heads (a 64 x 64-tile kernel: 700 us at 65 536 x 1024 x 512 against ~400)
-    const bool fc1_x3 = ctx_matmul_precision() != AMDS_MATMUL_HIGHEST && ((long)Bb * T) % 128 == 0 && Cd % 128 == 0 && F % 32 == 0;
+    // (staged: the GROUP's row count decides, as in the one call; the sub-call's is in the same class)
+    const bool fc1_x3 = ctx_matmul_precision() != AMDS_MATMUL_HIGHEST && ((long)(stage < 0 ? Bb : group_bags) * T) % 128 == 0 && Cd % 128 == 0 && F % 32 == 0;
     if (fc1_x3) RC(bg(hf, F, 0, 0, w.fc1_w, F, 0, 0, 1, h1, Cd, 0, 0, 1, 1, Bb * T, Cd, F, 1.0f, 0.0f, w.fc1_b, 0, stream));
     else RC(amds_linear_f32(hf, w.fc1_w, w.fc1_b, h1, Bb * T, Cd, F, 1, stream));
     hipLaunchKernelGGL(wrap_cls_kernel, dim3((unsigned)((long)Bb * n)), dim3(128), 0, st, w.cls_token, h1, x, Cd, T, n, fc1_x3 ? 1 : 0);
     AMDS_LAUNCH_CHECK("wrap_cls_kernel");
     // layer1, PPEG, layer2 (:317-319)
     RC(amds_layernorm(x, Cd, w.layer[0].norm_w, w.layer[0].norm_b, y, Cd, Bb * n, Cd, 1e-5f, AMDS_F32, stream));
-    RC(nystrom(p, w.layer[0], y, x, Bb, wk, stream));
+    RC(nystrom(p, w.layer[0], y, x, Bb, wk, stream, false, maxima, stage < 0 ? 0 : stage == 0 ? 1 : 2));
+    if (stage == 0) return AMDS_OK;
     RC(amds_ppeg(x, y, w.ppeg_w7, w.ppeg_b7, w.ppeg_w5, w.ppeg_b5, w.ppeg_w3, w.ppeg_b3, Bb, p.side, p.side, Cd, stream));
     std::swap(x, y);
     RC(amds_layernorm(x, Cd, w.layer[1].norm_w, w.layer[1].norm_b, y, Cd, Bb * n, Cd, 1e-5f, AMDS_F32, stream));
-    RC(nystrom(p, w.layer[1], y, x, Bb, wk, stream, ctx_mil_cls_tail() != 0));      // (amds_set_mil_cls_tail(0): every row, A/B and the chain tests)
+    RC(nystrom(p, w.layer[1], y, x, Bb, wk, stream, ctx_mil_cls_tail() != 0, maxima + 2, stage < 0 ? 0 : stage == 1 ? 1 : 2));      // (amds_set_mil_cls_tail(0): every row, A/B and the chain tests)
+    if (stage == 1) return AMDS_OK;
     // final LayerNorm on the class-token rows, _fc2 (:322-325)
     float* cls = reinterpret_cast<float*>(wk + p.cls);
     RC(amds_layernorm(x, (long)n * Cd, w.norm_w, w.norm_b, cls, Cd, Bb, Cd, 1e-5f, AMDS_F32, stream));
     return amds_linear_f32(cls, w.fc2_w, w.fc2_b, logits, Bb, cfg_host->classes, Cd, 0, stream);
+}
+
+extern "C" int amds_transmil_forward(const amds_transmil_cfg* cfg_host, const amds_transmil_weights* w_host, const void* bags, int bags_dtype, float* logits,
+                                     int n_bags, int n_tiles, void* ws, size_t ws_bytes, void* stream) {
+    AMDS_REQUIRE(logits, "amds_transmil_forward: null pointer");
+    return transmil_forward_body(cfg_host, w_host, bags, bags_dtype, logits, n_bags, n_tiles, ws, ws_bytes, stream, -1, nullptr, n_bags);
+}
+
+extern "C" int amds_transmil_staged_compatible(const amds_transmil_cfg* cfg_host, int group_bags, int n_bags, int n_tiles) {
+    TmPlan p;
+    if (group_bags < 1 || n_bags < 1 || tm_plan(cfg_host, n_bags, n_tiles, &p) != AMDS_OK) return 0;
+    return staged_compatible(cfg_host, p, group_bags, n_bags, n_tiles) ? 1 : 0;
+}
+
+extern "C" int amds_transmil_forward_staged(const amds_transmil_cfg* cfg_host, const amds_transmil_weights* w_host, const void* bags, int bags_dtype, float* logits,
+                                            int n_bags, int n_tiles, int group_bags, int stage, void* maxima, void* ws, size_t ws_bytes, void* stream) {
+    AMDS_REQUIRE(stage >= 0 && stage <= 2, "amds_transmil_forward_staged: stage %d is not 0, 1 or 2", stage);
+    AMDS_REQUIRE(maxima && ((uintptr_t)maxima & 15) == 0, "amds_transmil_forward_staged: maxima must be 16 bytes of device memory, 16-byte aligned");
+    AMDS_REQUIRE(logits || stage < 2, "amds_transmil_forward_staged: stage 2 needs logits");
+    return transmil_forward_body(cfg_host, w_host, bags, bags_dtype, logits, n_bags, n_tiles, ws, ws_bytes, stream, stage, reinterpret_cast<unsigned*>(maxima), group_bags);
 }

@@ -44,21 +44,26 @@ int tt_saved(const TtDims& d, TtSaved* s) {
 
 struct TtWs { size_t dx, dx2, dy, dcls, dlt, dh, dzh, part, cs, lnb, pw, zb, wflip, ny, gsc, total, cs_bytes, lnb_bytes, pw_bytes, ny_bytes; };
 
-int tt_ws(const TtDims& d, TtWs* w) {
+// `lean`: the plan of a backward that stops at _fc1's output with no parameter gradients (amds_transmil_gradcam): no dh / dzh, no per-bag dW1 partials, no column-sum
+// or PPEG weight-gradient scratch.  Every region it keeps is taken in the full plan too, so lean.total <= full.total for every shape; `dlt` then holds the basis vectors.
+int tt_ws(const TtDims& d, TtWs* w, bool lean = false) {
     Arena ar;
     const size_t Mt = (size_t)d.Bb * d.T, M = (size_t)d.Bb * d.n, Cd = d.Cd;
     w->ny_bytes = amds_nystrom_attn_workspace_bytes(d.Cd, d.Bb, d.n);
     if (w->ny_bytes == 0) return AMDS_ERR_INVALID;
     w->dx = ar.take(M * Cd * 4); w->dx2 = ar.take(M * Cd * 4); w->dy = ar.take(M * Cd * 4);
     w->dcls = ar.take((size_t)d.Bb * Cd * 4); w->dlt = ar.take((size_t)d.Bb * d.C * 4);
-    w->dh = ar.take(Mt * Cd * 4); w->dzh = ar.take(Mt * Cd * 4);
-    w->part = ar.take((size_t)d.Bb * Cd * d.F * 4);
-    size_t cs = amds_colsum_workspace_bytes(d.Bb, d.Cd * d.F);
-    cs = std::max(cs, amds_colsum_workspace_bytes((int)Mt, d.Cd));
-    cs = std::max(cs, amds_colsum_workspace_bytes(d.Bb, std::max(d.Cd, d.C)));
-    w->cs_bytes = std::max<size_t>(cs, 4); w->cs = ar.take(w->cs_bytes);
+    w->dh = w->dzh = w->part = w->cs = w->pw = 0; w->cs_bytes = w->pw_bytes = 0;
+    if (!lean) {
+        w->dh = ar.take(Mt * Cd * 4); w->dzh = ar.take(Mt * Cd * 4);
+        w->part = ar.take((size_t)d.Bb * Cd * d.F * 4);
+        size_t cs = amds_colsum_workspace_bytes(d.Bb, d.Cd * d.F);
+        cs = std::max(cs, amds_colsum_workspace_bytes((int)Mt, d.Cd));
+        cs = std::max(cs, amds_colsum_workspace_bytes(d.Bb, std::max(d.Cd, d.C)));
+        w->cs_bytes = std::max<size_t>(cs, 4); w->cs = ar.take(w->cs_bytes);
+    }
     w->lnb_bytes = std::max<size_t>(amds_layernorm_bwd_workspace_bytes((int)M, d.Cd), 4); w->lnb = ar.take(w->lnb_bytes);
-    w->pw_bytes = std::max<size_t>(amds_ppeg_wgrad_workspace_bytes(d.Bb, d.Cd), 4); w->pw = ar.take(w->pw_bytes);
+    if (!lean) { w->pw_bytes = std::max<size_t>(amds_ppeg_wgrad_workspace_bytes(d.Bb, d.Cd), 4); w->pw = ar.take(w->pw_bytes); }
     w->zb = ar.take(Cd * 4); w->wflip = ar.take(Cd * (49 + 25 + 9) * 4);
     w->ny = ar.take(w->ny_bytes);
     w->gsc = ar.take((size_t)(2 * Cd + 50 * Cd) * 4);
@@ -90,6 +95,44 @@ __global__ void __launch_bounds__(128) tt_tile_rows_kernel(const float* __restri
     const float* src = dx + (b * n + 1 + t) * Cd;
     float* dst = dh + r * Cd;
     for (int c = threadIdx.x; c < Cd; c += 128) dst[c] = src[c];
+}
+// ---- Grad-CAM tail (amds_transmil_gradcam) ------------------------------------------------------------------------------------------------------------------
+// reference src/stamp/heatmaps/__init__.py:54 / :137: cam[t] = |mean_f feats[t][f] * d logit / d feats[t][f]|.  _fc1 is Linear + ReLU: with z = feats W^T + b and
+// dz = [z > 0] * dh, d logit / d feats[t][:] = dz[t][:] W, so the mean is (1 / F) sum_d dz[t][d] (z[t][d] - b[d]).  The arena's h is z wherever the ReLU passes
+// (the pre-activation below "highest", the activation at "highest"), and dh is dx's tile row plus, for the first `add` tiles, the row of their wrap-padded copy.
+// dlogits of one class: basis[b][j] = (j == c)
+__global__ void tt_cam_basis_kernel(float* __restrict__ basis, int Bb, int C, int c) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < Bb * C) basis[i] = (i % C == c) ? 1.f : 0.f;
+}
+// One wave per tile row, 8 columns per lane and step (16-byte loads), fp32 throughout, a fixed-order butterfly over the 64 lanes: deterministic.  Cd is a multiple
+// of 8: a lane's 8 columns are all inside the row or all outside it (the column tail of a Cd that is no multiple of 512 is lanes that skip the step).
+__global__ void __launch_bounds__(256) tt_cam_rowdot_kernel(const float* __restrict__ dx, const float* __restrict__ h, const float* __restrict__ bias, float* __restrict__ out,
+                                                            long Mt, int T, int n, int add, int Cd, float mul) {
+    const int lane = threadIdx.x & 63;
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= Mt) return;                                         // (whole waves leave together; no barrier below)
+    const long b = r / T;
+    const int t = (int)(r - b * T);
+    const float* g = dx + (b * n + 1 + t) * Cd;
+    const bool wrapped = t < add;                                // wave-uniform
+    const float* gw = g + (long)T * Cd;                          // row 1 + T + t: read only where wrapped (t < add keeps it below n)
+    const float* hr = h + r * Cd;
+    float acc = 0.f;
+    for (int c0 = lane * 8; c0 < Cd; c0 += 512) {
+        const f32x4 h0 = *reinterpret_cast<const f32x4*>(hr + c0), h1 = *reinterpret_cast<const f32x4*>(hr + c0 + 4);
+        f32x4 g0 = *reinterpret_cast<const f32x4*>(g + c0), g1 = *reinterpret_cast<const f32x4*>(g + c0 + 4);
+        const f32x4 b0 = *reinterpret_cast<const f32x4*>(bias + c0), b1 = *reinterpret_cast<const f32x4*>(bias + c0 + 4);
+        if (wrapped) { g0 += *reinterpret_cast<const f32x4*>(gw + c0); g1 += *reinterpret_cast<const f32x4*>(gw + c0 + 4); }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            acc += h0[e] > 0.f ? g0[e] * (h0[e] - b0[e]) : 0.f;
+            acc += h1[e] > 0.f ? g1[e] * (h1[e] - b1[e]) : 0.f;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if (lane == 0) out[r] = fabsf(acc * mul);
 }
 __global__ void tt_flip_taps_kernel(const float* __restrict__ w, float* __restrict__ out, int rows, int taps) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -180,20 +223,24 @@ extern "C" int amds_transmil_train_forward(const amds_transmil_cfg* cfg_host, co
     return amds_linear_f32(clsn, w.fc2_w, w.fc2_b, logits, Bb, d.C, Cd, 0, stream);
 }
 
-extern "C" int amds_transmil_train_backward(const amds_transmil_cfg* cfg_host, const amds_transmil_weights* w_host, const float* dlogits, float p_drop, uint64_t seed,
-                                            int n_bags, int n_tiles, const void* saved, size_t saved_bytes, const amds_transmil_grads* grads_host, float* dbags, void* ws,
-                                            size_t ws_bytes, void* stream) {
-    AMDS_REQUIRE(cfg_host && w_host && dlogits && saved && ws, "amds_transmil_train_backward: null pointer");
-    AMDS_REQUIRE(grads_host || dbags, "amds_transmil_train_backward: nothing to compute (no gradient buffers, no dbags)");
+// The backward's launch sequence.  `cam` NULL: amds_transmil_train_backward as declared.  `cam` set (amds_transmil_gradcam; no gradient buffers, no dbags, the lean
+// workspace plan): stops after layer1's LayerNorm backward and reduces dx against the saved h in ONE kernel -- cam[b * T + t] of the class `dlogits` selects.
+static int transmil_backward_body(const amds_transmil_cfg* cfg_host, const amds_transmil_weights* w_host, const float* dlogits, float p_drop, uint64_t seed, int n_bags,
+                                  int n_tiles, const void* saved, size_t saved_bytes, const amds_transmil_grads* grads_host, float* dbags, void* ws, size_t ws_bytes,
+                                  void* stream, float* cam) {
+    const char* who = cam ? "amds_transmil_gradcam" : "amds_transmil_train_backward";
+    AMDS_REQUIRE(cfg_host && w_host && dlogits && saved && ws, "%s: null pointer", who);
+    AMDS_REQUIRE(cam || grads_host || dbags, "amds_transmil_train_backward: nothing to compute (no gradient buffers, no dbags)");
+    AMDS_REQUIRE(!cam || (!grads_host && !dbags), "amds_transmil_gradcam: takes no gradient buffers");
     TtDims d; TtSaved s; TtWs k;
     RC(tt_dims(cfg_host, n_bags, n_tiles, &d));
     RC(tt_saved(d, &s));
-    RC(tt_ws(d, &k));
+    RC(tt_ws(d, &k, cam != nullptr));
     if (saved_bytes < s.total || ws_bytes < k.total) {
-        set_error("amds_transmil_train_backward: arena %zu / workspace %zu < required %zu / %zu bytes", saved_bytes, ws_bytes, s.total, k.total);
+        set_error("%s: arena %zu / workspace %zu < required %zu / %zu bytes", who, saved_bytes, ws_bytes, s.total, k.total);
         return AMDS_ERR_WORKSPACE;
     }
-    AMDS_REQUIRE((((uintptr_t)saved | (uintptr_t)ws) & 255) == 0, "amds_transmil_train_backward: arena and workspace must be 256-byte aligned");
+    AMDS_REQUIRE((((uintptr_t)saved | (uintptr_t)ws) & 255) == 0, "%s: arena and workspace must be 256-byte aligned", who);
     const amds_transmil_weights& w = *w_host;
     const amds_transmil_grads* G = grads_host;
     AMDS_REQUIRE(!G || (G->fc1_w && G->fc1_b && G->cls_token && G->ppeg_corr && G->norm_w && G->norm_b && G->fc2_w && G->fc2_b && G->layer[0].norm_w && G->layer[0].norm_b &&
@@ -246,6 +293,12 @@ extern "C" int amds_transmil_train_backward(const amds_transmil_cfg* cfg_host, c
     RC(amds_nystrom_attn_bwd(&w.layer[0], Cd, dx, dy, G ? &g1 : nullptr, Bb, n, p_drop, seed, 1, sv + s.ny1, s.ny_bytes, wk + k.ny, k.ny_bytes, stream));
     RC(amds_layernorm_bwd(dy, Cd, reinterpret_cast<const float*>(sv + s.x1), Cd, reinterpret_cast<const float*>(sv + s.mu1), reinterpret_cast<const float*>(sv + s.rs1),
                           w.layer[0].norm_w, dx, Cd, 1, G ? G->layer[0].norm_w : scratch, G ? G->layer[0].norm_b : scratch + Cd, 0, (int)M, Cd, wk + k.lnb, k.lnb_bytes, stream));
+    if (cam) {      // ---- Grad-CAM tail: tile rows, wrap-padding add, ReLU mask and the product with W_fc1 folded into one row-dot against h - b
+        hipLaunchKernelGGL(tt_cam_rowdot_kernel, dim3((unsigned)((Mt + 3) / 4)), dim3(256), 0, st, dx, reinterpret_cast<const float*>(sv + s.h), w.fc1_b, cam, Mt, T, n, d.add, Cd,
+                           1.0f / (float)F);
+        AMDS_LAUNCH_CHECK("tt_cam_rowdot_kernel");
+        return AMDS_OK;
+    }
     // ---- class token, wrap padding, ReLU, _fc1
     if (G) RC(colsum(dx, (long)n * Cd, G->cls_token, Bb, Cd));
     float *dh = reinterpret_cast<float*>(wk + k.dh), *dzh = reinterpret_cast<float*>(wk + k.dzh);
@@ -262,5 +315,43 @@ extern "C" int amds_transmil_train_backward(const amds_transmil_cfg* cfg_host, c
         RC(colsum(dzh, Cd, G->fc1_b, Mt, Cd));
     }
     if (dbags) RC(amds_bgemm_f32(dzh, Cd, 0, 0, w.fc1_w, F, 0, 0, 0, dbags, F, 0, 0, 1, 1, (int)Mt, F, Cd, 1.0f, 0.0f, nullptr, 0, stream));
+    return AMDS_OK;
+}
+
+extern "C" int amds_transmil_train_backward(const amds_transmil_cfg* cfg_host, const amds_transmil_weights* w_host, const float* dlogits, float p_drop, uint64_t seed,
+                                            int n_bags, int n_tiles, const void* saved, size_t saved_bytes, const amds_transmil_grads* grads_host, float* dbags, void* ws,
+                                            size_t ws_bytes, void* stream) {
+    return transmil_backward_body(cfg_host, w_host, dlogits, p_drop, seed, n_bags, n_tiles, saved, saved_bytes, grads_host, dbags, ws, ws_bytes, stream, nullptr);
+}
+
+// ---- amds_transmil_gradcam (include/amdstamp.h): |mean_f feats * d logit_c / d feats| per tile and class, no [tiles][n_feats] tensor ----------------------------
+extern "C" size_t amds_transmil_gradcam_workspace_bytes(const amds_transmil_cfg* cfg_host, int n_bags, int n_tiles) {
+    TtDims d; TtWs w;
+    if (tt_dims(cfg_host, n_bags, n_tiles, &d) != AMDS_OK || tt_ws(d, &w, true) != AMDS_OK) return 0;
+    return w.total;
+}
+
+extern "C" int amds_transmil_gradcam(const amds_transmil_cfg* cfg_host, const amds_transmil_weights* w_host, int n_bags, int n_tiles, const void* saved, size_t saved_bytes,
+                                     float* cam_raw, void* ws, size_t ws_bytes, void* stream) {
+    AMDS_REQUIRE(cfg_host && w_host && saved && cam_raw && ws, "amds_transmil_gradcam: null pointer");
+    if (n_bags == 0) return AMDS_OK;
+    TtDims d; TtSaved s; TtWs k;
+    RC(tt_dims(cfg_host, n_bags, n_tiles, &d));
+    RC(tt_saved(d, &s));
+    RC(tt_ws(d, &k, true));
+    if (saved_bytes < s.total || ws_bytes < k.total) {
+        set_error("amds_transmil_gradcam: arena %zu / workspace %zu < required %zu / %zu bytes", saved_bytes, ws_bytes, s.total, k.total);
+        return AMDS_ERR_WORKSPACE;
+    }
+    AMDS_REQUIRE((((uintptr_t)saved | (uintptr_t)ws) & 255) == 0, "amds_transmil_gradcam: arena and workspace must be 256-byte aligned");
+    AMDS_REQUIRE(w_host->fc1_b && ((uintptr_t)w_host->fc1_b & 15) == 0, "amds_transmil_gradcam: fc1_b must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    float* basis = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + k.dlt);       // [n_bags][classes]: dlogits = e_c for every bag, refilled per class
+    const long Mt = (long)d.Bb * d.T;
+    for (int c = 0; c < d.C; ++c) {
+        hipLaunchKernelGGL(tt_cam_basis_kernel, dim3((d.Bb * d.C + 255) / 256), dim3(256), 0, st, basis, d.Bb, d.C, c);
+        AMDS_LAUNCH_CHECK("tt_cam_basis_kernel");
+        RC(transmil_backward_body(cfg_host, w_host, basis, 0.0f, 0, n_bags, n_tiles, saved, saved_bytes, nullptr, nullptr, ws, ws_bytes, stream, cam_raw + (size_t)c * Mt));
+    }
     return AMDS_OK;
 }

@@ -13,6 +13,10 @@ Two routes to the Grad-CAM scores:
     bf16 operands and `model.fp16_overflow_events += 1`.
   * jacrev (any module with the reference's ``forward(bags, coords=, mask=)``: TransMIL, a torch model; can be forced for the `vit` head): the
     reference's own three lines on the device.
+  * library (`method="library"`, "the head's one-library-call Grad-CAM"): for the `vit` head the fused route above; for `stamp_amd.mil.TransMIL` one
+    eval-mode training forward (`transmil_core.forward_train`), ONE library call for all classes (`transmil_core.gradcam` -> amds_transmil_gradcam: per class
+    the backward's launches without parameter gradients down to `_fc1`, then a row-dot against the saved `_fc1` output) and amds_softmax_over_tiles.  fp32
+    throughout, operand precision from `torch.get_float32_matmul_precision()` like the module: no fp16, so no overflow re-run.  "auto" does not pick it.
 The module is put in eval mode for the duration of a call; ALiBi running means are not updated; no parameter receives a `.grad` and `feats` needs no
 `requires_grad`.  There is no CPU fallback: CPU tensors raise.
 """
@@ -23,8 +27,8 @@ from dataclasses import dataclass
 
 import torch
 
-from . import _lib, mil_core, ops
-from .mil import VisionTransformer, _all_finite
+from . import _lib, mil_core, ops, transmil_core
+from .mil import TransMIL, VisionTransformer, _all_finite
 
 _FP16_SCALE = 1024.0            # the power of two the fp16 basis vectors carry (as `_MilVitFunction`'s loss scale)
 MAX_BAGS_PER_CALL = 32768       # one-tile bags per inference call of `tile_scores` (the attention kernels' grids take at most 65535 bags)
@@ -50,9 +54,15 @@ def _check_inputs(feats: torch.Tensor, coords: torch.Tensor | None) -> None:
 
 
 def _pick(model, method: str) -> str:
-    if method not in ("auto", "fused", "jacrev"):
-        raise ValueError(f"method must be 'auto', 'fused' or 'jacrev', got {method!r}")
+    if method not in ("auto", "fused", "jacrev", "library"):
+        raise ValueError(f"method must be 'auto', 'fused', 'jacrev' or 'library', got {method!r}")
     fused_ok = isinstance(model, VisionTransformer)
+    if method == "library":          # the head's one-library-call Grad-CAM
+        if fused_ok:
+            return "fused"
+        if isinstance(model, TransMIL):
+            return "library"
+        raise ValueError(f"method='library' needs a stamp_amd.mil.VisionTransformer or stamp_amd.mil.TransMIL, got {type(model).__name__}")
     if method == "fused" and not fused_ok:
         raise ValueError(f"method='fused' needs a stamp_amd.mil.VisionTransformer, got {type(model).__name__}")
     return ("fused" if fused_ok else "jacrev") if method == "auto" else method
@@ -81,6 +91,17 @@ def _cam_raw_fused(model: VisionTransformer, feats: torch.Tensor, coords: torch.
         model.fp16_overflow_events += 1         # an fp16 activation or gradient overflowed: the same slide on bf16 operands (fp32's range)
     pk, _, saved = forward(torch.bfloat16)
     return mil_core.gradcam(pk, saved, scale=1.0)
+
+
+def _cam_raw_transmil(model: TransMIL, feats: torch.Tensor) -> torch.Tensor:
+    """-> cam_raw [C, N] (module docstring, the library route of the TransMIL head; coords are ignored like in its forward)."""
+    F = model._fc1[0].in_features
+    if feats.shape[1] != F:
+        raise ValueError(f"feats must be [tiles, {F}], got {tuple(feats.shape)}")
+    if feats.shape[0] < 1:
+        raise ValueError("empty bag")
+    _, saved = transmil_core.forward_train(model._get(feats.device), feats.detach().unsqueeze(0), (F, model.dim_hidden, model.n_classes), training=False)
+    return transmil_core.gradcam(saved)
 
 
 def _cam_raw_jacrev(model: torch.nn.Module, feats: torch.Tensor, coords: torch.Tensor | None, squeeze_all: bool) -> torch.Tensor:
@@ -112,12 +133,12 @@ def _softmax_over_tiles(cam_raw: torch.Tensor) -> torch.Tensor:
 def gradcam(model: torch.nn.Module, feats: torch.Tensor, coords: torch.Tensor | None = None, *, raw: bool = False, method: str = "auto") -> torch.Tensor:
     """reference `_gradcam_per_category` (:36-56): feats [N, F] fp16 / fp32, coords [N, 2] (micrometres; required by an ALiBi head) -> [N, C] fp32, the
     per-class Grad-CAM scores soft-maxed over the tiles; `raw=True`: the scores before that softmax (line 54), [N, C].  `method`: "auto" (fused for the
-    HIP `vit` head, else jacrev), "fused", "jacrev"."""
+    HIP `vit` head, else jacrev), "fused", "jacrev", "library" (the head's one-library-call Grad-CAM: `vit` as "fused", TransMIL through amds_transmil_gradcam)."""
     _check_inputs(feats, coords)
     route = _pick(model, method)
     with _eval_mode(model):
-        if route == "fused":
-            cam_raw = _cam_raw_fused(model, feats, coords)
+        if route in ("fused", "library"):
+            cam_raw = _cam_raw_fused(model, feats, coords) if route == "fused" else _cam_raw_transmil(model, feats)
             return cam_raw.t().contiguous() if raw else _softmax_over_tiles(cam_raw)
         cam_raw = _cam_raw_jacrev(model, feats, coords, squeeze_all=False)
         if cam_raw.dim() != 2:
@@ -135,27 +156,73 @@ def gradcam_single(model: torch.nn.Module, feats: torch.Tensor, coords: torch.Te
     with _eval_mode(model):
         if route == "fused":
             return _cam_raw_fused(model, feats, coords)[0]
+        if route == "library":
+            return _cam_raw_transmil(model, feats)[0]
         cam = _cam_raw_jacrev(model, feats, coords, squeeze_all=True)
         if cam.dim() != 1:
             raise ValueError(f"gradcam_single is for single-output models, the Jacobian reduced to {tuple(cam.shape)}")
         return cam
 
 
+def _largest_fitting(need_bytes, budget: int, limit: int) -> int:
+    """The largest bag count in [1, limit] with need_bytes(bags) <= budget (need_bytes grows with the bag count: bisection); 1 if not even one bag fits --
+    the call itself then reports what it needs."""
+    if need_bytes(limit) <= budget:
+        return limit
+    lo, hi = 1, limit - 1
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if need_bytes(mid) <= budget:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
+def default_tiles_per_call(model: torch.nn.Module, device=None) -> int:
+    """The default chunk of `tile_scores`.  `mil.TransMIL`: the largest bag count <= transmil_core.MAX_BAGS_PER_CALL (bags x 8 heads is one launch's batch
+    dimension) whose amds_transmil_workspace_bytes(cfg, bags, 1) fits in half of the free device memory -- a one-tile bag is padded to dim_hidden / 2 token
+    rows and carries 8 heads of attention matrices.  Any other module: MAX_BAGS_PER_CALL."""
+    if not isinstance(model, TransMIL):
+        return MAX_BAGS_PER_CALL
+    import ctypes as C
+    cfg = _lib.TransMilCfg(model._fc1[0].in_features, model.dim_hidden, model.n_classes)
+    query = _lib.lib().amds_transmil_workspace_bytes
+    return _largest_fitting(lambda bags: query(C.byref(cfg), bags, 1), torch.cuda.mem_get_info(device)[0] // 2, transmil_core.MAX_BAGS_PER_CALL)
+
+
 def tile_scores(model: torch.nn.Module, feats: torch.Tensor, coords: torch.Tensor | None = None, *, tiles_per_call: int | None = None) -> torch.Tensor:
     """reference :417-427: every tile as a bag of its own under an all-False mask, softmax over the classes -> [N, C] fp32.  The module's masked inference
-    forward in chunks of `tiles_per_call` bags (default: all at once, at most MAX_BAGS_PER_CALL per call); one chunk equals
-    ``torch.softmax(model(feats.unsqueeze(-2), coords=coords.unsqueeze(-2), mask=zeros), 1)`` bit for bit."""
+    forward in chunks of `tiles_per_call` bags (default: `default_tiles_per_call`); one chunk equals
+    ``torch.softmax(model(feats.unsqueeze(-2), coords=coords.unsqueeze(-2), mask=zeros), 1)`` bit for bit.
+
+    `mil.TransMIL`: the bags of one call are NOT independent -- each pseudo-inverse starts from maxima over all bags of the call (trans_mil.py:26-28) --, so
+    the chunks whose rows equal the module's own call are fixed: consecutive groups of transmil_core.MAX_BAGS_PER_CALL (8191) tiles, the most one
+    forward takes.  `tiles_per_call` (default: what half of the free memory allows; above 8191 raises) only bounds the bags of one LIBRARY call: a group that
+    needs several runs staged (`transmil_core.forward_infer_grouped`: three passes, the maxima on the device, sub-call sizes that repeat the one call's
+    kernel choices) with the bits of the one call, so the result depends neither on `tiles_per_call` nor on the free memory.  This CHANGES what an explicit
+    `tiles_per_call` below the slide size returned for a TransMIL before: independent chunks then, each with its own maxima (3e-4 apart in the
+    probabilities); the group's bits now.  Every other call returns the bits it returned."""
     _check_inputs(feats, coords)
     N = feats.shape[0]
-    step = MAX_BAGS_PER_CALL if tiles_per_call is None else int(tiles_per_call)
+    step = default_tiles_per_call(model, feats.device) if tiles_per_call is None else int(tiles_per_call)
     if step < 1:
         raise ValueError("tiles_per_call must be >= 1")
+    group = step
+    if isinstance(model, TransMIL):
+        group = transmil_core.MAX_BAGS_PER_CALL
+        if step > group:
+            raise ValueError(f"tiles_per_call={step} exceeds the TransMIL forward's limit of {group} bags per call")
     outs = []
     with _eval_mode(model), torch.no_grad():
-        for a in range(0, N, step):
-            e = min(N, a + step)
-            logits = model(feats[a:e].unsqueeze(-2), coords=None if coords is None else coords[a:e].unsqueeze(-2),
-                           mask=torch.zeros(e - a, 1, dtype=torch.bool, device=feats.device))
+        for a in range(0, N, group):
+            e = min(N, a + group)
+            if e - a > step:          # (TransMIL alone: group == step for every other module)
+                dims = (model._fc1[0].in_features, model.dim_hidden, model.n_classes)
+                logits = transmil_core.forward_infer_grouped(model._c_weights(feats.device), dims, feats[a:e].unsqueeze(-2), step)
+            else:
+                logits = model(feats[a:e].unsqueeze(-2), coords=None if coords is None else coords[a:e].unsqueeze(-2),
+                               mask=torch.zeros(e - a, 1, dtype=torch.bool, device=feats.device))
             outs.append(torch.softmax(logits, dim=1))
     return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
 
@@ -239,9 +306,11 @@ class SlideHeatmap:
     tile_relevance: torch.Tensor | None = None  # regression: gradcam / max [N] (:593)
 
 
-def slide_heatmap(model: torch.nn.Module, feats: torch.Tensor, coords_um: torch.Tensor, *, task: str) -> SlideHeatmap:
+def slide_heatmap(model: torch.nn.Module, feats: torch.Tensor, coords_um: torch.Tensor, *, task: str, method: str = "auto",
+                  tiles_per_call: int | None = None) -> SlideHeatmap:
     """One slide, `task` "classification" (:401-498) or "regression" (:586-597): slide score, Grad-CAM scores, per-tile scores, their 2-D arrangements and
-    the per-category maps -- the tensors the reference's plotting takes from here."""
+    the per-category maps -- the tensors the reference's plotting takes from here.  `method` goes to `gradcam` / `gradcam_single`, `tiles_per_call` to
+    `tile_scores`."""
     if task not in ("classification", "regression"):
         raise ValueError(f"task must be 'classification' or 'regression', got {task!r}")
     _check_inputs(feats, coords_um)
@@ -249,11 +318,11 @@ def slide_heatmap(model: torch.nn.Module, feats: torch.Tensor, coords_um: torch.
         logits = model(feats.unsqueeze(0), coords=coords_um.unsqueeze(0), mask=None).squeeze(0)          # :392-399
     cn = grid_coords(coords_um)
     if task == "regression":
-        cam = gradcam_single(model, feats, coords_um)
+        cam = gradcam_single(model, feats, coords_um, method=method)
         g2 = vals_to_im(cam, cn)
         g2 = (g2 - g2.min()) / (g2.max() - g2.min() + 1e-8)
         return SlideHeatmap(task, logits.squeeze(), cn, cam, g2, tile_relevance=cam / cam.max().clamp(min=1e-8))
-    cam = gradcam(model, feats, coords_um)
-    scores = tile_scores(model, feats, coords_um)
+    cam = gradcam(model, feats, coords_um, method=method)
+    scores = tile_scores(model, feats, coords_um, tiles_per_call=tiles_per_call)
     support, attention, cat = category_maps(cam, scores)
     return SlideHeatmap(task, logits.softmax(0), cn, cam, vals_to_im(cam, cn), scores, vals_to_im(scores, cn), support, attention, cat)

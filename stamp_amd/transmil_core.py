@@ -249,6 +249,29 @@ def backward(saved: dict, dlogits: torch.Tensor, *, need_params: bool = True, ne
     return G, (dbags.view(Bb, Tn, Fd) if need_bags else None)
 
 
+def gradcam(saved: dict) -> torch.Tensor:
+    """-> cam_raw [C, Bb * T] fp32, |mean_f bags * d logit_c / d bags| for every tile and class (the reference's Grad-CAM scores before the softmax) from the
+    `saved` dict of an eval-mode `forward_train` (training=False): ONE library call (amds_transmil_gradcam) that loops over the class basis vectors and never
+    forms dbags or the [C, tiles, dim_input] Jacobian.  The arena is read with the `cfg` that forward resolved."""
+    import ctypes as C
+    if saved["p_out"] != 0.0:
+        raise ValueError("gradcam needs the arena of a forward with dropout off (forward_train(..., training=False))")
+    _, _, Cc = saved["dims"]
+    Bb, Tn, _ = saved["shape"]
+    arena = saved["arena"]
+    dev = arena.device
+    lib = _lib.lib()
+    need = lib.amds_transmil_gradcam_workspace_bytes(C.byref(saved["cfg"]), Bb, Tn)
+    if need == 0:
+        _lib.check(-1, "transmil_gradcam_workspace_bytes")
+    ws = ops.scratch("transmil_gradcam", dev, need)
+    cam = torch.empty(Cc, Bb * Tn, dtype=torch.float32, device=dev)
+    ops.sync_float32_matmul_precision()
+    _lib.check(lib.amds_transmil_gradcam(C.byref(saved["cfg"]), C.byref(saved["w"]), Bb, Tn, arena.data_ptr(), arena.numel(), cam.data_ptr(), ws.data_ptr(), ws.numel(),
+                                         ops._stream()), "transmil_gradcam")
+    return cam
+
+
 def forward_infer(w: "_lib.TransMilWeights", dims: tuple[int, int, int], h: torch.Tensor) -> torch.Tensor:
     """Bags [Bb, T, dim_input] -> logits [Bb, dim_output]: the deploy / validation forward, ONE library call (amds_transmil_forward, csrc/transmil_fwd.hip)
     on the fp32 weights `w` points to (`TransMIL.forward` in eval mode, and `HipTransMilTrainer.predict` on its flat master buffer)."""
@@ -271,6 +294,60 @@ def forward_infer(w: "_lib.TransMilWeights", dims: tuple[int, int, int], h: torc
     ops.sync_float32_matmul_precision()
     _lib.check(lib.amds_transmil_forward(C.byref(cfg), C.byref(w), h.data_ptr(), ops._DT[h.dtype], logits.data_ptr(), Bb, Tn, ws.data_ptr(), ws.numel(), ops._stream()),
                "transmil_forward")
+    return logits
+
+
+def staged_partition(ok, group: int, step: int) -> list[int]:
+    """Sub-call sizes for a group of `group` bags, none above `step`, every one accepted by `ok(bags)` (amds_transmil_staged_compatible: the sub-call repeats the
+    kernel choices of the one call over the group): the largest accepted size whose remainder is accepted too (whole tiles: multiples of a tile), else the fewest
+    near-equal parts of two accepted sizes (no part too small).  Host only."""
+    if group <= step:
+        return [group]
+    for s in range(step, 0, -1):
+        r = group % s
+        if ok(s) and (r == 0 or ok(r)):
+            return [s] * (group // s) + ([r] if r else [])
+    for k in range(-(-group // step), group + 1):
+        base, extra = divmod(group, k)
+        if base + (1 if extra else 0) <= step and ok(base) and (extra == 0 or ok(base + 1)):
+            return [base + 1] * extra + [base] * (k - extra)
+    raise RuntimeError(f"no split of {group} bags into library calls of at most {step} bags repeats the kernel choices of one call: raise tiles_per_call")
+
+
+def forward_infer_grouped(w: "_lib.TransMilWeights", dims: tuple[int, int, int], h: torch.Tensor, bags_per_call: int) -> torch.Tensor:
+    """`forward_infer(w, dims, h)` for a group of bags [Bb, T, dim_input] in library calls of at most `bags_per_call` bags, bit for bit.  The bags of a call meet
+    in the pseudo-inverse's maxima (trans_mil.py:26-28), so the group runs three times over its sub-calls (amds_transmil_forward_staged) -- layer1's maxima,
+    layer2's maxima, the logits -- with the maxima in 16 bytes on the device; and in the kernel the two whole-call products (`_fc1`, `to_qkv`) pick by their
+    row count, so the sub-call sizes come from `staged_partition`: they may be smaller than `bags_per_call` asks, never larger."""
+    import ctypes as C
+    Fd, Cd, Cc = dims
+    Bb, Tn, F = h.shape
+    if F != Fd:
+        raise ValueError(f"bags must be [batch, tile, {Fd}], got {tuple(h.shape)}")
+    if int(bags_per_call) < 1:
+        raise ValueError("bags_per_call must be >= 1")
+    if Bb <= int(bags_per_call):
+        return forward_infer(w, dims, h)
+    dev = h.device
+    if h.dtype not in ops._DT:
+        h = h.float()
+    h = h.contiguous()
+    cfg = _lib.TransMilCfg(Fd, Cd, Cc)
+    lib = _lib.lib()
+    parts = staged_partition(lambda s: bool(lib.amds_transmil_staged_compatible(C.byref(cfg), Bb, s, Tn)), Bb, min(int(bags_per_call), MAX_BAGS_PER_CALL))
+    need = lib.amds_transmil_workspace_bytes(C.byref(cfg), max(parts), Tn)
+    if need == 0:
+        _lib.check(-1, "transmil_workspace_bytes")
+    ws = ops.scratch("transmil", dev, need)
+    maxima = torch.zeros(4, dtype=torch.int32, device=dev)
+    logits = torch.empty(Bb, Cc, dtype=torch.float32, device=dev)
+    ops.sync_float32_matmul_precision()
+    for stage in (0, 1, 2):
+        a = 0
+        for n in parts:
+            _lib.check(lib.amds_transmil_forward_staged(C.byref(cfg), C.byref(w), h[a:a + n].data_ptr(), ops._DT[h.dtype], logits[a:a + n].data_ptr(), n, Tn, Bb, stage,
+                                                        maxima.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()), "transmil_forward_staged")
+            a += n
     return logits
 
 

@@ -6,8 +6,13 @@ warmed up, median of --reps calls (host clock around a device synchronise), the 
 
     python tools/heatmap_only.py [--out DIR] [--reps N] [--sizes 1024,8192] [--feats 1024] [--classes 2,4] [--alibi] [--precision high|medium]
     python tools/heatmap_only.py --profile-call [--sizes 8192]
+    python tools/heatmap_only.py --model transmil [--hidden 512] [--precision high|highest] [--routes library,jacrev] [--count-launches]
 
---profile-call: one fused `gradcam` call at the first size / F / C after a warm-up, nothing else (for `rocprofv3 --kernel-trace --stats -- python ...`)."""
+--profile-call: one fused `gradcam` call at the first size / F / C after a warm-up, nothing else (for `rocprofv3 --kernel-trace --stats -- python ...`); with
+--model transmil the call is the first of --routes.
+--model transmil: `stamp_amd.mil.TransMIL` (dim_hidden --hidden), routes "library" (one amds_transmil_gradcam call) and "jacrev" (one amds_transmil_train_backward
+per class, the [C, N, F] Jacobian, the reduction), interleaved like the pair above; writes heatmap_transmil_ab_<precision>.{txt,json}.  --count-launches: the device kernels of
+one call of each route (torch.profiler), also per class."""
 import argparse
 import json
 import statistics
@@ -19,7 +24,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch  # noqa: E402
 
 from stamp_amd import heatmaps, mil_core  # noqa: E402
-from stamp_amd.mil import VisionTransformer  # noqa: E402
+from stamp_amd.mil import TransMIL, VisionTransformer  # noqa: E402
 
 
 def timed(fn, reps):
@@ -51,6 +56,69 @@ def slide(n, f, seed=1):
     return feats, coords
 
 
+def count_kernels(fn):
+    """Device kernels launched by one call of `fn` (None where the profiler gives no device events)."""
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    n = sum(1 for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA") and "memcpy" not in e.name.lower() and "memset" not in e.name.lower())
+    return n or None
+
+
+def main_transmil(args, sizes, fs, cs):
+    routes = args.routes.split(",")
+    assert all(r in ("library", "jacrev") for r in routes) and routes, routes
+    call = lambda m, feats, route: heatmaps.gradcam(m, feats, raw=True, method=route)  # noqa: E731
+
+    def model(f, c):
+        torch.manual_seed(1)
+        return TransMIL(dim_output=c, dim_input=f, dim_hidden=args.hidden).cuda().eval()
+
+    if args.profile_call:
+        m = model(fs[0], cs[0])
+        feats, _ = slide(sizes[0], fs[0])
+        for _ in range(2):
+            call(m, feats, routes[0])
+            torch.cuda.synchronize()
+        print(f"profiled one TransMIL {routes[0]} gradcam call: N={sizes[0]} F={fs[0]} C={cs[0]} dim_hidden={args.hidden} precision={args.precision}")
+        return
+    rows, lines = [], []
+    for f in fs:
+        for c in cs:
+            m = model(f, c)
+            for n in sizes:
+                feats, _ = slide(n, f)
+                res = {"N": n, "F": f, "C": c, "dim_hidden": args.hidden, "precision": args.precision}
+                try:
+                    for run in (0, 1):                              # the routes twice, alternated: run-to-run spread
+                        for r in reversed(routes):
+                            res[f"{r}_ms_run{run}"] = round(timed(lambda: call(m, feats, r), args.reps) * 1e3, 3)
+                    for r in routes:
+                        res[f"{r}_peak_MiB"] = round(peak(lambda: call(m, feats, r)) / 2 ** 20, 1)
+                        if args.count_launches:
+                            res[f"{r}_kernels"] = count_kernels(lambda: call(m, feats, r))
+                    line = f"N={n:6d} F={f} C={c} hidden={args.hidden} {args.precision}: " + ", ".join(
+                        f"{r} {res[f'{r}_ms_run0']:9.2f} / {res[f'{r}_ms_run1']:9.2f} ms peak {res[f'{r}_peak_MiB']:.0f} MiB"
+                        + (f" kernels {res[f'{r}_kernels']} ({(res[f'{r}_kernels'] or 0) / c:.1f} per class)" if args.count_launches else "") for r in routes)
+                    if len(routes) == 2:
+                        line += "; jacrev / library " + " / ".join(f"{res[f'jacrev_ms_run{k}'] / res[f'library_ms_run{k}']:.3f}" for k in (0, 1))
+                    lines.append(line)
+                except (RuntimeError, torch.OutOfMemoryError) as e:          # a size the library or the memory does not take: said, not hidden
+                    res["skipped"] = str(e).splitlines()[0][:300]
+                    lines.append(f"N={n:6d} F={f} C={c}: skipped ({res['skipped']})")
+                print(lines[-1], flush=True)
+                rows.append(res)
+                del feats
+                torch.cuda.empty_cache()
+    if args.out:
+        out = Path(args.out)
+        out.mkdir(parents=True, exist_ok=True)
+        (out / f"heatmap_transmil_ab_{args.precision}.json").write_text(json.dumps({"device": torch.cuda.get_device_name(0), "reps": args.reps, "rows": rows}, indent=1) + "\n")
+        (out / f"heatmap_transmil_ab_{args.precision}.txt").write_text("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -59,11 +127,19 @@ def main():
     ap.add_argument("--feats", default="1024,1536")
     ap.add_argument("--classes", default="2,4")
     ap.add_argument("--alibi", action="store_true")
-    ap.add_argument("--precision", default="high", choices=["high", "medium"])
+    ap.add_argument("--precision", default="high", choices=["high", "medium", "highest"])
     ap.add_argument("--profile-call", action="store_true")
+    ap.add_argument("--model", default="vit", choices=["vit", "transmil"])
+    ap.add_argument("--hidden", type=int, default=512)
+    ap.add_argument("--routes", default="library,jacrev")
+    ap.add_argument("--count-launches", action="store_true")
     args = ap.parse_args()
     sizes, fs, cs = ([int(v) for v in s.split(",")] for s in (args.sizes, args.feats, args.classes))
     torch.set_float32_matmul_precision(args.precision)
+    if args.model == "transmil":
+        return main_transmil(args, sizes, fs, cs)
+    if args.precision == "highest":
+        ap.error("--precision highest is for --model transmil (the vit head's operands are 16-bit)")
 
     def model(f, c):
         torch.manual_seed(1)

@@ -705,6 +705,50 @@ def golden_heatmaps() -> None:
         save(f"heatmaps_{tag}.npz", **arrs)
 
 
+def golden_heatmaps_transmil() -> None:
+    """The heat-map quantities of the reference's own TransMIL (models/trans_mil.py) from the reference's own functions (src/stamp/heatmaps/__init__.py):
+    `_gradcam_per_category` :36-56, `_gradcam_single` :115-139, the slide logits :392-399 and the one-tile-bag scores :417-427, as `golden_heatmaps` does for
+    the `vit` head.  One C = 3 model and a dim_output = 1 twin on three slides: N = 61 (side 8, 3 wrap-padded tiles), 50 (14) and 49 (none).  Keys carry the
+    slide's tile count: feats_61, cam_raw_61 [N, C], ..."""
+    from typing import Optional, cast
+
+    from torch import Tensor
+    from torch.func import jacrev
+
+    tm = sys.modules.get("stamp.modeling.models.trans_mil") or load_by_path("stamp.modeling.models.trans_mil", REF / "modeling" / "models" / "trans_mil.py")
+    glb = exec_defs(REF / "heatmaps" / "__init__.py", {"_gradcam_per_category", "_gradcam_single"},
+                    dict(torch=torch, Tensor=Tensor, jacrev=jacrev, cast=cast, Optional=Optional))
+
+    class OneLogit(torch.nn.Module):
+        def __init__(self, model, c):
+            super().__init__()
+            self.model, self.c = model, c
+
+        def forward(self, bags, *, coords, mask):
+            return self.model(bags, coords=coords, mask=mask)[:, self.c]
+
+    C, F, D, GW = 3, 40, 64, 9
+    torch.manual_seed(41)
+    model = tm.TransMIL(dim_output=C, dim_input=F, dim_hidden=D).eval()
+    single = tm.TransMIL(dim_output=1, dim_input=F, dim_hidden=D).eval()
+    with torch.no_grad():       # a head as a trained one has it: class rows that differ (a fresh Linear's rows give nearly parallel maps)
+        model._fc2.weight.mul_(4.0)
+    arrs = dict(hparams=np.array([C, F, D]), slides=np.array([61, 50, 49]), **sd_np(model), **sd_np(single, "single:"))
+    for N in (61, 50, 49):
+        feats = torch.randn(N, F)
+        cells = torch.randperm(GW * 8)[:N]
+        coords_um = torch.stack([cells % GW, cells // GW], dim=1).float() * 256.0
+        cam = glb["_gradcam_per_category"](model, feats, coords_um).detach()
+        cam_raw = torch.stack([glb["_gradcam_single"](OneLogit(model, c), feats, coords_um).detach() for c in range(C)], dim=1)
+        cam_single = glb["_gradcam_single"](single, feats, coords_um).detach()
+        with torch.no_grad():
+            slide_logits = model(feats.unsqueeze(0), coords=coords_um.unsqueeze(0), mask=None).squeeze(0)
+            scores = torch.softmax(model(feats.unsqueeze(-2), coords=coords_um.unsqueeze(-2), mask=torch.zeros(N, 1, dtype=torch.bool)), dim=1)
+        for k, v in dict(feats=feats, coords_um=coords_um, cam=cam, cam_raw=cam_raw, cam_single=cam_single, slide_logits=slide_logits, scores=scores).items():
+            arrs[f"{k}_{N}"] = v.numpy()
+    save("heatmaps_transmil.npz", **arrs)
+
+
 def golden_transmil() -> None:
     tm = load_by_path("stamp.modeling.models.trans_mil", REF / "modeling" / "models" / "trans_mil.py")
     for tag, T, dim_in, dim_h in (("t50", 50, 24, 64), ("t300", 300, 32, 64)):
@@ -1253,6 +1297,7 @@ def main() -> None:
     golden_mil_vit()
     golden_mil_vit_train()
     golden_heatmaps()
+    golden_heatmaps_transmil()
     golden_transmil()
     golden_mlp_cox_transforms()
     golden_bag()
