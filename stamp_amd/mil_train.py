@@ -381,7 +381,8 @@ def _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, per_ca
 
 
 def fit(trainer: "HipMilVitTrainer | HipTransMilTrainer", train_batches, valid_batches, *, max_epochs: int, patience: int = 16, class_weights=None,
-        loss_fn=None, log=None, valid_bags_per_call: int = 1, monitor: str = "validation_loss", valid_auroc: bool = False) -> dict:
+        loss_fn=None, log=None, valid_bags_per_call: int = 1, monitor: str = "validation_loss", valid_auroc: bool = False,
+        valid_auprc: bool = False) -> dict:
     """The epoch loop of the reference's `train_model_` (src/stamp/modeling/train.py:504-564) around `HipMilVitTrainer.step` or
     `transmil_train.HipTransMilTrainer.step` (any object with their step / predict / predict_ragged / epoch_end / P drives it).
 
@@ -411,13 +412,18 @@ def fit(trainer: "HipMilVitTrainer | HipTransMilTrainer", train_batches, valid_b
 
     valid_auroc=True (classification, loss_fn=None): hist["validation_auroc"] holds, per epoch, the mean one-vs-rest AUROC
     ``metrics.multiclass_auroc(softmax(logits), argmax(targets))`` over the validation set (the reference logs it for every classification run,
-    models/__init__.py:217, 270-277); selection is unchanged."""
+    models/__init__.py:217, 270-277); selection is unchanged.
+    valid_auprc=True (same conditions): hist["validation_auprc"] holds, per epoch, the mean one-vs-rest average precision
+    ``metrics.multiclass_auprc(softmax(logits), argmax(targets))`` over the whole validation set (amds_binary_curves), from the same kept logits as
+    valid_auroc; selection is unchanged, and with the flag off neither the history nor a bit of the run changes."""
     if valid_bags_per_call < 1:
         raise ValueError("valid_bags_per_call must be >= 1")
     if monitor not in ("validation_loss", "val_cindex"):
         raise ValueError(f"monitor must be 'validation_loss' or 'val_cindex', got {monitor!r}")
     if valid_auroc and (loss_fn is not None or monitor != "validation_loss"):
         raise ValueError("valid_auroc=True applies to classification: loss_fn=None, monitor='validation_loss'")
+    if valid_auprc and (loss_fn is not None or monitor != "validation_loss"):
+        raise ValueError("valid_auprc=True applies to classification: loss_fn=None, monitor='validation_loss'")
     cindex = monitor == "val_cindex"
     dev = trainer.dev
     best = {"loss": float("-inf") if cindex else float("inf"), "epoch": -1, "P": None}
@@ -426,6 +432,8 @@ def fit(trainer: "HipMilVitTrainer | HipTransMilTrainer", train_batches, valid_b
         hist.update(val_cox_loss=[], val_cindex=[], train_pred_median=[])
     if valid_auroc:
         hist["validation_auroc"] = []
+    if valid_auprc:
+        hist["validation_auprc"] = []
     wait = 0
     skipped = getattr(trainer, "skipped_steps", 0)          # (any object with the trainer's step / predict / epoch_end drives this loop)
     for epoch in range(max_epochs):
@@ -450,7 +458,7 @@ def fit(trainer: "HipMilVitTrainer | HipTransMilTrainer", train_batches, valid_b
                 f"loss scale now {trainer.current_loss_scale:g}")
         skipped = now
         vtot, vcnt = 0.0, 0
-        kept = [] if cindex or valid_auroc else None          # every validation batch's (logits, targets), on the device
+        kept = [] if cindex or valid_auroc or valid_auprc else None          # every validation batch's (logits, targets), on the device
         if valid_bags_per_call > 1:
             vtot, vcnt = _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, valid_bags_per_call, kept, not cindex)
         for bags, coords, _sizes, targets in (valid_batches() if valid_bags_per_call == 1 else ()):
@@ -466,9 +474,13 @@ def fit(trainer: "HipMilVitTrainer | HipTransMilTrainer", train_batches, valid_b
             vtot += float(vl) * bags.shape[0]
             vcnt += bags.shape[0]
         vloss = vtot / max(vcnt, 1)
-        if valid_auroc:
+        if valid_auroc or valid_auprc:
             lg_all, y_all = torch.cat([lg.float() for lg, _ in kept]), torch.cat([t.float() for _, t in kept])
-            hist["validation_auroc"].append(float(metrics.multiclass_auroc(torch.softmax(lg_all, dim=1), y_all.argmax(dim=1))[1]))
+            probs_all, cls_all = torch.softmax(lg_all, dim=1), y_all.argmax(dim=1)
+            if valid_auroc:
+                hist["validation_auroc"].append(float(metrics.multiclass_auroc(probs_all, cls_all)[1]))
+            if valid_auprc:
+                hist["validation_auprc"].append(float(metrics.multiclass_auprc(probs_all, cls_all)[1]))
         score = vloss
         if cindex:
             y = torch.cat([t.float().reshape(-1, 2) for _, t in kept]) if kept else torch.zeros(0, 2, device=dev)
