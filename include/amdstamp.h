@@ -1038,6 +1038,48 @@ int amds_softmax_over_tiles(const float* in, float* out, int classes, long n, vo
  * read) and returns AMDS_ERR_INVALID if there was one (`out` is then unspecified). */
 int amds_scatter_grid(const float* vals, const int64_t* xy, float* out, int* cell_ws, long n, int k, int h, int w, void* stream);
 
+/* The first pass of amds_scatter_grid alone: cell_ws int32 [h * w + 1], cell_ws[y * w + x] = the highest tile index that names the cell, -1 where no tile
+ * lies (the last element is the out-of-grid count).  Same limits, same synchronising check and error as amds_scatter_grid, whose cell_ws holds the same
+ * table after a successful call and may be used in its place.  The table is what amds_heatmap_raster / amds_heatmap_classmap take as `cell`. */
+int amds_scatter_cells(const int64_t* xy, int* cell_ws, long n, int h, int w, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Heat-map rasters: the pixel arithmetic of the reference's `raw/` images (src/stamp/heatmaps/__init__.py), matplotlib and Pillow restated.  All
+ * results are fixed functions of the inputs (integer look-ups, one fp32 multiply, binary64 blends compiled without contraction): bit-reproducible, no
+ * atomics.  Launches only, on `stream`.  Images are row-major, RGBA / RGB interleaved bytes.
+ *
+ * amds_heatmap_raster: `np.uint8(cmap(x) * 255)` with the alpha channel replaced, then `resize((w * scale, h * scale), NEAREST)` = pixel replication
+ * (:500-529 classification, :600-609 regression, :683-717 survival) for all n_cat categories in one launch.
+ *   lut: u8 [n_lut][4] = uint8(cmap(arange(n_lut)) * 255), 1 <= n_lut <= 256.  Colour of an fp32 argument x: NaN -> (0, 0, 0); x < 0 -> lut[0];
+ *   x * n_lut >= n_lut -> lut[n_lut - 1]; else lut[(int)(x * n_lut)], the product rounded to fp32 (exact for n_lut = 256).  The alpha byte is 255 where
+ *   the alpha source > 0, else 0 (a NaN source: 0); the table's own alpha column is not used.
+ *   cell != NULL: arg, alpha_src fp32 [n_cat][n] per tile and cell the table of amds_scatter_cells for the h x w grid; a cell without a tile (an entry
+ *   outside [0, n), never dereferenced) has argument 0.0f and alpha 0: the zero fill of `_vals_to_im` (:142-156), colour lut[0].
+ *   cell == NULL: arg, alpha_src fp32 images [n_cat][h][w] (n is ignored).
+ *   out: u8 [n_cat][h * scale][w * scale][4], 4-byte aligned.  scale >= 1.
+ *
+ * amds_heatmap_classmap: `_show_class_map` (:241-258) and its x`scale` resize (:445-448), one image.  top: int32 class index per tile [n] (cell != NULL)
+ * or image [h][w] (cell == NULL), looked up directly: lut[min(max(top, 0), n_lut - 1)] (matplotlib's integer rule; Pastel1 has 9 entries).  alpha_src
+ * fp32 in the same arrangement: alpha byte 255 where > 0.  A cell without a tile is lut[0] with alpha 0 (the reference's colour there is whatever
+ * torch.topk returns on an all-zero row; nothing reads it under alpha 0).  out: u8 [h * scale][w * scale][4].
+ *
+ * amds_heatmap_overlay: `_create_overlay` (:261-284) for all categories in one launch.  score: u8 [n_cat][h * scale][w * scale][4], 4-byte aligned, as
+ * amds_heatmap_raster wrote it (scale = 1: the unscaled image the reference resizes); it is read at [ytab[y] * scale][xtab[x] * scale].  thumb: u8
+ * [th][tw][3].  ytab int32 [th], xtab int32 [tw]: the source row / column of Pillow's NEAREST resize from (h, w) to (th, tw), built by the caller as
+ * Pillow does: a = n_in / n_out in double, xo = 0.5 * a, then for each output index in order src = (int)xo, xo += a (the closed form
+ * floor((i + 0.5) * a) differs).  Entries are clamped into [0, h) / [0, w) before use.  Per channel in binary64: s = byte / 255.0, t = thumb / 255.0,
+ * o = alpha * s + (1 - alpha) * t where the sampled alpha byte > 0, else t; out = (uint8)(o * 255.0), truncating -- an unblended pixel returns the
+ * thumbnail's byte.  0 <= alpha <= 1 (AMDS_ERR_INVALID otherwise).  out: u8 [n_cat][th][tw][3].
+ *
+ * Limits: n_cat, h, w, scale, th, tw >= 1; h * scale, w * scale < 2^31; h * w < 2^31 - 1; 1 <= n < 2^31 with `cell`; at most 2^44 output pixels.
+ * Offsets are 64-bit.  AMDS_ERR_INVALID otherwise, also for a NULL pointer or a misaligned image. */
+int amds_heatmap_raster(const float* arg, const float* alpha_src, const int* cell, const uint8_t* lut, int n_lut, uint8_t* out, int n_cat, long n, int h,
+                        int w, int scale, void* stream);
+int amds_heatmap_classmap(const int32_t* top, const float* alpha_src, const int* cell, const uint8_t* lut, int n_lut, uint8_t* out, long n, int h, int w,
+                          int scale, void* stream);
+int amds_heatmap_overlay(const uint8_t* score, const uint8_t* thumb, const int32_t* ytab, const int32_t* xtab, double alpha, uint8_t* out, int n_cat, int h,
+                         int w, int scale, int th, int tw, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Rank metrics: exact pair counts of the concordance statistic.  Items i have a risk score_i (higher = worse), a time_i and an event_i in {0, 1}.  The
  * ordered pair (i, j) is PERMISSIBLE when event_i == 1 and (time_i < time_j or (time_i == time_j and event_j == 0)); a permissible pair is CONCORDANT when

@@ -348,6 +348,10 @@ PROTOTYPES = {
     "amds_mil_vit_gradcam": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _f, _vp, _vp, _sz, _vp]),
     "amds_softmax_over_tiles": (_i, [_vp, _vp, _i, _l, _vp]),
     "amds_scatter_grid": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _vp]),
+    "amds_scatter_cells": (_i, [_vp, _vp, _l, _i, _i, _vp]),
+    "amds_heatmap_raster": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _l, _i, _i, _i, _vp]),
+    "amds_heatmap_classmap": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _l, _i, _i, _i, _vp]),
+    "amds_heatmap_overlay": (_i, [_vp, _vp, _vp, _vp, C.c_double, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "amds_concordance_workspace_bytes": (_sz, [_l, _i]),
     "amds_concordance_counts": (_i, [_vp, _l, _l, _vp, _l, _vp, _l, _vp, _l, _l, _i, _vp, _vp, _sz, _vp]),
     "amds_binary_curves_workspace_bytes": (_sz, [_l, _l, _i, _i]),

@@ -72,22 +72,42 @@ extern "C" int amds_softmax_over_tiles(const float* in, float* out, int classes,
     return AMDS_OK;
 }
 
+// pass 1 of both entries: every cell -1, the out-of-grid count 0, then the winners
+static int scatter_cells_launch(const int64_t* xy, int* cell_ws, long n, int h, int w, hipStream_t st) {
+    const long cells = (long)h * w;
+    AMDS_HIP(hipMemsetAsync(cell_ws, 0xff, (size_t)cells * 4, st));              // every cell -1
+    AMDS_HIP(hipMemsetAsync(cell_ws + cells, 0, 4, st));                         // the out-of-grid count
+    hipLaunchKernelGGL(scatter_cells_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, xy, cell_ws, n, h, w);
+    AMDS_LAUNCH_CHECK("scatter_cells_kernel");
+    return AMDS_OK;
+}
+
+// the one host read of both entries: the out-of-grid count
+static int scatter_cells_check(const char* who, const int* cell_ws, long n, int h, int w, hipStream_t st) {
+    int bad = 0;
+    AMDS_HIP(hipMemcpyAsync(&bad, cell_ws + (long)h * w, 4, hipMemcpyDeviceToHost, st));
+    AMDS_HIP(hipStreamSynchronize(st));
+    AMDS_REQUIRE(bad == 0, "%s: %d of %ld coordinates lie outside the %d x %d grid", who, bad, n, w, h);
+    return AMDS_OK;
+}
+
 extern "C" int amds_scatter_grid(const float* vals, const int64_t* xy, float* out, int* cell_ws, long n, int k, int h, int w, void* stream) {
     AMDS_REQUIRE(vals && xy && out && cell_ws, "amds_scatter_grid: null pointer");
     AMDS_REQUIRE(n >= 1 && n < (1L << 31) && k >= 1 && h >= 1 && w >= 1 && (long)h * w < (1L << 31) - 1 && (long)h * w * k < (1L << 40),
                  "amds_scatter_grid: bad shape n=%ld k=%d h=%d w=%d", n, k, h, w);
     hipStream_t st = (hipStream_t)stream;
     const long cells = (long)h * w;
-    AMDS_HIP(hipMemsetAsync(cell_ws, 0xff, (size_t)cells * 4, st));              // every cell -1
-    AMDS_HIP(hipMemsetAsync(cell_ws + cells, 0, 4, st));                         // the out-of-grid count
-    hipLaunchKernelGGL(scatter_cells_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, xy, cell_ws, n, h, w);
-    AMDS_LAUNCH_CHECK("scatter_cells_kernel");
+    if (const int rc = scatter_cells_launch(xy, cell_ws, n, h, w, st)) return rc;
     const long blocks = (cells * k + 255) / 256;
     hipLaunchKernelGGL(scatter_copy_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st, vals, cell_ws, out, cells, k);
     AMDS_LAUNCH_CHECK("scatter_copy_kernel");
-    int bad = 0;
-    AMDS_HIP(hipMemcpyAsync(&bad, cell_ws + cells, 4, hipMemcpyDeviceToHost, st));
-    AMDS_HIP(hipStreamSynchronize(st));
-    AMDS_REQUIRE(bad == 0, "amds_scatter_grid: %d of %ld coordinates lie outside the %d x %d grid", bad, n, w, h);
-    return AMDS_OK;
+    return scatter_cells_check("amds_scatter_grid", cell_ws, n, h, w, st);
+}
+
+extern "C" int amds_scatter_cells(const int64_t* xy, int* cell_ws, long n, int h, int w, void* stream) {
+    AMDS_REQUIRE(xy && cell_ws, "amds_scatter_cells: null pointer");
+    AMDS_REQUIRE(n >= 1 && n < (1L << 31) && h >= 1 && w >= 1 && (long)h * w < (1L << 31) - 1, "amds_scatter_cells: bad shape n=%ld h=%d w=%d", n, h, w);
+    hipStream_t st = (hipStream_t)stream;
+    if (const int rc = scatter_cells_launch(xy, cell_ws, n, h, w, st)) return rc;
+    return scatter_cells_check("amds_scatter_cells", cell_ws, n, h, w, st);
 }

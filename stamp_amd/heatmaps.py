@@ -2,8 +2,13 @@
 
 Reference: src/stamp/heatmaps/__init__.py -- `_gradcam_per_category` :36-56, `_gradcam_single` :115-139, `_vals_to_im` :142-156, the grid coordinates
 :376 with `get_stride` (src/stamp/modeling/data.py:1150-1161), the slide score :392-403, the one-tile-bag scores :417-427, the per-category support /
-attention / score maps :464-498 and the regression branch's normalisations :593-597.  Rendering (matplotlib, colour maps, overlays, PNG files, openslide
-thumbnails, ranked-tile export) is not here: every function returns tensors the reference's plotting code takes as they are.
+attention / score maps :464-498 and the regression branch's normalisations :593-597.
+
+Rendering: the bytes of the reference's `raw/` images -- the per-category RGBA score image (:500-529, 600-609, 683-717), the class map (:241-258, 437-448)
+and the blend over the slide thumbnail (`_create_overlay` :261-284) -- are `colorize`, `class_map`, `overlay` and `SlideHeatmap.render`: matplotlib's
+colour-map look-up and Pillow's NEAREST resize restated as three kernels (csrc/heatmap_render.hip), byte for byte; the four colour tables are data
+(stamp_amd/colormaps.json).  `ranked_tiles` is the selection of `_export_ranked_tiles` (:190-238).  Not here: matplotlib figures (the `plots/` folder, titles,
+legends), PNG / JPEG encoding and file names, reading the slide or its thumbnail (the caller passes the thumbnail crop).
 
 Two routes to the Grad-CAM scores:
   * fused (`stamp_amd.mil.VisionTransformer`, with or without ALiBi): one eval-mode training forward that keeps its activations
@@ -306,18 +311,206 @@ class SlideHeatmap:
     tile_relevance: torch.Tensor | None = None  # regression: gradcam / max [N] (:593)
 
 
+    def render(self, thumb: torch.Tensor | None = None, *, opacity: float = 0.6, scale: int = 8, train_pred_median: float | None = None) -> "HeatmapImages":
+        """The images of the reference's `raw/` folder for this slide, on the device (module docstring, "Rendering"): the per-category RGBA score image at
+        `scale` pixels per tile, the class map (classification) and, with `thumb` u8 [th, tw, 3] (the caller's thumbnail crop, :159-187), the score image
+        blended over it at `opacity`.  classification: RdBu_r of category_score / 2 + 0.5, alpha where attention > 0 (:500-522).  regression: magma of
+        gradcam_2d, alpha where the scattered gradcam > 0 (:600-604).  survival: Reds likewise (:705-711), or with `train_pred_median` RdBu_r of
+        (g - med) / (2 * max|g - med| + 1e-8) + 0.5 over g = gradcam_2d, empty cells included (:683-697).  One launch per kind of output."""
+        if train_pred_median is not None and self.task != "survival":
+            raise ValueError("train_pred_median belongs to task 'survival'")
+        classes = None
+        if self.task == "classification":
+            score = colorize(self.category_score / 2 + 0.5, self.attention, "RdBu_r", coords_norm=self.coords_norm, scale=scale)
+            classes = class_map(self.scores_2d.argmax(-1), self.gradcam_2d.sum(-1), scale=scale)          # :437-442; alpha :250
+        else:
+            g, cmap = self.gradcam_2d, ("magma" if self.task == "regression" else "Reds")
+            if train_pred_median is not None:
+                d = g - float(train_pred_median)
+                g, cmap = d / (2 * d.abs().amax() + 1e-8) + 0.5, "RdBu_r"
+            score = colorize(g[None], vals_to_im(self.gradcam, self.coords_norm)[None], cmap, scale=scale)
+        over = None if thumb is None else overlay(score, thumb, opacity, scale=scale)
+        return HeatmapImages(score, classes, over)
+
+
+@dataclass
+class HeatmapImages:
+    """`SlideHeatmap.render`: u8 device tensors, the bytes the reference writes into `raw/` before PNG encoding."""
+    score_rgba: torch.Tensor                    # [C, scale * H, scale * W, 4] (:526-533, 606-610, 713-717); regression / survival: C = 1
+    class_map: torch.Tensor | None = None       # [scale * H, scale * W, 4], classification only (:444-448)
+    overlay: torch.Tensor | None = None         # [C, th, tw, 3] when a thumbnail was given (:535-541, 620-624, 727-731)
+
+
+# ---- Rendering: look-up tables, rasters, overlays -------------------------------------------------------------------------------------------------
+COLORMAPS = ("RdBu_r", "magma", "Reds", "Pastel1")
+_TABLES: dict = {}
+
+
+def colormap_table(name: str):
+    """The u8 [N, 4] table uint8(cmap(arange(N)) * 255) of one of COLORMAPS, from stamp_amd/colormaps.json (text: per map the N RGBA entries as one
+    hexadecimal string, 8 digits per entry; recorded from matplotlib, whose version the file's `matplotlib_version` names;
+    tools/make_heatmap_render_golden.py writes it): matplotlib itself is not needed at run time."""
+    if name not in COLORMAPS:
+        raise ValueError(f"colour map must be one of {COLORMAPS}, got {name!r}")
+    if "host" not in _TABLES:
+        import json
+        import numpy as np
+        from pathlib import Path
+        rec = json.loads(Path(__file__).with_name("colormaps.json").read_text())
+        _TABLES["host"] = {k: np.frombuffer(bytes.fromhex(rec[k]), np.uint8).reshape(-1, 4) for k in COLORMAPS}
+    return _TABLES["host"][name]
+
+
+def _lut(name: str, device: torch.device) -> torch.Tensor:
+    key = (name, str(device))
+    if key not in _TABLES:
+        _TABLES[key] = torch.from_numpy(colormap_table(name).copy()).to(device).contiguous()
+    return _TABLES[key]
+
+
+def _cells(coords_norm: torch.Tensor, n: int):
+    """int64 grid coordinates [n, 2] -> (cell table int32 [h * w + 1] (amds_scatter_cells), h, w)."""
+    if coords_norm.dim() != 2 or coords_norm.shape[1] != 2 or coords_norm.shape[0] != n or n < 1:
+        raise ValueError(f"coords_norm must be [{n}, 2] with at least one tile, got {tuple(coords_norm.shape)}")
+    xy = coords_norm.to(torch.int64).contiguous()
+    w, h = (int(v) + 1 for v in xy.max(0).values.tolist())
+    if h < 1 or w < 1:
+        raise ValueError("negative grid coordinates")
+    cells = torch.empty(h * w + 1, dtype=torch.int32, device=xy.device)
+    _lib.check(_lib.lib().amds_scatter_cells(xy.data_ptr(), cells.data_ptr(), n, h, w, ops._stream()), "scatter_cells")
+    return cells, h, w
+
+
+def _out(out: torch.Tensor | None, shape, device) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(shape)} on {device}")
+    return out
+
+
+def _sources(vals: torch.Tensor, alpha_src: torch.Tensor, coords_norm: torch.Tensor | None, dtype: torch.dtype):
+    """-> (vals [C, ...] contiguous `dtype`, alpha_src fp32 alike, cell table or None, n, h, w, whether a leading category axis was added)."""
+    ops._dev(vals, alpha_src, coords_norm)
+    if vals.shape != alpha_src.shape:
+        raise ValueError(f"values and alpha source must have one shape, got {tuple(vals.shape)} and {tuple(alpha_src.shape)}")
+    base = 1 if coords_norm is not None else 2
+    if vals.dim() not in (base, base + 1):
+        raise ValueError(f"expected {'[C, tiles] or [tiles]' if base == 1 else '[C, H, W] or [H, W]'}, got {tuple(vals.shape)}")
+    single = vals.dim() == base
+    if single:
+        vals, alpha_src = vals[None], alpha_src[None]
+    if vals.shape[0] < 1:
+        raise ValueError("no category")
+    vals, alpha_src = vals.detach().to(dtype).contiguous(), alpha_src.detach().float().contiguous()
+    if coords_norm is None:
+        return vals, alpha_src, None, 0, int(vals.shape[1]), int(vals.shape[2]), single
+    cells, h, w = _cells(coords_norm, int(vals.shape[1]))
+    return vals, alpha_src, cells, int(vals.shape[1]), h, w, single
+
+
+def colorize(arg: torch.Tensor, alpha_src: torch.Tensor, cmap: str, *, coords_norm: torch.Tensor | None = None, scale: int = 8,
+             out: torch.Tensor | None = None) -> torch.Tensor:
+    """`np.uint8(plt.get_cmap(cmap)(x) * 255)` with alpha = 255 where `alpha_src` > 0, enlarged `scale` times by pixel replication (:500-529, 600-609,
+    683-717; amds_heatmap_raster, all categories in one launch).  With `coords_norm` int64 [N, 2]: arg, alpha_src per tile, [C, N] or [N], scattered like
+    `vals_to_im` (a cell without a tile: argument 0 -> lut[0], alpha 0).  Without: images [C, H, W] or [H, W].  -> u8 [C, scale * H, scale * W, 4]
+    (without the leading C for an input without it).  NaN -> RGB (0, 0, 0); x < 0 -> the first, x >= 1 -> the last table entry."""
+    arg, alpha_src, cells, n, h, w, single = _sources(arg, alpha_src, coords_norm, torch.float32)
+    scale = int(scale)
+    if scale < 1:
+        raise ValueError("scale must be >= 1")
+    lut = _lut(cmap, arg.device)
+    res = _out(out, ((h * scale, w * scale, 4) if single else (arg.shape[0], h * scale, w * scale, 4)), arg.device)
+    _lib.check(_lib.lib().amds_heatmap_raster(arg.data_ptr(), alpha_src.data_ptr(), ops._p(cells), lut.data_ptr(), lut.shape[0], res.data_ptr(),
+                                              arg.shape[0], n, h, w, scale, ops._stream()), "heatmap_raster")
+    return res
+
+
+def class_map(top: torch.Tensor, alpha_src: torch.Tensor, *, coords_norm: torch.Tensor | None = None, scale: int = 8,
+              out: torch.Tensor | None = None) -> torch.Tensor:
+    """`_show_class_map` (:241-258) and its resize (:445-448): Pastel1 of each tile's top class (an integer tensor; an index >= 9 takes the last entry),
+    alpha = 255 where `alpha_src` > 0 (the reference: `gradcam_2d.sum(-1)`).  With `coords_norm`: per tile [N]; without: images [H, W].  A cell without a
+    tile is the first table entry with alpha 0.  -> u8 [scale * H, scale * W, 4] (amds_heatmap_classmap)."""
+    if top.is_floating_point() or top.dtype == torch.bool:
+        raise ValueError(f"top must hold integer class indices, got {top.dtype}")
+    if top.dim() != (1 if coords_norm is not None else 2):
+        raise ValueError(f"top must be {'[tiles]' if coords_norm is not None else '[H, W]'}, got {tuple(top.shape)}")
+    top, alpha_src, cells, n, h, w, _ = _sources(top, alpha_src, coords_norm, torch.int32)
+    scale = int(scale)
+    if scale < 1:
+        raise ValueError("scale must be >= 1")
+    lut = _lut("Pastel1", top.device)
+    res = _out(out, (h * scale, w * scale, 4), top.device)
+    _lib.check(_lib.lib().amds_heatmap_classmap(top.data_ptr(), alpha_src.data_ptr(), ops._p(cells), lut.data_ptr(), lut.shape[0], res.data_ptr(), n, h, w,
+                                                scale, ops._stream()), "heatmap_classmap")
+    return res
+
+
+def resize_index_table(n_in: int, n_out: int) -> list[int]:
+    """The source index of every output index of Pillow's NEAREST resize from n_in to n_out samples: its running sum in double (`a = n_in / n_out`,
+    `xo = 0.5 * a`, then `src = int(xo); xo += a` in order).  The closed form floor((i + 0.5) * a) rounds differently."""
+    if n_in < 1 or n_out < 1:
+        raise ValueError("sizes must be >= 1")
+    a = n_in / n_out
+    xo, tab = 0.5 * a, []
+    for _ in range(n_out):
+        tab.append(min(int(xo), n_in - 1))
+        xo += a
+    return tab
+
+
+def overlay(score_rgba: torch.Tensor, thumb: torch.Tensor, opacity: float = 0.6, *, scale: int = 1, out: torch.Tensor | None = None) -> torch.Tensor:
+    """`_create_overlay` (:261-284) for all categories in one launch (amds_heatmap_overlay): score_rgba u8 [C, scale * H, scale * W, 4] or without the C,
+    as `colorize` returns it at `scale` (1: the unscaled image the reference resizes; any scale gives the same bytes), thumb u8 [th, tw, 3] ->
+    u8 [C, th, tw, 3].  The score image is resized to the thumbnail by Pillow's NEAREST rule (`resize_index_table`, built on the host) and blended in
+    binary64 where its alpha byte is > 0; elsewhere the thumbnail's byte is returned.  0 <= opacity <= 1."""
+    ops._dev(score_rgba, thumb)
+    if score_rgba.dtype != torch.uint8 or thumb.dtype != torch.uint8:
+        raise ValueError("score_rgba and thumb must be uint8")
+    single = score_rgba.dim() == 3
+    if single:
+        score_rgba = score_rgba[None]
+    scale = int(scale)
+    if score_rgba.dim() != 4 or score_rgba.shape[3] != 4 or scale < 1 or score_rgba.shape[0] < 1 or score_rgba.shape[1] % scale or score_rgba.shape[2] % scale \
+            or min(score_rgba.shape[1:3]) < scale:
+        raise ValueError(f"score_rgba must be [C, scale * H, scale * W, 4] or [scale * H, scale * W, 4], got {tuple(score_rgba.shape)} at scale {scale}")
+    if thumb.dim() != 3 or thumb.shape[2] != 3 or thumb.shape[0] < 1 or thumb.shape[1] < 1:
+        raise ValueError(f"thumb must be [th, tw, 3], got {tuple(thumb.shape)}")
+    if not 0.0 <= float(opacity) <= 1.0:
+        raise ValueError(f"opacity must lie in [0, 1], got {opacity}")
+    score_rgba, thumb = score_rgba.contiguous(), thumb.contiguous()
+    Cn, h, w = score_rgba.shape[0], score_rgba.shape[1] // scale, score_rgba.shape[2] // scale
+    th, tw = int(thumb.shape[0]), int(thumb.shape[1])
+    tabs = torch.tensor(resize_index_table(h, th) + resize_index_table(w, tw), dtype=torch.int32).to(thumb.device)
+    res = _out(out, ((th, tw, 3) if single else (Cn, th, tw, 3)), thumb.device)
+    _lib.check(_lib.lib().amds_heatmap_overlay(score_rgba.data_ptr(), thumb.data_ptr(), tabs.data_ptr(), tabs[th:].data_ptr(), float(opacity), res.data_ptr(),
+                                               Cn, h, w, scale, th, tw, ops._stream()), "heatmap_overlay")
+    return res
+
+
+def ranked_tiles(scores: torch.Tensor, topk: int, bottomk: int):
+    """The tiles `_export_ranked_tiles` saves (:216-238): -> (top_idx, top_val, bottom_idx, bottom_val), the `min(topk, N)` highest scores in descending
+    and the `min(bottomk, N)` lowest in ascending order; among equal scores the lower tile index comes first (a stable sort).  Plumbing: no kernel, any
+    device."""
+    s = scores.detach().flatten()
+    kt, kb = max(min(int(topk), s.numel()), 0), max(min(int(bottomk), s.numel()), 0)
+    tv, ti = torch.sort(s, descending=True, stable=True)
+    bv, bi = torch.sort(s, descending=False, stable=True)
+    return ti[:kt], tv[:kt], bi[:kb], bv[:kb]
+
+
 def slide_heatmap(model: torch.nn.Module, feats: torch.Tensor, coords_um: torch.Tensor, *, task: str, method: str = "auto",
                   tiles_per_call: int | None = None) -> SlideHeatmap:
-    """One slide, `task` "classification" (:401-498) or "regression" (:586-597): slide score, Grad-CAM scores, per-tile scores, their 2-D arrangements and
-    the per-category maps -- the tensors the reference's plotting takes from here.  `method` goes to `gradcam` / `gradcam_single`, `tiles_per_call` to
-    `tile_scores`."""
-    if task not in ("classification", "regression"):
-        raise ValueError(f"task must be 'classification' or 'regression', got {task!r}")
+    """One slide, `task` "classification" (:401-498), "regression" (:586-597) or "survival" (:668-679, the regression computation; its colouring is
+    `SlideHeatmap.render`'s): slide score, Grad-CAM scores, per-tile scores, their 2-D arrangements and the per-category maps -- the tensors the
+    reference's plotting takes from here.  `method` goes to `gradcam` / `gradcam_single`, `tiles_per_call` to `tile_scores`."""
+    if task not in ("classification", "regression", "survival"):
+        raise ValueError(f"task must be 'classification', 'regression' or 'survival', got {task!r}")
     _check_inputs(feats, coords_um)
     with _eval_mode(model), torch.no_grad():
         logits = model(feats.unsqueeze(0), coords=coords_um.unsqueeze(0), mask=None).squeeze(0)          # :392-399
     cn = grid_coords(coords_um)
-    if task == "regression":
+    if task != "classification":
         cam = gradcam_single(model, feats, coords_um, method=method)
         g2 = vals_to_im(cam, cn)
         g2 = (g2 - g2.min()) / (g2.max() - g2.min() + 1e-8)
