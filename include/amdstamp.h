@@ -1168,6 +1168,83 @@ int amds_binary_curves(const float* score, long score_item_stride, long score_pr
  *     nothing outside [ws, ws + amds_binary_curves_workspace_bytes) and the outputs is written. */
 
 /* ------------------------------------------------------------------------------------------------
+ * Survival report: two risk groups split at a cut-off -- the log-rank test between them, the Kaplan-Meier curve of each, the at-risk table under the
+ * plot, the median survival times and the comparable pairs (reference src/stamp/statistics/survival.py:16-87, 116-157: `logrank_test`,
+ * `KaplanMeierFitter`, `add_at_risk_counts`, `_comparable_pairs_count`).  Batched over problems: bands of the curves and intervals of the numbers are
+ * quantiles over bootstrap resamples of the same statistic.
+ *
+ * PROBLEMS AND ITEMS.  An item has an fp32 score (risk, higher = worse), an fp32 time and an event byte: 1 = death, 0 = censored, anything else =
+ * invalid; a NaN score or time makes the item invalid; an invalid item takes part in nothing -- the rule of amds_concordance_counts, and times compare
+ * through its fp32 order keys (-0 == +0, denormals kept).  With idx (int32 [n_problems][n_items]) problem r is the MULTISET idx[r] of ONE base problem of
+ * n_base items (problem 0 of the three arrays; their problem strides are not used), and a duplicated item counts twice.  An out-of-range index is never
+ * dereferenced; the call counts them, and ONLY with idx it SYNCHRONISES `stream` (one 8-byte read) and returns AMDS_ERR_INVALID if there was one (the
+ * outputs are then unspecified).
+ *
+ * GROUPS.  cutoff: fp64, problem p's at cutoff[p * cutoff_problem_stride], stride 0 (one cut-off for all problems) or 1.  An item is in group HIGH when
+ * (double)score > cutoff, else LOW -- the reference's `risk > median` / `risk <= median` (survival.py:64-65); the fp64 compare is exact for fp32 scores
+ * and a cut-off that is the midpoint of two of them.  A NaN cut-off sends every item to LOW.  Group 0 = LOW, group 1 = HIGH in every output.
+ *
+ * RISK SETS.  Over the distinct times t_k of the problem's valid items, ascending, with integer multiplicities: n_k and n_k^g = the items at risk
+ * (time >= t_k), in total and in group g; d_k and d_k^g = the deaths at t_k.
+ *   counts   int64 [n_problems][2][3]: per group {items, deaths, censored}.
+ *   logrank  fp64 [n_problems][3] = {O, E, V} for the HIGH group: O = sum_k d_k^H;  E = sum_k d_k * n_k^H / n_k;
+ *            V = sum over k with n_k > 1 of  d_k * (n_k - d_k) / (n_k - 1) * (n_k^H / n_k) * (n_k^L / n_k)  -- the two-sample log-rank test
+ *            (`lifelines.statistics.logrank_test`): chi2 = (O - E)^2 / V on one degree of freedom.  A problem with an empty group has NaN in all three
+ *            (the reference returns NaN there, survival.py:66-75).
+ *   pairs    int64 [n_problems] (may be NULL): the reference's `comparable_pairs` (survival.py:16-21) = #{(i, j): time_i < time_j, event_i == 1}
+ *            = sum_k d_k * (n_k - the items that leave at t_k).  This is NOT the PERMISSIBLE count of amds_concordance_counts, which also holds the pairs
+ *            (death, censored) at one time.
+ *   km       fp64 [n_problems][2][grid] (may be NULL): Kaplan-Meier on the caller's grid of times x,  S_g(x) = prod over t_k <= x of (1 - d_k^g / n_k^g),
+ *            each factor formed as (n_k^g - d_k^g) / n_k^g: 1.0 before the first time, exactly 0.0 once a whole risk set has died, NaN for an empty
+ *            group and for a NaN grid time.
+ *   at_risk  int64 [n_problems][2][grid][3] (may be NULL): per grid time x {items with time >= x, deaths with time <= x, censored with time <= x} of
+ *            the group; {-1, -1, -1} for a NaN grid time.  This is THIS LIBRARY'S definition of the table under the plot: lifelines'
+ *            `add_at_risk_counts` is not reproduced (lifelines is no dependency and its table was not available to compare against).
+ *   median   fp64 [n_problems][2]: MEDIAN survival time per group, the smallest t_k with S_g(t_k) <= 1/2, +inf if there is none
+ *            (`KaplanMeierFitter.median_survival_time_`), NaN for an empty group.  S is a rounded product; a product that equals 1/2 as a rational may
+ *            round to either side, so the test is  S_g(t_k) <= 0.5 * (1 + 2^-30): an exact 1/2 always counts as reached, and only a curve whose exact
+ *            value lies within 4.7e-10 above 1/2 is judged differently from exact arithmetic.
+ * grid_times: fp32, problem p's grid at grid_times[p * grid_problem_stride + k]; stride 0 = one grid for all problems.  grid: 0 (grid_times, km and
+ * at_risk all NULL) or 2..4096.  score / time / event are addressed as in amds_concordance_counts.
+ *
+ * How: one launch ranks the items of each base problem by time, by counting (pos_i = the number of valid items with a smaller time, O(n^2) compares
+ * through LDS tiles, no sort; tied items share a position); a second ranks every grid time against the same items the same way (the items with
+ * time <= x are then exactly the positions below its count: a grid point costs two array reads, no search); then one workgroup per problem adds its
+ * items' multiplicities at their positions (integer atomics) into four int32 arrays -- deaths and exits of LOW and of HIGH --, prefix-scans them (a risk
+ * set = the group's total minus the exits before the position), reduces E, V and the pairs, scans the two survival products, finds the medians and answers
+ * the grid.  The six arrays (32 bytes per position) live in LDS up to 5000 positions (160128 of a CU's 163840 bytes of LDS) and in `ws` above.  Every term
+ * is formed in fp64 from integers; fp64 sums and products run in a fixed order: a call is bitwise reproducible.  No n x n tensor, no floating-point atomics.
+ * Limits: 1 <= n_items <= 2^20, 1 <= n_base <= 2^20 (with idx), n_problems >= 1, n_problems * n_items < 2^31, grid as above, score_item_stride >= 1,
+ * problem strides >= 0, cutoff_problem_stride 0 or 1 -- AMDS_ERR_INVALID otherwise (amds_last_error names the limit), also for a NULL pointer or a `ws`
+ * not 256-byte aligned; ws_bytes < amds_survival_groups_workspace_bytes -> AMDS_ERR_WORKSPACE.  amds_survival_groups_workspace_bytes: n_base = 0 for a
+ * call without idx, the base problem's size for a call with it; grid_shared != 0 when grid_problem_stride == 0; 0 for anything outside the limits.
+ * Without idx: launches only, on `stream`. */
+size_t amds_survival_groups_workspace_bytes(long n_base, long n_items, int n_problems, int grid, int grid_shared);
+int amds_survival_groups(const float* score, long score_item_stride, long score_problem_stride, const float* time, long time_problem_stride,
+                         const uint8_t* event, long event_problem_stride, const double* cutoff, long cutoff_problem_stride, const int32_t* idx, long n_base,
+                         long n_items, int n_problems, const float* grid_times, long grid_problem_stride, int grid, int64_t* counts, double* logrank,
+                         double* median, int64_t* pairs, double* km, int64_t* at_risk, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_survival_groups_workspace_bytes) and the outputs is written. */
+
+/* Regression report: the moments R^2, Pearson r, MAE, RMSE and the fitted line of the scatter plot are formed from (reference
+ * src/stamp/statistics/regression.py:14-39, 70).  Items are pairs of fp32 (truth, pred), item k of problem p at truth[p * truth_problem_stride + k *
+ * truth_item_stride] and likewise pred; a NaN in either makes the item invalid (the reference drops such rows, regression.py:58).  idx as above: problem r
+ * is the multiset idx[r] of ONE base problem of n_base items (the problem strides are not used); an out-of-range index is never dereferenced and fails
+ * the call after one 8-byte read-back.
+ *   moments fp64 [n_problems][8] = {n, mean_t, mean_p, Sxx, Syy, Sxy, sum |p - t|, sum (p - t)^2} over the valid items, with
+ *   Sxx = sum (t - mean_t)^2, Syy = sum (p - mean_p)^2, Sxy = sum (t - mean_t)(p - mean_p) centred on the problem's OWN means: two passes in fp64, each
+ *   thread-strided and folded over a fixed tree (bitwise reproducible, no atomics).  n = 0: the means are NaN and the sums 0.
+ * Limits: 1 <= n_items < 2^31, 1 <= n_base < 2^31 (with idx), n_problems >= 1, item strides >= 1, problem strides >= 0 -- AMDS_ERR_INVALID otherwise,
+ * also for a NULL pointer or a `ws` not 256-byte aligned; a short `ws` -> AMDS_ERR_WORKSPACE; the size is 0 for a bad shape (n_base = 0 without idx).
+ * Without idx: one launch on `stream`. */
+size_t amds_regression_moments_workspace_bytes(long n_base, long n_items, int n_problems);
+int amds_regression_moments(const float* truth, long truth_item_stride, long truth_problem_stride, const float* pred, long pred_item_stride,
+                            long pred_problem_stride, const int32_t* idx, long n_base, long n_items, int n_problems, double* moments, void* ws, size_t ws_bytes,
+                            void* stream);
+/* ws: contents on entry are ignored; nothing outside [ws, ws + amds_regression_moments_workspace_bytes) and `moments` is written. */
+
+/* ------------------------------------------------------------------------------------------------
  * barspoon head, deploy / validation forward as one call (reference src/stamp/modeling/models/barspoon.py:27-205
  * `EncDecTransformer` in eval mode: projector, sinusoidal position encoding, pre-norm transformer encoder over the tiles, one class
  * token per target decoded against the tiles by a pre-norm transformer decoder, one Linear head per target)

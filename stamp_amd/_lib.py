@@ -356,6 +356,10 @@ PROTOTYPES = {
     "amds_concordance_counts": (_i, [_vp, _l, _l, _vp, _l, _vp, _l, _vp, _l, _l, _i, _vp, _vp, _sz, _vp]),
     "amds_binary_curves_workspace_bytes": (_sz, [_l, _l, _i, _i]),
     "amds_binary_curves": (_i, [_vp, _l, _l, _vp, _l, _vp, _l, _l, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "amds_survival_groups_workspace_bytes": (_sz, [_l, _l, _i, _i, _i]),
+    "amds_survival_groups": (_i, [_vp, _l, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _l, _i, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "amds_regression_moments_workspace_bytes": (_sz, [_l, _l, _i]),
+    "amds_regression_moments": (_i, [_vp, _l, _l, _vp, _l, _l, _vp, _l, _l, _i, _vp, _vp, _sz, _vp]),
     "amds_bgemm_f32": (_i, [_vp, _i, _l, _l, _vp, _i, _l, _l, _i, _vp, _i, _l, _l, _i, _i, _i, _i, _i, _f, _f, _vp, _i, _vp]),
     "amds_bgemm_f32_dual": (_i, [_vp, _i, _l, _l, _vp, _i, _l, _l, _i, _vp, _vp, _i, _l, _l, _i, _i, _i, _i, _i, _f, _f, _f, _f, _vp]),
     "amds_softmax_rows": (_i, [_vp, _l, _i, _vp]),
