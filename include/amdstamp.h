@@ -1673,7 +1673,8 @@ int amds_colsum(const void* x, long ld, float* out, int M, int N, int in_dtype, 
 /* ws: contents on entry are ignored (the call initialises every byte it reads);
  *     nothing outside [ws, ws + amds_colsum_workspace_bytes) is written. */
 /* out_i[e] = sum over s < rows of part_i[s * count_i + e], e < count_i, for up to 32 (part, out, count) triples in ONE launch, with the association of
- * amds_colsum(part_i, count_i, out_i, rows, count_i, AMDS_F32, ...) (same bits): the split-K partials of every weight gradient of a backward pass
+ * amds_colsum(part_i, count_i, out_i, rows, count_i, AMDS_F32, ...) (same bits, for every row count 1 .. 2048 the call accepts: the four accumulators per
+ * row lane of that path included, which part ways with a plain in-order sum from 49 rows on): the split-K partials of every weight gradient of a backward pass
  * (amds_wgrad_tn) summed behind the last of them instead of one reduction launch per matrix.  counts: multiples of 4; pointers 16-byte aligned. */
 int amds_sum_partials_multi(const float* const* parts_host, float* const* outs_host, const long* counts_host, int n, int rows, void* stream);
 /* Column sums a backward pass can postpone, summed by ONE launch behind the last of them (the MIL `vit` step kept 21 small reduction launches for

@@ -530,7 +530,9 @@ struct SumTable {
     long vec0[33];           // first float4 of entry i in the launch's sequence
     int n, rows;
 };
-// the association of amds_colsum's one-chunk path (16 row lanes, each adding its rows r, r + 16, r + 32, ... in order; the lanes added in order): the same bits
+// the association of amds_colsum's one-chunk path (colsum_block's vector branch: 16 row lanes; lane k adds rows k, k + 16, k + 32, k + 48 of each 64-row step into
+// four accumulators while a whole step is left and the rest into the first, (a0 + a1) + (a2 + a3); the lanes added in order): the same bits for every row
+// count the entry accepts (a single sequential accumulator per lane agrees up to 48 rows only: tests/test_cpu_train_rows_oracle.py)
 __global__ void __launch_bounds__(256) sum_partials_multi_kernel(SumTable tb) {
     const long v = (long)blockIdx.x * 256 + threadIdx.x;
     if (v >= tb.vec0[tb.n]) return;
@@ -541,9 +543,16 @@ __global__ void __launch_bounds__(256) sum_partials_multi_kernel(SumTable tb) {
     const long ld = tb.count[ei];
     f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int k = 0; k < 16 && k < tb.rows; ++k) {
-        f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int r = k; r < tb.rows; r += 16) a += *reinterpret_cast<const f32x4*>(p + (long)r * ld);
-        s += a;
+        f32x4 a0 = f32x4{0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0;
+        int r = k;
+        for (; r + 48 < tb.rows; r += 64) {
+            a0 += *reinterpret_cast<const f32x4*>(p + (long)r * ld);
+            a1 += *reinterpret_cast<const f32x4*>(p + (long)(r + 16) * ld);
+            a2 += *reinterpret_cast<const f32x4*>(p + (long)(r + 32) * ld);
+            a3 += *reinterpret_cast<const f32x4*>(p + (long)(r + 48) * ld);
+        }
+        for (; r < tb.rows; r += 16) a0 += *reinterpret_cast<const f32x4*>(p + (long)r * ld);
+        s += (a0 + a1) + (a2 + a3);
     }
     *reinterpret_cast<f32x4*>(tb.out[ei] + e) = s;
 }

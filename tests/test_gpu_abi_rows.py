@@ -5,7 +5,10 @@ workspaces everywhere; every case runs under 0x00 and 0xFF (bit-identical, finit
 Bars: where a kernel has a parity test of its own its bar is restated (named in the docstring).  The fp32 kernels that are only reached through the
 whole-model chains have none; theirs is the rounding bound of the arithmetic the header states, computed from the REFERENCE's operands: a sum of n fp32 terms
 evaluated in any order is within n * 2^-23 * sum|terms| of the exact sum (`_sum_bar`), a single fp32 result within 2^-23 of its magnitude, a value rounded once
-to bf16 within 2^-8 of its magnitude."""
+to bf16 within 2^-8 of its magnitude.
+
+The kernels of train.hip and dropout.hip (LayerNorm training forms, column sums, transposes, the dropout sites) are held to per-element bars, on every launch and
+with masks from an independent restatement of the rule, by tests/test_gpu_train_rows.py; the tensor-wide bars restated below stay as this file's contract check."""
 import ctypes as C
 
 import pytest
@@ -61,7 +64,8 @@ def test_layernorm(gpu, odt, rows, cols, stride):
 @pytest.mark.parametrize("rows,cols,pad,p", [(70, 128, 8, 0.25), (1025, 512, 0, 0.0), (333, 256, 64, 0.5)])
 def test_layernorm_training_forms(gpu, rows, cols, pad, p):
     """amds_layernorm_train / _train_copy, amds_layernorm_bwd / _bwd_cast / _bwd_partials on pitched rows (test_layernorm_train_and_bwd: y 1e-5, dx 2e-5, parameter
-    gradients 1e-3 of their range; the 16-bit copy of dx: the dropout site's multiplier times dx, rounded once to bf16)."""
+    gradients 1e-3 of their range; the 16-bit copy of dx: the dropout site's multiplier times dx, rounded once to bf16).  Per-element bars for y, mean, rstd, dx, the
+    parameter gradients and the copy: tests/test_gpu_train_rows.py::test_layernorm_train / test_layernorm_bwd."""
     lib, ld, seed, sid = _lib.lib(), cols + pad, 77, 13
     g = torch.Generator().manual_seed(rows)
     x0 = torch.randn(rows, cols, generator=g) * 2 + 0.5
@@ -125,7 +129,8 @@ def test_layernorm_training_forms(gpu, rows, cols, pad, p):
 @pytest.mark.parametrize("M,N,pad", [(777, 300, 4), (4100, 130, 0), (64, 2, 2)])
 def test_colsum_family(gpu, dt, M, N, pad):
     """amds_colsum, amds_colsum_partials + a kind-1 entry of amds_colsum_multi, a kind-0 entry (fp32, M <= 2048), amds_sum_partials_multi (test_colsum_multi_is_colsum_bit_for_bit:
-    2e-2 max(1, sqrt(M / 1000)), the routes bit-identical)."""
+    2e-2 max(1, sqrt(M / 1000)), the routes bit-identical).  Per-column bars (M + 2) 2^-23 sum|x|, integer grids bit-equal to fp64, and amds_sum_partials_multi
+    bit for bit amds_colsum up to 2048 rows: tests/test_gpu_train_rows.py::test_colsum / test_sum_partials_multi_is_colsum_bit_for_bit."""
     lib, ld = _lib.lib(), N + pad
     g = torch.Generator().manual_seed(M + N)
     x0 = torch.randn(M, N, generator=g).to(dt)
@@ -218,7 +223,8 @@ def test_cast_pad(gpu):
 def test_dropout_sites(gpu, p):
     """amds_dropout_add / _cast_bwd, amds_gelu_dropout_fwd / _bwd and the four *_rows forms (rows r * row_mul of the full tensor), pitched; the multipliers are
     the ones amds_dropout_mask writes for (seed, stream_id).  fp32 results: one fp32 rounding of the exact value (GELU: test_gelu_fwd_bwd's 1e-6 / 1e-5 times the
-    keep scale); 16-bit results: rounded once more."""
+    keep scale); 16-bit results: rounded once more.  The masks against a restatement of the rule, every dtype route and per-element bars:
+    tests/test_gpu_train_rows.py::test_act_dropout / test_dropout_sites / test_rows_forms."""
     lib, (rows, cols, pad, seed, sid, mul) = _lib.lib(), (37, 264, 8, 5, 3, 9)
     ld = cols + pad
     g = torch.Generator().manual_seed(11)
