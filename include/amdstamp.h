@@ -1598,6 +1598,61 @@ int amds_transmil_gradcam(const amds_transmil_cfg* cfg_host, const amds_transmil
 /* ws: contents on entry are ignored (the call initialises every byte it reads);
  *     nothing outside [ws, ws + amds_transmil_gradcam_workspace_bytes) is written. */
 
+/* ------------------------------------------------------------------------------------------------
+ * Gated-attention MIL head (CHIEF's CHIEFModel as a classifier; reference src/stamp/encoding/encoder/chief.py:27-89 CHIEFModel, :255-275 Attn_Net_Gated),
+ * eval forward, training forward and backward, one call each (csrc/abmil.hip).  Per bag of N rows x_n [n_feats], keep-masks m scaled by 1 / (1 - p):
+ *   h_n = m_h o relu(fc_w x_n + fc_b)  [L]      a_n = m_a o tanh(a_w h_n + a_b)  [D]      g_n = m_g o sigmoid(b_w h_n + b_b)  [D]
+ *   s_n = c_w . (a_n o g_n) + c_b               P = softmax_n(s) (chief.py:77-79)         M = sum_n P_n h_n  [L] ("WSI_feature_transformed", :80)
+ *   logits = cls_w M + cls_b  [classes] (`classifiers`, :56).     Eval: every mask is 1.  The gated form only.
+ * Every entry is ragged by construction, with the convention of amds_gated_attn_pool_batched: x [total_rows][n_feats] (AMDS_F32 / AMDS_F16 / AMDS_BF16),
+ * row_offsets DEVICE int64 [bags + 1] (row_offsets[0] = 0, row_offsets[bags] = total_rows; NULL allowed when bags == 1); a dense batch is equal offsets.  Every
+ * bag holds at least one row (offsets outside [0, total_rows] are clamped on the device; the rows of an empty bag pool to 0).
+ * Precision: fc, a | b (ONE stacked [2D][L] product) and their dx / dW forms are amds_bgemm_f32 calls, so the head follows amds_set_matmul_precision exactly as
+ * TransMIL does; everything else is exact fp32.  No floating-point atomics: partial sums merge in a fixed order, a call is reproducible bit for bit.
+ * Batch independence: the forwards run their products on the call's rows padded with zero rows to a multiple of amds_abmil_row_pad() = 256, so the row count
+ * amds_bgemm_f32 picks its kernel by always falls in ONE class: a bag's eval outputs do not depend on what else is in the call, at every length (there is no
+ * shared-length limit to respect), and a training forward with p_fc = p_gate = 0 gives the eval forward's bits.
+ * Dropout (amds_abmil_dropout): three element-wise sites with the counter-based masks of amds_dropout_mask -- stream id 1 for h (cols = L, probability p_fc),
+ * 2 for a and 3 for g (cols = D, probability p_gate); the flat element index is row * cols + col over the call's PACKED rows, so the keep masks are
+ * amds_dropout_mask(total_rows * cols, p, seed, id) reshaped [total_rows][cols].  NULL or p = 0: no mask.
+ * The weight gradients sum over every row of the call: the rows are cut into at most 33 chunks (a multiple of 256 rows each, fixed by the padded row count
+ * alone), one product per chunk into fp32 partials, then amds_colsum over the chunks.
+ * Limits (AMDS_ERR_INVALID, and 0 from the *_bytes entries, with amds_last_error naming the rule): every width >= 1, n_feats, L, classes <= 65536, D <= 32768,
+ * 2 D L and L n_feats <= 2^30; 1 <= bags <= 2^24; total_rows >= bags; total_rows <= 65535 * 64 - 256.  The *_bytes entries run on the host alone (no device needed).
+ * Saved state of a training forward: (L + 2 D + 2) * 4 bytes per row of the padded row count (h; tanh | sigmoid before their dropouts; score; probability) plus
+ * L * 4 bytes per bag (M), each region rounded up to 256 bytes; nothing N x N and no copy of x is kept (the backward stages x again).
+ * Arenas and workspaces 256-byte aligned; too small is AMDS_ERR_WORKSPACE before anything is launched.  Launches only, on `stream`. */
+typedef struct { int n_feats, L, D, classes; } amds_abmil_cfg;
+typedef struct {
+    const float* fc_w;  const float* fc_b;    /* [L][n_feats], [L]   attention_net.0 */
+    const float* a_w;   const float* a_b;     /* [D][L], [D]         attention_net.3.attention_a.0 */
+    const float* b_w;   const float* b_b;     /* [D][L], [D]         attention_net.3.attention_b.0 */
+    const float* c_w;   const float* c_b;     /* [1][D], [1]         attention_net.3.attention_c */
+    const float* cls_w; const float* cls_b;   /* [classes][L], [classes]   classifiers */
+} amds_abmil_weights;
+typedef struct { float *fc_w, *fc_b, *a_w, *a_b, *b_w, *b_b, *c_w, *c_b, *cls_w, *cls_b; } amds_abmil_grads;      /* shaped like the weights; overwritten */
+typedef struct { float p_fc, p_gate; uint64_t seed; } amds_abmil_dropout;
+int amds_abmil_row_pad(void);
+size_t amds_abmil_workspace_bytes(const amds_abmil_cfg* cfg_host, int bags, long total_rows);
+size_t amds_abmil_train_saved_bytes(const amds_abmil_cfg* cfg_host, int bags, long total_rows);
+size_t amds_abmil_train_workspace_bytes(const amds_abmil_cfg* cfg_host, int bags, long total_rows);      /* serves the training forward and the backward */
+/* logits fp32 [bags][classes]; attn_raw fp32 [total_rows] (the scores s, before the softmax) or NULL; pooled fp32 [bags][L] (M) or NULL */
+int amds_abmil_forward(const amds_abmil_cfg* cfg_host, const amds_abmil_weights* w_host, const void* x, int x_dtype, const long long* row_offsets, int bags,
+                       long total_rows, float* logits, float* attn_raw, float* pooled, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_abmil_workspace_bytes) is written. */
+int amds_abmil_train_forward(const amds_abmil_cfg* cfg_host, const amds_abmil_weights* w_host, const void* x, int x_dtype, const long long* row_offsets, int bags,
+                             long total_rows, const amds_abmil_dropout* drop_host, float* logits, void* saved, size_t saved_bytes, void* ws, size_t ws_bytes,
+                             void* stream);
+/* The backward of that forward: the same x, row_offsets and drop_host; dlogits fp32 [bags][classes].  grads_host: all ten parameter gradients are written
+ * (NULL: the input gradient only); dx fp32 [total_rows][n_feats], the gradient w.r.t. x, is written only when the pointer is not NULL.  One of the two must
+ * be given. */
+int amds_abmil_train_backward(const amds_abmil_cfg* cfg_host, const amds_abmil_weights* w_host, const void* x, int x_dtype, const long long* row_offsets, int bags,
+                              long total_rows, const amds_abmil_dropout* drop_host, const float* dlogits, const void* saved, size_t saved_bytes,
+                              const amds_abmil_grads* grads_host, float* dx, void* ws, size_t ws_bytes, void* stream);
+/* saved, ws: contents on entry are ignored (the calls initialise every byte they read);
+ *     nothing outside [saved, saved + amds_abmil_train_saved_bytes) and [ws, ws + amds_abmil_train_workspace_bytes) is written. */
+
 /* Backward pieces of the TransMIL head (training: the reference differentiates trans_mil.py with autograd inside
  * LitTileClassifier._step, src/stamp/modeling/models/__init__.py:239-279); fp32 like the forward.  The matrix products of the
  * backward are amds_bgemm_f32 calls.

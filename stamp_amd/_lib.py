@@ -197,6 +197,22 @@ class GapWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("fc_w", "fc_b", "a_w", "a_b", "b_w", "b_b", "c_w", "c_b", "packed")]
 
 
+class AbmilCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n_feats", "L", "D", "classes")]
+
+
+class AbmilWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("fc_w", "fc_b", "a_w", "a_b", "b_w", "b_b", "c_w", "c_b", "cls_w", "cls_b")]
+
+
+class AbmilGrads(C.Structure):
+    _fields_ = AbmilWeights._fields_
+
+
+class AbmilDropout(C.Structure):
+    _fields_ = [("p_fc", C.c_float), ("p_gate", C.c_float), ("seed", C.c_uint64)]
+
+
 _vp, _i, _l, _f, _sz = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
 _u64, _u32 = C.c_uint64, C.c_uint32
 
@@ -441,6 +457,13 @@ PROTOTYPES = {
     "amds_gated_attn_pool_batched": (_i, [_vp, _vp, _i, _l, C.POINTER(GapWeights), _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "amds_gated_attn_pool_unfused_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "amds_gated_attn_pool_unfused": (_i, [_vp, C.POINTER(GapWeights), _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "amds_abmil_row_pad": (_i, []),
+    "amds_abmil_workspace_bytes": (_sz, [_vp, _i, _l]),
+    "amds_abmil_train_saved_bytes": (_sz, [_vp, _i, _l]),
+    "amds_abmil_train_workspace_bytes": (_sz, [_vp, _i, _l]),
+    "amds_abmil_forward": (_i, [_vp, _vp, _vp, _i, _vp, _i, _l, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "amds_abmil_train_forward": (_i, [_vp, _vp, _vp, _i, _vp, _i, _l, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "amds_abmil_train_backward": (_i, [_vp, _vp, _vp, _i, _vp, _i, _l, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -64,9 +64,10 @@ def _ragged_outputs(model, batches, device, bags_per_call: int, max_rows_per_cal
     A TransMIL head groups by padded token rows (`TransMIL.forward_ragged`, transmil_core.group_bags_padded): each batch's row is the batch-1 forward's to fp32
     rounding (the packed products may take another tile shape than a one-bag call's)."""
     from . import mil_core
+    from .abmil import GatedAttentionMIL
     from .mil import TransMIL
 
-    trans = isinstance(model, TransMIL)
+    trans = isinstance(model, (TransMIL, GatedAttentionMIL))          # heads whose forward_ragged groups for itself
     limit = 0 if trans else mil_core.max_shared_tiles(model._infer_pack(torch.device(device)))
     outs: list = []
     pend: list = []
@@ -162,9 +163,10 @@ def predict_(model: torch.nn.Module, batches: Iterable, patient_ids: Sequence[st
             cat = {t: torch.softmax(v, dim=1) for t, v in cat.items()}
         n = next(iter(cat.values())).shape[0]
         return {pid: {t: cat[t][i] for t in cat} for i, pid in enumerate(list(patient_ids)[:n])}
+    from .abmil import GatedAttentionMIL
     from .mil import TransMIL, VisionTransformer
 
-    if bags_per_call > 1 and isinstance(model, (VisionTransformer, TransMIL)):
+    if bags_per_call > 1 and isinstance(model, (VisionTransformer, TransMIL, GatedAttentionMIL)):
         outs = _ragged_outputs(model, batches, device, bags_per_call, max_rows_per_call)
     else:
         outs = []

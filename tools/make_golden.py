@@ -138,6 +138,40 @@ def golden_chief() -> None:
              **{k: v for k, v in sd_np(model).items() if k.startswith("w:attention_net.")})  # only the used path
 
 
+def golden_abmil() -> None:
+    """The reference's CHIEFModel used as an attention-MIL classifier (stamp_amd/abmil.py): `CHIEFModel(size_arg="xs", n_classes=2)` in eval mode on two bags of
+    77 and 40 rows, `classifiers(WSI_feature_transformed)` per bag, and autograd's gradients of every used parameter for cross_entropy(logits, [0, 1]).  The
+    attention network's weights are those of chief_gated_attention_xs.npz (not stored again); `classifiers.*` is stored.  x holds fp16 values (stored as fp16)."""
+    import torch.nn as nn
+    import torch.nn.functional as F
+
+    glb = {"nn": nn, "torch": torch, "F": F}
+    exec_defs(REF / "encoding" / "encoder" / "chief.py", {"CHIEFModel", "Attn_Net_Gated", "Attn_Net", "Att_Head", "initialize_weights"}, glb)
+    torch.manual_seed(4100)
+    model = glb["CHIEFModel"](size_arg="xs", dropout=True, n_classes=2).eval()
+    base = np.load(OUT / "chief_gated_attention_xs.npz")
+    with torch.no_grad():
+        for k, p in model.named_parameters():
+            if k.startswith("attention_net."):
+                p.copy_(torch.from_numpy(base["w:" + k]))
+        model.classifiers.bias.add_(0.1 * torch.randn_like(model.classifiers.bias))
+    lengths = (77, 40)
+    x16 = (torch.randn(sum(lengths), model.size_dict["xs"][0]) * 0.7).half()
+    raws, pooled, logits = [], [], []
+    for xb in x16.float().split(lengths):
+        out = model(xb)
+        raws.append(out["attention_raw"].reshape(-1))
+        pooled.append(out["WSI_feature_transformed"].reshape(-1))
+        logits.append(model.classifiers(out["WSI_feature_transformed"]).reshape(-1))
+    lg = torch.stack(logits)
+    loss = F.cross_entropy(lg, torch.tensor([0, 1]))
+    used = {k: p for k, p in model.named_parameters() if k.startswith(("attention_net.", "classifiers."))}
+    grads = torch.autograd.grad(loss, list(used.values()))
+    save("abmil_xs.npz", x=x16.numpy(), lengths=np.array(lengths), attention_raw=torch.cat(raws).detach().numpy(),
+         WSI_feature_transformed=torch.stack(pooled).detach().numpy(), logits=lg.detach().numpy(), loss=loss.detach().numpy(), size_arg=np.array("xs"),
+         **{"w:" + k: v.detach().numpy() for k, v in used.items() if k.startswith("classifiers.")}, **{"g:" + k: g.numpy() for k, g in zip(used, grads)})
+
+
 def golden_eagle() -> None:
     """EAGLE slide encoder: the reference's own `_generate_slide_embedding` (run as a plain function on a stand-in `self` holding the reference's
     CHIEFModel) and its coordinate alignment helper, on seeded inputs."""
@@ -1284,7 +1318,12 @@ def golden_reference_facts() -> None:
 
 def main() -> None:
     install_shims()
+    if len(sys.argv) > 1:          # python tools/make_golden.py golden_abmil ...: only the named fixtures
+        for name in sys.argv[1:]:
+            globals()[name]()
+        return
     golden_chief()
+    golden_abmil()
     golden_eagle()
     golden_barspoon()
     golden_ticon()
