@@ -1653,6 +1653,27 @@ int amds_abmil_train_backward(const amds_abmil_cfg* cfg_host, const amds_abmil_w
 /* saved, ws: contents on entry are ignored (the calls initialise every byte they read);
  *     nothing outside [saved, saved + amds_abmil_train_saved_bytes) and [ws, ws + amds_abmil_train_workspace_bytes) is written. */
 
+/* Heat-map scores of the gated-attention head, ONE call per slide or per batch of slides: the eval forward's logits, scores and softmax weights, the
+ * Grad-CAM scores of ALL classes and every tile's logits as a bag of its own.  Conventions, limits and precision as amds_abmil_forward.
+ * Grad-CAM (reference src/stamp/heatmaps/__init__.py:43-54, `_gradcam_single` :126-137): cam_raw[c][n] = | mean_f x_nf d logit_c / d x_nf |.  For this head, in
+ * eval mode (t = tanh(a_w h + a_b), q = sigmoid(b_w h + b_b), c_w written w_c), the chain rule gives a closed form whose one product does not depend on c:
+ *   u_n = w_c o q_n o (1 - t_n^2)      v_n = w_c o t_n o q_n o (1 - q_n)      r_n = [u_n | v_n] [a_w ; b_w]   [L]      (ONE [rows x 2D] . [2D x L] product)
+ *   e_n = (h_n - fc_b) o [h_n > 0]     (= fc_w x_n on the live units: x . (fc_w^T dz) = (fc_w x) . dz and dz = 0 where h = 0, so neither x nor fc_w is read again)
+ *   B_n = e_n . r_n      A_nc = e_n . cls_w[c]      g_nc - gbar_c = cls_w[c] . (h_n - M)      (gbar_c = sum_k P_k g_kc = cls_w[c] . M, from the pooled row)
+ *   cam_raw[c][n] = | P_n (A_nc + (g_nc - gbar_c) B_n) | / n_feats
+ * No class loop over the network, no dx, no [classes][rows][n_feats] Jacobian.  The r product is an amds_bgemm_f32 call on the padded row count (it follows
+ * amds_set_matmul_precision; a row's bits depend on its bag alone); all other sums are fp32 in a fixed order: a slide's outputs do not depend on what else is in the call.
+ * Tile scores (:417-427): tile n as a bag of its own has P = 1 and M = h_n, so tile_logits[n] = cls_w h_n + cls_b -- the bits of amds_abmil_forward on that
+ * one-row bag.
+ * logits fp32 [bags][classes], bit for bit amds_abmil_forward's, as are attn_raw fp32 [total_rows] (or NULL); probs fp32 [total_rows], the softmax weights P
+ * (or NULL); cam_raw fp32 [classes][total_rows] (or NULL: neither Grad-CAM kernel nor the r product is launched); tile_logits fp32 [total_rows][classes] (or
+ * NULL: skipped).  With cam_raw or tile_logits: total_rows x classes < 2^31. */
+size_t amds_abmil_heatmap_workspace_bytes(const amds_abmil_cfg* cfg_host, int bags, long total_rows);
+int amds_abmil_heatmap(const amds_abmil_cfg* cfg_host, const amds_abmil_weights* w_host, const void* x, int x_dtype, const long long* row_offsets, int bags,
+                       long total_rows, float* logits, float* attn_raw, float* probs, float* cam_raw, float* tile_logits, void* ws, size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_abmil_heatmap_workspace_bytes) is written. */
+
 /* Backward pieces of the TransMIL head (training: the reference differentiates trans_mil.py with autograd inside
  * LitTileClassifier._step, src/stamp/modeling/models/__init__.py:239-279); fp32 like the forward.  The matrix products of the
  * backward are amds_bgemm_f32 calls.

@@ -462,6 +462,8 @@ PROTOTYPES = {
     "amds_abmil_train_saved_bytes": (_sz, [_vp, _i, _l]),
     "amds_abmil_train_workspace_bytes": (_sz, [_vp, _i, _l]),
     "amds_abmil_forward": (_i, [_vp, _vp, _vp, _i, _vp, _i, _l, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "amds_abmil_heatmap_workspace_bytes": (_sz, [_vp, _i, _l]),
+    "amds_abmil_heatmap": (_i, [_vp, _vp, _vp, _i, _vp, _i, _l, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "amds_abmil_train_forward": (_i, [_vp, _vp, _vp, _i, _vp, _i, _l, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "amds_abmil_train_backward": (_i, [_vp, _vp, _vp, _i, _vp, _i, _l, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
 }

@@ -6,7 +6,8 @@ tiles (:77-79); ``WSI_feature_transformed = A @ h`` (:80) feeds ``classifiers = 
 the reference's (`attention_net.0.*`, `attention_net.3.attention_{a,b}.0.*`, `attention_net.3.attention_c.*`, `classifiers.*`), so CHIEF's pretrained attention
 network loads (`from_chief`) and can be fine-tuned on a cohort.  Out of scope: the un-gated `Attn_Net`, the instance classifiers, CHIEF's text branch.
 
-Everything runs in the library (csrc/abmil.hip): `amds_abmil_forward` (eval), `amds_abmil_train_forward` / `amds_abmil_train_backward` (ONE call each).
+Everything runs in the library (csrc/abmil.hip): `amds_abmil_forward` (eval), `amds_abmil_train_forward` / `amds_abmil_train_backward` (ONE call each),
+`amds_abmil_heatmap` (`heatmap_scores`: logits, attention, Grad-CAM of all classes and per-tile logits of one or many slides in ONE call).
 Every call is ragged by construction -- packed rows plus int64 row offsets --, a dense [B, N, F] batch is equal offsets.  The three products per row follow
 `torch.get_float32_matmul_precision()` exactly as TransMIL does ("highest": exact fp32 MFMA; below: bf16 x 3, `ops.sync_float32_matmul_precision`).  A bag's
 eval logits do not depend on what else is in the call, at every length (include/amdstamp.h), so `forward_ragged` groups by count and rows alone.
@@ -93,6 +94,25 @@ def forward_infer(w, dims, x: torch.Tensor, offsets: torch.Tensor, n_bags: int, 
                                       ops._p(pooled), ws.data_ptr(), ws.numel(), ops._stream()), "abmil_forward")
     out = (logits,) + ((attn,) if return_attn else ()) + ((pooled,) if return_pooled else ())
     return out if len(out) > 1 else logits
+
+
+def heatmap_scores(w, dims, x: torch.Tensor, offsets: torch.Tensor, n_bags: int, *, want_cam: bool = True, want_tiles: bool = True) -> dict:
+    """Packed rows [rows, F] + int64 device offsets [n_bags + 1] -> dict(logits [n_bags, C], attn_raw [rows], probs [rows] (the softmax weights),
+    cam_raw [C, rows] or None, tile_logits [rows, C] or None) in ONE library call (amds_abmil_heatmap): the eval forward's bits, the Grad-CAM scores of all
+    classes before the softmax over the tiles (reference src/stamp/heatmaps/__init__.py:43-54) in closed form, and every tile's logits as a bag of its own
+    (:417-427).  An output that is not wanted costs nothing."""
+    x = _rows(x, dims)
+    dev, rows = x.device, x.shape[0]
+    lib, cfg = _lib.lib(), _cfg(dims)
+    ws = ops.scratch("abmil_heatmap", dev, _need(lib.amds_abmil_heatmap_workspace_bytes, cfg, n_bags, rows, "abmil_heatmap_workspace_bytes"))
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+    out = {"logits": new(n_bags, dims[3]), "attn_raw": new(rows), "probs": new(rows), "cam_raw": new(dims[3], rows) if want_cam else None,
+           "tile_logits": new(rows, dims[3]) if want_tiles else None}
+    ops.sync_float32_matmul_precision()
+    _lib.check(lib.amds_abmil_heatmap(C.byref(cfg), C.byref(w), x.data_ptr(), ops._DT[x.dtype], offsets.data_ptr(), n_bags, rows, out["logits"].data_ptr(),
+                                      out["attn_raw"].data_ptr(), out["probs"].data_ptr(), ops._p(out["cam_raw"]), ops._p(out["tile_logits"]), ws.data_ptr(), ws.numel(),
+                                      ops._stream()), "abmil_heatmap")
+    return out
 
 
 def forward_train(w, dims, x: torch.Tensor, offsets: torch.Tensor, n_bags: int, *, p_fc: float, p_gate: float, seed: int):
@@ -293,6 +313,27 @@ class GatedAttentionMIL(nn.Module):
             outs.append(self.forward_infer_ragged(mil_core.pack_bags(bags[a:e], n_feats=self.dims[0])))
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
 
+    def heatmap_scores(self, bags, *, want_cam: bool = True, want_tiles: bool = True, bags_per_call: int | None = None,
+                       max_rows_per_call: int = MAX_ROWS_PER_CALL) -> dict:
+        """One slide [N, dim_input] or a list of slides [N_i, dim_input] -> the dict of `heatmap_scores` over the slides' rows back to back (logits
+        [slides, C], attn_raw / probs [rows], cam_raw [C, rows], tile_logits [rows, C]), one library call per group of `forward_ragged`'s grouping (default: as
+        few calls as the library's row limit allows).  A slide's values are bit for bit those of its own call.  eval + no_grad only, like `forward_ragged`."""
+        self._check_infer("heatmap_scores")
+        bags = [bags] if isinstance(bags, torch.Tensor) else list(bags)
+        lengths = mil_core._validate_bags(bags, None, self.dims[0], False)
+        if not bags:
+            raise ValueError("heatmap_scores needs at least one slide")
+        if not bags[0].is_cuda:
+            raise RuntimeError("HIP GatedAttentionMIL needs bags on the GPU (no CPU fallback)")
+        outs = []
+        for a, e in group_bags(lengths, bags_per_call or len(bags), max_rows_per_call):
+            x = bags[a] if e - a == 1 else mil_core.pack_bags(bags[a:e], n_feats=self.dims[0]).feats
+            outs.append(heatmap_scores(self._c_weights(x.device), self.dims, x, _offsets(lengths[a:e], x.device), e - a, want_cam=want_cam, want_tiles=want_tiles))
+        if len(outs) == 1:
+            return outs[0]
+        cat = {"logits": 0, "attn_raw": 0, "probs": 0, "cam_raw": 1, "tile_logits": 0}
+        return {k: None if outs[0][k] is None else torch.cat([o[k] for o in outs], dim=d) for k, d in cat.items()}
+
     @torch.no_grad()
     def attention(self, bag: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
         """One bag [N, dim_input] -> (softmax weights [N], raw scores [N]) of the eval forward (what CHIEF reports as `attention_raw`, chief.py:77-84)."""
@@ -441,4 +482,4 @@ class HipAbmilTrainer:
         return group_bags(lengths, per_call, self.valid_max_rows_per_call)
 
 
-__all__ = ["GatedAttentionMIL", "HipAbmilTrainer", "CHIEF_SIZES", "KEYS", "forward_infer", "forward_train", "backward", "dropout_masks", "group_bags"]
+__all__ = ["GatedAttentionMIL", "HipAbmilTrainer", "CHIEF_SIZES", "KEYS", "forward_infer", "forward_train", "backward", "heatmap_scores", "dropout_masks", "group_bags"]

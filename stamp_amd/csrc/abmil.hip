@@ -51,6 +51,15 @@ void ab_eval_ws(const AbDims& d, AbEvalWs* w) {
     w->k.wab = ar.take((size_t)2 * d.D * d.L * 4); w->k.bab = ar.take((size_t)2 * d.D * 4);
     w->total = ar.off;
 }
+// heat-map workspace: the eval workspace, then r [rows_p][L] and the bag of every row
+struct AbHeatWs { AbEvalWs e; size_t r, rowbag, total; };
+void ab_heat_ws(const AbDims& d, AbHeatWs* w) {
+    ab_eval_ws(d, &w->e);
+    Arena ar;
+    ar.off = w->e.total;
+    w->r = ar.take((size_t)d.rows_p * d.L * 4); w->rowbag = ar.take((size_t)d.rows * 4);
+    w->total = ar.off;
+}
 // saved state of a training forward: h (after ReLU and dropout), tanh | sigmoid BEFORE their dropouts, score and probability per row; the pooled row per bag
 struct AbSaved { size_t h, tg, s, p, m, total; };
 void ab_saved(const AbDims& d, AbSaved* s) {
@@ -299,6 +308,121 @@ __global__ void __launch_bounds__(256) ab_dh_finish_kernel(float* __restrict__ d
     }
 }
 
+// ---- heat map (amds_abmil_heatmap) --------------------------------------------------------------------------------------------------------------------------------
+// 16 bytes a lane where a row's pitch allows it.  ALIGNED = false: the tensor is a caller's weight (no alignment asked of it), four 4-byte loads.
+template <bool ALIGNED>
+__device__ __forceinline__ float4 ab_ld4(const float* p) {
+    if constexpr (ALIGNED) return *reinterpret_cast<const float4*>(p);
+    else return make_float4(p[0], p[1], p[2], p[3]);
+}
+// One wave per row of [rows_p]: the gate vectors u = w_c o q o (1 - t^2) | v = w_c o t o q o (1 - q) written over the saved t | q (eval: no masks); zero on the
+// padding rows -- the buffer is an operand of a product over rows_p.  VEC (D % 4 == 0): lanes own four consecutive columns.
+template <bool VEC>
+__global__ void __launch_bounds__(256) ab_cam_gate_kernel(float* __restrict__ tq, const float* __restrict__ wc, long rows, long rows_p, int D) {
+    const int lane = threadIdx.x & 63;
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows_p) return;
+    float* row = tq + r * 2 * D;
+    if (r >= rows) {
+        for (int d = lane; d < 2 * D; d += 64) row[d] = 0.f;
+        return;
+    }
+    if constexpr (VEC) {
+        for (int d = lane * 4; d < D; d += 256) {
+            const float4 t = *reinterpret_cast<const float4*>(row + d), q = *reinterpret_cast<const float4*>(row + D + d), w = ab_ld4<false>(wc + d);
+            *reinterpret_cast<float4*>(row + d) = make_float4(w.x * q.x * (1.f - t.x * t.x), w.y * q.y * (1.f - t.y * t.y), w.z * q.z * (1.f - t.z * t.z), w.w * q.w * (1.f - t.w * t.w));
+            *reinterpret_cast<float4*>(row + D + d) = make_float4(w.x * t.x * q.x * (1.f - q.x), w.y * t.y * q.y * (1.f - q.y), w.z * t.z * q.z * (1.f - q.z), w.w * t.w * q.w * (1.f - q.w));
+        }
+    } else {
+        for (int d = lane; d < D; d += 64) {
+            const float t = row[d], q = row[D + d], w = wc[d];
+            row[d] = w * q * (1.f - t * t);
+            row[D + d] = w * t * q * (1.f - q);
+        }
+    }
+}
+// The three sums of one row for NC classes c0 .. c0 + NC - 1: B = e . r (first group only), A_c = e . W_cls[c], G_c = (h - M) . W_cls[c] with
+// e = (h - b_fc) o [h > 0].  Lanes own columns l = 4 lane + 256 k (VEC) or lane + 64 k, each sum in that order, then the wave butterfly.
+constexpr int AB_CAM_CG = 4;          // classes per pass over a row
+template <int NC, bool VEC, bool WAL>
+__device__ __forceinline__ void ab_cam_pass(const float* __restrict__ hr, const float* __restrict__ rr, const float* __restrict__ mb, const float* __restrict__ bf,
+                                            const float* __restrict__ W, int L, int lane, bool first, float* B, float (&A)[AB_CAM_CG], float (&G)[AB_CAM_CG]) {
+    float b = 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) A[c] = G[c] = 0.f;
+    if constexpr (VEC) {
+        for (int l = lane * 4; l < L; l += 256) {
+            const float4 hv = *reinterpret_cast<const float4*>(hr + l), mv = *reinterpret_cast<const float4*>(mb + l), bv = ab_ld4<WAL>(bf + l);
+            const float e0 = hv.x > 0.f ? hv.x - bv.x : 0.f, e1 = hv.y > 0.f ? hv.y - bv.y : 0.f, e2 = hv.z > 0.f ? hv.z - bv.z : 0.f, e3 = hv.w > 0.f ? hv.w - bv.w : 0.f;
+            if (first) {
+                const float4 rv = *reinterpret_cast<const float4*>(rr + l);
+                b = fmaf(e0, rv.x, b); b = fmaf(e1, rv.y, b); b = fmaf(e2, rv.z, b); b = fmaf(e3, rv.w, b);
+            }
+            const float d0 = hv.x - mv.x, d1 = hv.y - mv.y, d2 = hv.z - mv.z, d3 = hv.w - mv.w;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const float4 wv = ab_ld4<WAL>(W + (long)c * L + l);
+                A[c] = fmaf(e0, wv.x, A[c]); A[c] = fmaf(e1, wv.y, A[c]); A[c] = fmaf(e2, wv.z, A[c]); A[c] = fmaf(e3, wv.w, A[c]);
+                G[c] = fmaf(d0, wv.x, G[c]); G[c] = fmaf(d1, wv.y, G[c]); G[c] = fmaf(d2, wv.z, G[c]); G[c] = fmaf(d3, wv.w, G[c]);
+            }
+        }
+    } else {
+        for (int l = lane; l < L; l += 64) {
+            const float hv = hr[l];
+            const float e = hv > 0.f ? hv - bf[l] : 0.f, dm = hv - mb[l];
+            if (first) b = fmaf(e, rr[l], b);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const float wv = W[(long)c * L + l];
+                A[c] = fmaf(e, wv, A[c]);
+                G[c] = fmaf(dm, wv, G[c]);
+            }
+        }
+    }
+    if (first) *B = wave_sum(b);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) { A[c] = wave_sum(A[c]); G[c] = wave_sum(G[c]); }
+}
+// One wave per row (a workgroup's four waves walk the rows 4 blockIdx + w, + 4 gridDim, ...): cam_raw[c][n] = | P_n (A_nc + G_nc B_n) | / F for every class, the
+// classes in groups of AB_CAM_CG and a remainder.  G_nc = W_cls[c] . (h_n - M_bag(n)) is g_nc - gbar_c with gbar taken from the POOLED row, the difference formed
+// per element before the dot.  LDSW: W_cls [C][L] and b_fc [L] staged in LDS once per workgroup (b_fc is then read from memory once per thread); otherwise both
+// are read through the caches.  VEC: L % 4 == 0, 16-byte reads of h, r and M (workspace rows, 16-byte aligned then) and of the LDS copies.
+template <bool VEC, bool LDSW>
+__global__ void __launch_bounds__(256) ab_cam_kernel(const float* __restrict__ h, const float* __restrict__ rr, const float* __restrict__ p, const float* __restrict__ m,
+                                                     const int* __restrict__ rowbag, const float* __restrict__ bfc, const float* __restrict__ wcls, float* __restrict__ cam,
+                                                     long rows, int L, int C, float n_feats) {
+    extern __shared__ __align__(16) float ab_cam_lds[];
+    const float *W = wcls, *bf = bfc;
+    if constexpr (LDSW) {
+        const long CL = (long)C * L;
+        for (long i = threadIdx.x; i < CL; i += 256) ab_cam_lds[i] = wcls[i];
+        for (int i = threadIdx.x; i < L; i += 256) ab_cam_lds[CL + i] = bfc[i];
+        __syncthreads();
+        W = ab_cam_lds; bf = ab_cam_lds + CL;
+    }
+    const int lane = threadIdx.x & 63;
+    for (long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (long)gridDim.x * 4) {          // (no barrier inside: waves run free)
+        const float *hr = h + r * L, *rrow = rr + r * L, *mb = m + (long)rowbag[r] * L;
+        const float pn = p[r];
+        float B = 0.f, A[AB_CAM_CG], G[AB_CAM_CG];
+        for (int c0 = 0; c0 < C; c0 += AB_CAM_CG) {
+            const int nc = min(AB_CAM_CG, C - c0);
+            const float* Wc = W + (long)c0 * L;
+            if (nc == 4) ab_cam_pass<4, VEC, VEC && LDSW>(hr, rrow, mb, bf, Wc, L, lane, c0 == 0, &B, A, G);
+            else if (nc == 3) ab_cam_pass<3, VEC, VEC && LDSW>(hr, rrow, mb, bf, Wc, L, lane, c0 == 0, &B, A, G);
+            else if (nc == 2) ab_cam_pass<2, VEC, VEC && LDSW>(hr, rrow, mb, bf, Wc, L, lane, c0 == 0, &B, A, G);
+            else ab_cam_pass<1, VEC, VEC && LDSW>(hr, rrow, mb, bf, Wc, L, lane, c0 == 0, &B, A, G);
+            if (lane < nc) {
+                float a = A[0], g = G[0];
+#pragma unroll
+                for (int c = 1; c < AB_CAM_CG; ++c)
+                    if (lane == c) { a = A[c]; g = G[c]; }
+                cam[(long)(c0 + lane) * rows + r] = fabsf(pn * fmaf(g, B, a)) / n_feats;
+            }
+        }
+    }
+}
+
 inline unsigned ab_grid1d(long n) { return (unsigned)std::max<long>(1, std::min<long>(8192, (n + 255) / 256)); }
 
 bool ab_weights_complete(const amds_abmil_weights& w) { return w.fc_w && w.fc_b && w.a_w && w.a_b && w.b_w && w.b_b && w.c_w && w.c_b && w.cls_w && w.cls_b; }
@@ -406,6 +530,79 @@ extern "C" int amds_abmil_forward(const amds_abmil_cfg* cfg_host, const amds_abm
     auto f = [&](size_t off) { return reinterpret_cast<float*>(wk + off); };
     return ab_forward_body(d, *w_host, x, x_dtype, row_offsets, 0.f, 0.f, 0, f(k.xs), f(k.k.wab), f(k.k.bab), f(k.h), f(k.ab), attn_raw ? attn_raw : f(k.s), f(k.p),
                            pooled ? pooled : f(k.m), logits, stream);
+}
+
+extern "C" size_t amds_abmil_heatmap_workspace_bytes(const amds_abmil_cfg* cfg_host, int bags, long total_rows) {
+    AbDims d; AbHeatWs w;
+    if (ab_dims(cfg_host, bags, total_rows, &d, "amds_abmil_heatmap_workspace_bytes") != AMDS_OK) return 0;
+    ab_heat_ws(d, &w);
+    return w.total;
+}
+
+namespace amds {
+namespace {
+constexpr int AB_CAM_LDS_MAX = 160 * 1024, AB_CAM_GRID_MAX = 2048;          // (2048 workgroups of four waves: eight waves a SIMD on 256 CUs)
+// what ab_cam_kernel stages in LDS: W_cls [C][L] and b_fc [L]
+inline long ab_cam_lds_bytes(const AbDims& d) { return ((long)d.C * d.L + d.L) * 4; }
+// the one step of the Grad-CAM launches that can fail: taken BEFORE the call's first launch, so that a refused call launches nothing
+int ab_cam_prepare(const AbDims& d) {
+    const long lds = ab_cam_lds_bytes(d);
+    if (lds <= 64 * 1024 || lds > AB_CAM_LDS_MAX) return AMDS_OK;
+    if (d.L % 4 == 0) AMDS_HIP(lds_opt_in<ab_cam_kernel<true, true>>(AB_CAM_LDS_MAX));
+    else AMDS_HIP(lds_opt_in<ab_cam_kernel<false, true>>(AB_CAM_LDS_MAX));
+    return AMDS_OK;
+}
+template <bool VEC, bool LDSW>
+int ab_cam_launch(const AbDims& d, int lds, const float* h, const float* r, const float* p, const float* m, const int* rowbag, const amds_abmil_weights& w, float* cam,
+                  hipStream_t st) {
+    const unsigned grid = (unsigned)std::min<long>((d.rows + 3) / 4, AB_CAM_GRID_MAX);
+    hipLaunchKernelGGL((ab_cam_kernel<VEC, LDSW>), dim3(grid), dim3(256), LDSW ? lds : 0, st, h, r, p, m, rowbag, w.fc_b, w.cls_w, cam, d.rows, d.L, d.C, (float)d.F);
+    AMDS_LAUNCH_CHECK("ab_cam_kernel");
+    return AMDS_OK;
+}
+}  // namespace
+}  // namespace amds
+
+extern "C" int amds_abmil_heatmap(const amds_abmil_cfg* cfg_host, const amds_abmil_weights* w_host, const void* x, int x_dtype, const long long* row_offsets, int bags,
+                                  long total_rows, float* logits, float* attn_raw, float* probs, float* cam_raw, float* tile_logits, void* ws, size_t ws_bytes,
+                                  void* stream) {
+    const char* who = "amds_abmil_heatmap";
+    AbDims d; AbHeatWs k;
+    RC(ab_dims(cfg_host, bags, total_rows, &d, who));
+    RC(ab_check_call(who, w_host, x, x_dtype, row_offsets, bags));
+    AMDS_REQUIRE(logits && ws, "%s: null pointer", who);
+    AMDS_REQUIRE(!(cam_raw || tile_logits) || d.rows * d.C < (1L << 31), "%s: total_rows=%ld x classes=%d (cam_raw and tile_logits hold fewer than 2^31 elements)", who, d.rows, d.C);
+    ab_heat_ws(d, &k);
+    if (ws_bytes < k.total) { set_error("%s: workspace %zu < required %zu bytes", who, ws_bytes, k.total); return AMDS_ERR_WORKSPACE; }
+    AMDS_REQUIRE(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+    hipStream_t st = (hipStream_t)stream;
+    const amds_abmil_weights& w = *w_host;
+    char* wk = reinterpret_cast<char*>(ws);
+    auto f = [&](size_t off) { return reinterpret_cast<float*>(wk + off); };
+    float *h = f(k.e.h), *tq = f(k.e.ab), *m = f(k.e.m), *r = f(k.r), *p = probs ? probs : f(k.e.p);
+    if (cam_raw) RC(ab_cam_prepare(d));
+    RC(ab_forward_body(d, w, x, x_dtype, row_offsets, 0.f, 0.f, 0, f(k.e.xs), f(k.e.k.wab), f(k.e.k.bab), h, tq, attn_raw ? attn_raw : f(k.e.s), p, m, logits, stream));
+    if (tile_logits) {          // a tile as a bag of its own: P = 1, M = h_n -- the classifier over the rows of h
+        const long n_out = d.rows * d.C;
+        hipLaunchKernelGGL(ab_classifier_kernel, dim3((unsigned)((n_out + 3) / 4)), dim3(256), 0, st, h, w.cls_w, w.cls_b, tile_logits, n_out, d.C, d.L);
+        AMDS_LAUNCH_CHECK("ab_classifier_kernel");
+    }
+    if (!cam_raw) return AMDS_OK;
+    int* rowbag = reinterpret_cast<int*>(wk + k.rowbag);
+    AMDS_HIP(hipMemsetAsync(rowbag, 0, (size_t)d.rows * 4, st));     // (an uncovered row reads bag 0's M with P = 0: in bounds, its score is 0)
+    hipLaunchKernelGGL(ab_rowbag_kernel, dim3((unsigned)d.bags), dim3(256), 0, st, rowbag, row_offsets, d.bags, d.rows);
+    AMDS_LAUNCH_CHECK("ab_rowbag_kernel");
+    if (d.D % 4 == 0) hipLaunchKernelGGL(ab_cam_gate_kernel<true>, dim3((unsigned)(d.rows_p / 4)), dim3(256), 0, st, tq, w.c_w, d.rows, d.rows_p, d.D);
+    else hipLaunchKernelGGL(ab_cam_gate_kernel<false>, dim3((unsigned)(d.rows_p / 4)), dim3(256), 0, st, tq, w.c_w, d.rows, d.rows_p, d.D);
+    AMDS_LAUNCH_CHECK("ab_cam_gate_kernel");
+    // r = [u | v] W_ab: the shape of the backward's dh = dab W_ab, on the padded row count like every product of the head
+    RC(amds_bgemm_f32(tq, 2 * d.D, 0, 0, f(k.e.k.wab), d.L, 0, 0, 0, r, d.L, 0, 0, 1, 1, (int)d.rows_p, d.L, 2 * d.D, 1.0f, 0.0f, nullptr, 0, stream));
+    const long lds = ab_cam_lds_bytes(d);
+    const bool vec = d.L % 4 == 0, in_lds = lds <= AB_CAM_LDS_MAX;
+    if (vec && in_lds) return ab_cam_launch<true, true>(d, (int)lds, h, r, p, m, rowbag, w, cam_raw, st);
+    if (vec) return ab_cam_launch<true, false>(d, 0, h, r, p, m, rowbag, w, cam_raw, st);
+    if (in_lds) return ab_cam_launch<false, true>(d, (int)lds, h, r, p, m, rowbag, w, cam_raw, st);
+    return ab_cam_launch<false, false>(d, 0, h, r, p, m, rowbag, w, cam_raw, st);
 }
 
 extern "C" int amds_abmil_train_forward(const amds_abmil_cfg* cfg_host, const amds_abmil_weights* w_host, const void* x, int x_dtype, const long long* row_offsets, int bags,

@@ -22,6 +22,11 @@ Two routes to the Grad-CAM scores:
     eval-mode training forward (`transmil_core.forward_train`), ONE library call for all classes (`transmil_core.gradcam` -> amds_transmil_gradcam: per class
     the backward's launches without parameter gradients down to `_fc1`, then a row-dot against the saved `_fc1` output) and amds_softmax_over_tiles.  fp32
     throughout, operand precision from `torch.get_float32_matmul_precision()` like the module: no fp16, so no overflow re-run.  "auto" does not pick it.
+  * library, closed form (`stamp_amd.abmil.GatedAttentionMIL`; "auto" and "library" both pick it): ONE library call (`abmil.heatmap_scores` ->
+    amds_abmil_heatmap) returns the eval forward's logits, scores and softmax weights, the Grad-CAM scores of ALL classes and every tile's logits as a bag
+    of its own.  The head's Grad-CAM has a closed form whose one product does not depend on the class (include/amdstamp.h): no class loop, no gradient
+    w.r.t. the features, no Jacobian.  `slide_heatmap` makes that one call per slide and also reports the softmax weights (`SlideHeatmap.tile_attention`).
+    The head takes no mask and has no vmap rule, so "jacrev" does not work for it; "fused" is refused.
 The module is put in eval mode for the duration of a call; ALiBi running means are not updated; no parameter receives a `.grad` and `feats` needs no
 `requires_grad`.  There is no CPU fallback: CPU tensors raise.
 """
@@ -33,6 +38,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib, mil_core, ops, transmil_core
+from .abmil import GatedAttentionMIL
 from .mil import TransMIL, VisionTransformer, _all_finite
 
 _FP16_SCALE = 1024.0            # the power of two the fp16 basis vectors carry (as `_MilVitFunction`'s loss scale)
@@ -62,12 +68,15 @@ def _pick(model, method: str) -> str:
     if method not in ("auto", "fused", "jacrev", "library"):
         raise ValueError(f"method must be 'auto', 'fused', 'jacrev' or 'library', got {method!r}")
     fused_ok = isinstance(model, VisionTransformer)
+    if isinstance(model, GatedAttentionMIL) and method in ("auto", "library"):          # its closed form: one library call, the route "auto" takes too
+        return "library"
     if method == "library":          # the head's one-library-call Grad-CAM
         if fused_ok:
             return "fused"
         if isinstance(model, TransMIL):
             return "library"
-        raise ValueError(f"method='library' needs a stamp_amd.mil.VisionTransformer or stamp_amd.mil.TransMIL, got {type(model).__name__}")
+        raise ValueError(f"method='library' needs a stamp_amd.mil.VisionTransformer, stamp_amd.mil.TransMIL or stamp_amd.abmil.GatedAttentionMIL, "
+                         f"got {type(model).__name__}")
     if method == "fused" and not fused_ok:
         raise ValueError(f"method='fused' needs a stamp_amd.mil.VisionTransformer, got {type(model).__name__}")
     return ("fused" if fused_ok else "jacrev") if method == "auto" else method
@@ -109,6 +118,23 @@ def _cam_raw_transmil(model: TransMIL, feats: torch.Tensor) -> torch.Tensor:
     return transmil_core.gradcam(saved)
 
 
+def _abmil_scores(model: GatedAttentionMIL, feats: torch.Tensor, *, want_cam: bool, want_tiles: bool) -> dict:
+    """ONE amds_abmil_heatmap call on one slide (module docstring, the closed-form route; coords are ignored like in the head's forward)."""
+    if feats.shape[1] != model.dims[0]:
+        raise ValueError(f"feats must be [tiles, {model.dims[0]}], got {tuple(feats.shape)}")
+    if feats.shape[0] < 1:
+        raise ValueError("empty bag")
+    with torch.no_grad():
+        return model.heatmap_scores(feats.detach(), want_cam=want_cam, want_tiles=want_tiles)
+
+
+def _cam_raw_library(model: torch.nn.Module, feats: torch.Tensor) -> torch.Tensor:
+    """-> cam_raw [C, N] of the "library" route: TransMIL or the gated-attention head."""
+    if isinstance(model, GatedAttentionMIL):
+        return _abmil_scores(model, feats, want_cam=True, want_tiles=False)["cam_raw"]
+    return _cam_raw_transmil(model, feats)
+
+
 def _cam_raw_jacrev(model: torch.nn.Module, feats: torch.Tensor, coords: torch.Tensor | None, squeeze_all: bool) -> torch.Tensor:
     """The reference's lines :43-54 (`squeeze_all`: :126-137) -> cam before the softmax, [C, N] (or [N])."""
     from torch.func import jacrev
@@ -138,12 +164,13 @@ def _softmax_over_tiles(cam_raw: torch.Tensor) -> torch.Tensor:
 def gradcam(model: torch.nn.Module, feats: torch.Tensor, coords: torch.Tensor | None = None, *, raw: bool = False, method: str = "auto") -> torch.Tensor:
     """reference `_gradcam_per_category` (:36-56): feats [N, F] fp16 / fp32, coords [N, 2] (micrometres; required by an ALiBi head) -> [N, C] fp32, the
     per-class Grad-CAM scores soft-maxed over the tiles; `raw=True`: the scores before that softmax (line 54), [N, C].  `method`: "auto" (fused for the
-    HIP `vit` head, else jacrev), "fused", "jacrev", "library" (the head's one-library-call Grad-CAM: `vit` as "fused", TransMIL through amds_transmil_gradcam)."""
+    HIP `vit` head, the closed-form library call for `abmil.GatedAttentionMIL`, else jacrev), "fused", "jacrev", "library" (the head's one-library-call
+    Grad-CAM: `vit` as "fused", TransMIL through amds_transmil_gradcam, the gated-attention head through amds_abmil_heatmap)."""
     _check_inputs(feats, coords)
     route = _pick(model, method)
     with _eval_mode(model):
         if route in ("fused", "library"):
-            cam_raw = _cam_raw_fused(model, feats, coords) if route == "fused" else _cam_raw_transmil(model, feats)
+            cam_raw = _cam_raw_fused(model, feats, coords) if route == "fused" else _cam_raw_library(model, feats)
             return cam_raw.t().contiguous() if raw else _softmax_over_tiles(cam_raw)
         cam_raw = _cam_raw_jacrev(model, feats, coords, squeeze_all=False)
         if cam_raw.dim() != 2:
@@ -162,7 +189,7 @@ def gradcam_single(model: torch.nn.Module, feats: torch.Tensor, coords: torch.Te
         if route == "fused":
             return _cam_raw_fused(model, feats, coords)[0]
         if route == "library":
-            return _cam_raw_transmil(model, feats)[0]
+            return _cam_raw_library(model, feats)[0]
         cam = _cam_raw_jacrev(model, feats, coords, squeeze_all=True)
         if cam.dim() != 1:
             raise ValueError(f"gradcam_single is for single-output models, the Jacobian reduced to {tuple(cam.shape)}")
@@ -207,12 +234,19 @@ def tile_scores(model: torch.nn.Module, feats: torch.Tensor, coords: torch.Tenso
     needs several runs staged (`transmil_core.forward_infer_grouped`: three passes, the maxima on the device, sub-call sizes that repeat the one call's
     kernel choices) with the bits of the one call, so the result depends neither on `tiles_per_call` nor on the free memory.  This CHANGES what an explicit
     `tiles_per_call` below the slide size returned for a TransMIL before: independent chunks then, each with its own maxima (3e-4 apart in the
-    probabilities); the group's bits now.  Every other call returns the bits it returned."""
+    probabilities); the group's bits now.  Every other call returns the bits it returned.
+
+    `abmil.GatedAttentionMIL` (its forward takes no mask): the classifier over the rows of h (amds_abmil_heatmap's tile_logits, the bits of the head's
+    forward on every one-row bag), `tiles_per_call` ROWS per library call; a row's bits do not depend on the chunk."""
     _check_inputs(feats, coords)
     N = feats.shape[0]
     step = default_tiles_per_call(model, feats.device) if tiles_per_call is None else int(tiles_per_call)
     if step < 1:
         raise ValueError("tiles_per_call must be >= 1")
+    if isinstance(model, GatedAttentionMIL):
+        with _eval_mode(model):
+            outs = [torch.softmax(_abmil_scores(model, feats[a:a + step], want_cam=False, want_tiles=True)["tile_logits"], dim=1) for a in range(0, N, step)]
+        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
     group = step
     if isinstance(model, TransMIL):
         group = transmil_core.MAX_BAGS_PER_CALL
@@ -309,6 +343,7 @@ class SlideHeatmap:
     attention: torch.Tensor | None = None       # [C, N] (:483-494)
     category_score: torch.Tensor | None = None  # [C, N] (:496-498)
     tile_relevance: torch.Tensor | None = None  # regression: gradcam / max [N] (:593)
+    tile_attention: torch.Tensor | None = None  # `abmil.GatedAttentionMIL` alone: the softmax weights over the tiles [N] (chief.py:77-79); None for the other heads
 
 
     def render(self, thumb: torch.Tensor | None = None, *, opacity: float = 0.6, scale: int = 8, train_pred_median: float | None = None) -> "HeatmapImages":
@@ -499,14 +534,39 @@ def ranked_tiles(scores: torch.Tensor, topk: int, bottomk: int):
     return ti[:kt], tv[:kt], bi[:kb], bv[:kb]
 
 
+def _slide_heatmap_abmil(model: GatedAttentionMIL, feats: torch.Tensor, coords_um: torch.Tensor, task: str, tiles_per_call: int | None) -> SlideHeatmap:
+    if tiles_per_call is not None and int(tiles_per_call) < 1:
+        raise ValueError("tiles_per_call must be >= 1")
+    classify = task == "classification"
+    if not classify and model.n_classes != 1:
+        raise ValueError(f"gradcam_single is for single-output models (dim_output == 1), this one has {model.n_classes} outputs: use gradcam")
+    with _eval_mode(model):
+        sc = _abmil_scores(model, feats, want_cam=True, want_tiles=classify)
+    cn = grid_coords(coords_um)
+    logits = sc["logits"][0]
+    if not classify:
+        cam = sc["cam_raw"][0]
+        g2 = vals_to_im(cam, cn)
+        g2 = (g2 - g2.min()) / (g2.max() - g2.min() + 1e-8)
+        return SlideHeatmap(task, logits.squeeze(), cn, cam, g2, tile_relevance=cam / cam.max().clamp(min=1e-8), tile_attention=sc["probs"])
+    cam = _softmax_over_tiles(sc["cam_raw"])
+    scores = torch.softmax(sc["tile_logits"], dim=1)
+    support, attention, cat = category_maps(cam, scores)
+    return SlideHeatmap(task, logits.softmax(0), cn, cam, vals_to_im(cam, cn), scores, vals_to_im(scores, cn), support, attention, cat, tile_attention=sc["probs"])
+
+
 def slide_heatmap(model: torch.nn.Module, feats: torch.Tensor, coords_um: torch.Tensor, *, task: str, method: str = "auto",
                   tiles_per_call: int | None = None) -> SlideHeatmap:
     """One slide, `task` "classification" (:401-498), "regression" (:586-597) or "survival" (:668-679, the regression computation; its colouring is
     `SlideHeatmap.render`'s): slide score, Grad-CAM scores, per-tile scores, their 2-D arrangements and the per-category maps -- the tensors the
-    reference's plotting takes from here.  `method` goes to `gradcam` / `gradcam_single`, `tiles_per_call` to `tile_scores`."""
+    reference's plotting takes from here.  `method` goes to `gradcam` / `gradcam_single`, `tiles_per_call` to `tile_scores`.
+    `abmil.GatedAttentionMIL` on its library route: ONE library call gives all of it (bit for bit what the single functions return: `tiles_per_call`
+    changes no bit for this head and is not needed), and `tile_attention` holds the softmax weights."""
     if task not in ("classification", "regression", "survival"):
         raise ValueError(f"task must be 'classification', 'regression' or 'survival', got {task!r}")
     _check_inputs(feats, coords_um)
+    if isinstance(model, GatedAttentionMIL) and _pick(model, method) == "library":
+        return _slide_heatmap_abmil(model, feats, coords_um, task, tiles_per_call)
     with _eval_mode(model), torch.no_grad():
         logits = model(feats.unsqueeze(0), coords=coords_um.unsqueeze(0), mask=None).squeeze(0)          # :392-399
     cn = grid_coords(coords_um)

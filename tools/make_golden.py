@@ -172,6 +172,53 @@ def golden_abmil() -> None:
          **{"w:" + k: v.detach().numpy() for k, v in used.items() if k.startswith("classifiers.")}, **{"g:" + k: g.numpy() for k, g in zip(used, grads)})
 
 
+def golden_abmil_heatmap() -> None:
+    """The heat-map quantities of the reference's CHIEFModel used as a classifier, from the reference's own functions (src/stamp/heatmaps/__init__.py):
+    `_gradcam_per_category` :36-56 and `_gradcam_single` :115-139 (per class, for the scores before the softmax) on a few-line adapter whose
+    ``forward(bags, coords=, mask=)`` is ``classifiers(CHIEFModel("xs")(bags[0])["WSI_feature_transformed"])``, and the logits of every tile as a bag of its own
+    (:417-427).  Inputs and weights are those of abmil_xs.npz and chief_gated_attention_xs.npz; RESULTS only are stored: cam_<N> (soft-maxed over the tiles)
+    and cam_raw_<N>, both [N, C], for the 77-row and the 40-row bag, and tile_logits [117, C]."""
+    from typing import Optional, cast
+
+    import torch.nn as nn
+    import torch.nn.functional as F
+    from torch import Tensor
+    from torch.func import jacrev
+
+    glb = {"nn": nn, "torch": torch, "F": F}
+    exec_defs(REF / "encoding" / "encoder" / "chief.py", {"CHIEFModel", "Attn_Net_Gated", "Attn_Net", "Att_Head", "initialize_weights"}, glb)
+    hm = exec_defs(REF / "heatmaps" / "__init__.py", {"_gradcam_per_category", "_gradcam_single"},
+                   dict(torch=torch, Tensor=Tensor, jacrev=jacrev, cast=cast, Optional=Optional))
+    fx, base = np.load(OUT / "abmil_xs.npz"), np.load(OUT / "chief_gated_attention_xs.npz")
+    chief = glb["CHIEFModel"](size_arg="xs", dropout=True, n_classes=2).eval()
+    with torch.no_grad():
+        for k, p in chief.named_parameters():
+            if k.startswith("attention_net."):
+                p.copy_(torch.from_numpy(base["w:" + k]))
+            elif k.startswith("classifiers."):
+                p.copy_(torch.from_numpy(fx["w:" + k]))
+
+    class Adapter(torch.nn.Module):
+        def __init__(self, c=None):
+            super().__init__()
+            self.c = c
+
+        def forward(self, bags, *, coords, mask):
+            out = chief.classifiers(chief(bags[0])["WSI_feature_transformed"])
+            return out if self.c is None else out[:, self.c]
+
+    x = torch.from_numpy(fx["x"]).float()
+    lengths = [int(n) for n in fx["lengths"]]
+    arrs = {}
+    for xb in x.split(lengths):
+        N, coords = xb.shape[0], torch.zeros(xb.shape[0], 2)
+        arrs[f"cam_{N}"] = hm["_gradcam_per_category"](Adapter(), xb, coords).detach().numpy()
+        arrs[f"cam_raw_{N}"] = torch.stack([hm["_gradcam_single"](Adapter(c), xb, coords).detach() for c in range(2)], dim=1).numpy()
+    with torch.no_grad():
+        arrs["tile_logits"] = torch.cat([Adapter()(r[None, None], coords=None, mask=None) for r in x]).numpy()
+    save("abmil_heatmap_xs.npz", lengths=np.array(lengths), **arrs)
+
+
 def golden_eagle() -> None:
     """EAGLE slide encoder: the reference's own `_generate_slide_embedding` (run as a plain function on a stand-in `self` holding the reference's
     CHIEFModel) and its coordinate alignment helper, on seeded inputs."""
@@ -1324,6 +1371,7 @@ def main() -> None:
         return
     golden_chief()
     golden_abmil()
+    golden_abmil_heatmap()
     golden_eagle()
     golden_barspoon()
     golden_ticon()
