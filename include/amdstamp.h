@@ -847,6 +847,20 @@ int amds_bag_batch_gather(const void* store, long store_ld, int store_dtype, con
 /* the shifts the call above draws, u8 [n_bags][bag_size][cols] (all 0 when vp_min_fraction_bits == 0); for tests */
 int amds_bag_batch_shifts(uint8_t* shifts, int n_bags, int bag_size, int cols, int vp_min_fraction_bits, uint64_t seed, uint32_t stream_id, void* stream);
 
+/* An epoch's bag indices in ONE launch (csrc/bag_batch.hip): `_to_fixed_size_bag`'s `randperm(rows)[:bag_size]` per patient (reference
+ * src/stamp/modeling/data.py:811-862) in the reference's DISTRIBUTION, drawn from the library's counter-based hash and not from torch's CPU random stream.
+ *   offsets   device int32 [store patients + 1]: patient p owns store rows offsets[p] .. offsets[p + 1]
+ *   patients  device int64 [n]: store patient indices in the epoch's order (repeats allowed); an index outside the store is the caller's error
+ *   idx       device int64 [n][bag_size]: entry j < sizes[b] of bag b = offsets[p] + pi(j), every later entry -1 -- exactly what amds_bag_batch_gather takes
+ *   sizes     device int64 [n] = min(bag_size, rows of the patient); a patient with 0 rows gives size 0 and a row of -1
+ * pi is a keyed bijection of [0, rows) that depends on (seed, epoch, p) only -- never on the patient's position in `patients` or on n: a balanced Feistel
+ * network on 2 * ceil(bits / 2) bits, bits = max(2, ceil(log2 rows)); round function fmix32(half ^ round key) & mask; 12 round keys
+ * fmix32(drop_rowkey(seed, epoch, p) ^ (round + 1) * 0x9E3779B1) (the dropout masks' key function); cycle-walked until the value is < rows, which takes at most
+ * domain - rows + 1 applications (the walk starts inside [0, rows) and the network is a bijection of the domain) -- the loop's trip limit.
+ * n == 0 succeeds without a launch; NULL pointers, bag_size < 1 or n < 0 return AMDS_ERR_INVALID before any launch.  No atomics, no workspace; deterministic;
+ * one launch on `stream`. */
+int amds_bag_plan(const int* offsets, const long* patients, long* idx, long* sizes, int n, int bag_size, uint64_t seed, uint32_t epoch, void* stream);
+
 /* Mean over tiles: x [B][T][F] (f16/f32) -> out fp32 [B][F] (reference src/stamp/modeling/models/mlp.py:40-41). */
 int amds_mean_pool(const void* x, float* out, int B, int T, int F, int in_dtype, void* stream);
 /* its gradient: dx fp32 [B][T][F] = dy[B][F] / T (training the MLP / Linear heads on bags, mlp.py:40-41) */

@@ -305,6 +305,7 @@ PROTOTYPES = {
     "amds_vary_precision": (_i, [_vp, _vp, _vp, _l, _i, _vp]),
     "amds_bag_batch_gather": (_i, [_vp, _l, _i, _vp, _vp, _vp, _l, _i, _vp, _i, _i, _i, _i, _u64, _u32, _vp]),
     "amds_bag_batch_shifts": (_i, [_vp, _i, _i, _i, _i, _u64, _u32, _vp]),
+    "amds_bag_plan": (_i, [_vp, _vp, _vp, _vp, _i, _i, _u64, _u32, _vp]),
     "amds_mean_pool": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "amds_linear_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "amds_mil_vit_workspace_bytes": (_sz, [_vp, _i, _i]),

@@ -11,13 +11,22 @@ and builds a training batch with one `amds_bag_batch_gather` launch (csrc/bag_ba
 data.py:811-862, optionally the reference's `vary_precision` transform).  The packed store IS the layout the ragged inference forwards take
 (`mil_core.RaggedBags`), so a validation group is a view: a row slice and rebased offsets, no copy.
 
-Random draws, per epoch of `train_batches`, all from `generator` (None: torch's global CPU generator), in this order:
-  1. shuffle: ONE `torch.randperm(len(cohort))` -- the patient order of the epoch;
-  2. the bags' own draws, `mil.fixed_size_bag_indices` per patient in that order (a `torch.randperm(n)` for every patient with more than `bag_size` tiles):
-     exactly what fetching `BagDataset` items in that order with `num_workers=0` consumes;
+Random draws, per epoch of `train_batches`, from `generator` (None: torch's global CPU generator), in this order:
+  1. shuffle: ONE `torch.randperm(len(view))` -- the patient order of the epoch;
+  2. the bags' own draws
+       sampler="torch" (default): `mil.fixed_size_bag_indices` per patient in that order (a `torch.randperm(n)` for every patient with more than `bag_size`
+         tiles): exactly what fetching `BagDataset` items in that order with `num_workers=0` consumes;
+       sampler="device": nothing from `generator`.  ONE `amds_bag_plan` launch draws `randperm(n)[:bag_size]` for every patient of the epoch as a bijection
+         keyed on (`seed`, e, store patient index), e = how often the callable `train_batches` returned has been invoked before (0 for the first epoch).  A
+         patient's bag depends on that key alone -- not on its place in the epoch, its batch, or the view it is reached through.  That is the reference's
+         distribution, not torch's random stream (include/amdstamp.h, amds_bag_plan); it needs shuffle=True (the equidistant plan stays on the host);
   3. with `vary_precision_bits`: one `torch.randint` = the epoch's mask seed; batch j masks with (seed, stream_id = j) through the library's counter-based
      hash.  That is the reference transform's distribution, not torch's random stream (include/amdstamp.h, amds_bag_batch_gather).
-The epoch's whole index plan is built on the host and uploaded once; the loop then only launches (no host synchronisation).
+With the host sampler the epoch's whole index plan is built on the host and uploaded once; with the device sampler only the patient order is.  The loop then only
+launches (no host synchronisation).
+
+`ResidentCohort.view(patients)` is a `CohortView`: a list of store patients over the SAME tensors (no copy) with the cohort's own batch methods -- the folds of
+`crossval.crossval` are views of one cohort, read once.  The cohort's methods are those of the view over all its patients.
 There is no spilling: a cohort that does not fit `max_bytes` or the free device memory is refused before anything is allocated.  One device; no CPU fallback."""
 from __future__ import annotations
 
@@ -118,6 +127,8 @@ class ResidentCohort:
             fv, cv = fbuf[:n * Fd].view(n, Fd), cbuf[:n * 2].view(n, 2)
             for f in fs:
                 d, a = h5io.read_file(f)
+                if h5io.feature_type(a) in ("slide", "patient"):
+                    raise ValueError(f"{f}: {h5io.feature_type(a)}-level features; a resident cohort (and crossval on it) takes tile-level feature files")
                 x = np.asarray(d["feats"] if "feats" in d else d["patch_embeddings"])
                 c = np.asarray(h5io.get_coords(d, a).coords_um)
                 if o + x.shape[0] > n or x.shape[1] != Fd or c.shape != (x.shape[0], 2):
@@ -146,54 +157,32 @@ class ResidentCohort:
             return {k: v[sel] for k, v in self._targets_dev.items()}          # the dict `bags.collate_multitarget` builds
         return self._targets_dev[sel]
 
-    # ---- training batches ------------------------------------------------------------------------------------------------------------------------
-    def _epoch(self, batch_size, bag_size, shuffle, generator, out_dtype, vary_precision_bits, drop_last, with_sizes):
-        from . import ops
-        N = len(self)
-        order = torch.randperm(N, generator=generator) if shuffle else torch.arange(N)
-        if drop_last:
-            order = order[:N - N % batch_size]
-        idx, sizes = self.plan_indices(order.tolist(), bag_size, deterministic=not shuffle, generator=generator)
-        bits = int(vary_precision_bits or 0)
-        seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator).item()) if bits else 0
-        idx, sizes, order = idx.to(self.device), sizes.to(self.device), order.to(self.device)          # the epoch's plan: uploaded once
-        for j, a in enumerate(range(0, order.numel(), batch_size)):
-            e = min(a + batch_size, order.numel())
-            bags, coords = ops.bag_batch_gather(self.feats, self.coords, idx[a:e], out_dtype, vary_precision_bits=bits, seed=seed, stream_id=j)
-            targets = self._targets_of(order[a:e])
-            yield (bags, coords, sizes[a:e], targets) if with_sizes else (bags, coords, targets)
+    # ---- views: a list of patients over the same store -------------------------------------------------------------------------------------------
+    def view(self, patients: Iterable[int]) -> "CohortView":
+        """The patients `patients` (store indices, in that order) as a `CohortView`: the folds of a cross-validation are views of ONE cohort."""
+        return CohortView(self, patients)
+
+    def _all(self) -> "CohortView":
+        return CohortView(self, range(len(self)))
 
     def train_batches(self, batch_size: int, bag_size: int, shuffle: bool = True, generator: torch.Generator | None = None,
-                      out_dtype: torch.dtype = torch.float32, vary_precision_bits: int | None = None, drop_last: bool = False):
-        """-> the callable `mil_train.fit` takes: per epoch an iterable of (bags [B, bag_size, F] `out_dtype`, coords fp32 [B, bag_size, 2], bag_sizes int64
-        [B], targets [B, D] -- or the dict of a multi-target cohort) on the device.  Sampling is random when shuffling and equidistant when not, like
-        `tile_bag_dataloader`; the draws and their order: module docstring."""
-        if batch_size < 1 or bag_size < 1:
-            raise ValueError("batch_size and bag_size must be >= 1")
-        return lambda: self._epoch(batch_size, bag_size, shuffle, generator, out_dtype, vary_precision_bits, drop_last, True)
+                      out_dtype: torch.dtype = torch.float32, vary_precision_bits: int | None = None, drop_last: bool = False, sampler: str = "torch",
+                      seed: int = 0):
+        """`CohortView.train_batches` of all patients."""
+        return self._all().train_batches(batch_size, bag_size, shuffle, generator, out_dtype, vary_precision_bits, drop_last, sampler, seed)
 
     def barspoon_batches(self, batch_size: int, bag_size: int, shuffle: bool = True, generator: torch.Generator | None = None,
-                         out_dtype: torch.dtype = torch.float32, vary_precision_bits: int | None = None, drop_last: bool = False):
-        """`train_batches` as the (feats, positions, targets) 3-tuples `HipBarspoonTrainer.fit` takes."""
-        if batch_size < 1 or bag_size < 1:
-            raise ValueError("batch_size and bag_size must be >= 1")
-        return lambda: self._epoch(batch_size, bag_size, shuffle, generator, out_dtype, vary_precision_bits, drop_last, False)
-
-    # ---- validation: views of the store ----------------------------------------------------------------------------------------------------------
-    def _valid(self, with_sizes):
-        for p in range(len(self)):
-            a, n = self.offsets[p], self.lengths[p]
-            item = (self.feats[a:a + n].unsqueeze(0), self.coords[a:a + n].unsqueeze(0))
-            targets = {k: v[p:p + 1] for k, v in self._targets_dev.items()} if self.multi_target else self._targets_dev[p:p + 1]
-            yield (*item, self._lengths_dev[p:p + 1], targets) if with_sizes else (*item, targets)
+                         out_dtype: torch.dtype = torch.float32, vary_precision_bits: int | None = None, drop_last: bool = False, sampler: str = "torch",
+                         seed: int = 0):
+        """`CohortView.barspoon_batches` of all patients."""
+        return self._all().barspoon_batches(batch_size, bag_size, shuffle, generator, out_dtype, vary_precision_bits, drop_last, sampler, seed)
 
     def valid_batches(self):
-        """-> the callable `fit` takes for validation: one whole bag per batch (the reference's `bag_size=None`, batch 1 loader), every tensor a view of the
-        store (features in the store's precision)."""
-        return lambda: self._valid(True)
+        """`CohortView.valid_batches` of all patients."""
+        return self._all().valid_batches()
 
     def barspoon_valid_batches(self):
-        return lambda: self._valid(False)
+        return self._all().barspoon_valid_batches()
 
     def ragged_group(self, a: int, e: int):
         """Patients a .. e - 1 as `mil_core.RaggedBags` for the ragged inference forwards: a row slice of the features and of the coordinates, offsets rebased
@@ -205,4 +194,108 @@ class ResidentCohort:
         return RaggedBags(self.feats[r0:r1], self.coords[r0:r1], self._offsets_dev[a:e + 1] - r0, tuple(self.lengths[a:e]))
 
 
-__all__ = ["ResidentCohort", "plan_indices", "MAX_ROWS"]
+SAMPLERS = ("torch", "device")
+
+
+class CohortView:
+    """A list of store patient indices over a `ResidentCohort`'s own `feats` / `coords` / target tensors: nothing is copied.  With `sampler="torch"` a view over
+    the patients S draws from `generator` exactly what a separate `ResidentCohort` built from `[patient_data[i] for i in S]` draws (one `randperm(len(S))`, then
+    `mil.fixed_size_bag_indices` per patient, which consumes by the patient's length only), so its batches are bit-identical to that cohort's."""
+
+    def __init__(self, cohort: ResidentCohort, patients: Iterable[int]) -> None:
+        self.cohort = cohort
+        self.patients = [int(p) for p in patients]
+        bad = [p for p in self.patients if not 0 <= p < len(cohort)]
+        if bad:
+            raise ValueError(f"patients {bad[:8]} outside 0..{len(cohort)}")
+        self._patients_t = torch.tensor(self.patients, dtype=torch.int64)
+        self._patients_dev = None
+
+    def __len__(self) -> int:
+        return len(self.patients)
+
+    def _on_device(self) -> torch.Tensor:
+        if self._patients_dev is None:
+            self._patients_dev = self._patients_t.to(self.cohort.device)
+        return self._patients_dev
+
+    # ---- training batches ------------------------------------------------------------------------------------------------------------------------
+    def _epoch(self, batch_size, bag_size, shuffle, generator, out_dtype, vary_precision_bits, drop_last, with_sizes, sampler, plan_seed, epoch):
+        from . import ops
+        c = self.cohort
+        N = len(self)
+        order = torch.randperm(N, generator=generator) if shuffle else torch.arange(N)
+        if drop_last:
+            order = order[:N - N % batch_size]
+        if sampler == "device":
+            idx = sizes = None                      # planned on the device, below: no per-patient draw on the host
+        else:
+            idx, sizes = c.plan_indices(self._patients_t[order].tolist(), bag_size, deterministic=not shuffle, generator=generator)
+        bits = int(vary_precision_bits or 0)
+        seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator).item()) if bits else 0
+        if sampler == "device":
+            order = self._on_device()[order.to(c.device)]          # store patient indices in the epoch's order
+            idx, sizes = ops.bag_plan(c._offsets_dev, order, bag_size, plan_seed, epoch)
+        else:
+            idx, sizes, order = idx.to(c.device), sizes.to(c.device), self._patients_t[order].to(c.device)          # the epoch's plan: uploaded once
+        for j, a in enumerate(range(0, order.numel(), batch_size)):
+            e = min(a + batch_size, order.numel())
+            bags, coords = ops.bag_batch_gather(c.feats, c.coords, idx[a:e], out_dtype, vary_precision_bits=bits, seed=seed, stream_id=j)
+            targets = c._targets_of(order[a:e])
+            yield (bags, coords, sizes[a:e], targets) if with_sizes else (bags, coords, targets)
+
+    def _feed(self, batch_size, bag_size, shuffle, generator, out_dtype, vary_precision_bits, drop_last, with_sizes, sampler, seed):
+        if batch_size < 1 or bag_size < 1:
+            raise ValueError("batch_size and bag_size must be >= 1")
+        if sampler not in SAMPLERS:
+            raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
+        if sampler == "device" and not shuffle:
+            raise ValueError('sampler="device" draws random bags; shuffle=False asks for the equidistant plan, which is deterministic and stays on the host')
+        count = iter(range(2 ** 32))          # the epoch number of the device sampler: invocations of the returned callable, from 0
+        return lambda: self._epoch(batch_size, bag_size, shuffle, generator, out_dtype, vary_precision_bits, drop_last, with_sizes, sampler, int(seed),
+                                   next(count))
+
+    def train_batches(self, batch_size: int, bag_size: int, shuffle: bool = True, generator: torch.Generator | None = None,
+                      out_dtype: torch.dtype = torch.float32, vary_precision_bits: int | None = None, drop_last: bool = False, sampler: str = "torch",
+                      seed: int = 0):
+        """-> the callable `mil_train.fit` takes: per epoch an iterable of (bags [B, bag_size, F] `out_dtype`, coords fp32 [B, bag_size, 2], bag_sizes int64
+        [B], targets [B, D] -- or the dict of a multi-target cohort) on the device.  Sampling is random when shuffling and equidistant when not, like
+        `tile_bag_dataloader`.  sampler="torch": the bags' draws come from `generator` on the host; sampler="device": from ONE amds_bag_plan launch keyed
+        (`seed`, epoch = number of earlier invocations of the returned callable, store patient index).  The draws and their order: module docstring."""
+        return self._feed(batch_size, bag_size, shuffle, generator, out_dtype, vary_precision_bits, drop_last, True, sampler, seed)
+
+    def barspoon_batches(self, batch_size: int, bag_size: int, shuffle: bool = True, generator: torch.Generator | None = None,
+                         out_dtype: torch.dtype = torch.float32, vary_precision_bits: int | None = None, drop_last: bool = False, sampler: str = "torch",
+                         seed: int = 0):
+        """`train_batches` as the (feats, positions, targets) 3-tuples `HipBarspoonTrainer.fit` takes."""
+        return self._feed(batch_size, bag_size, shuffle, generator, out_dtype, vary_precision_bits, drop_last, False, sampler, seed)
+
+    # ---- validation: views of the store ----------------------------------------------------------------------------------------------------------
+    def _valid(self, with_sizes):
+        c = self.cohort
+        for p in self.patients:
+            a, n = c.offsets[p], c.lengths[p]
+            item = (c.feats[a:a + n].unsqueeze(0), c.coords[a:a + n].unsqueeze(0))
+            targets = {k: v[p:p + 1] for k, v in c._targets_dev.items()} if c.multi_target else c._targets_dev[p:p + 1]
+            yield (*item, c._lengths_dev[p:p + 1], targets) if with_sizes else (*item, targets)
+
+    def valid_batches(self):
+        """-> the callable `fit` takes for validation: one whole bag per batch (the reference's `bag_size=None`, batch 1 loader), every tensor a view of the
+        store (features in the store's precision)."""
+        return lambda: self._valid(True)
+
+    def barspoon_valid_batches(self):
+        return lambda: self._valid(False)
+
+    def ragged_group(self, a: int, e: int):
+        """Patients a .. e - 1 of the view as `mil_core.RaggedBags` (`ResidentCohort.ragged_group`): they must be consecutive in the store, since the group is
+        one row slice; ValueError otherwise."""
+        if not 0 <= a <= e <= len(self):
+            raise ValueError(f"patients {a}..{e} outside 0..{len(self)}")
+        p0 = self.patients[a] if a < e else 0
+        if self.patients[a:e] != list(range(p0, p0 + e - a)):
+            raise ValueError(f"patients {a}..{e} of the view are not consecutive in the store: {self.patients[a:e][:8]}...")
+        return self.cohort.ragged_group(p0, p0 + e - a)
+
+
+__all__ = ["ResidentCohort", "CohortView", "plan_indices", "MAX_ROWS", "SAMPLERS"]

@@ -3,6 +3,7 @@
 //                             (reference src/stamp/modeling/data.py:811-862 `_to_fixed_size_bag` + the `.float()` of :617, for n_bags bags at once; the
 //                             optional vp is src/stamp/modeling/transforms.py:5-29 with counter-based shifts)
 //   * amds_bag_batch_shifts   the shifts that call draws, as u8, for tests
+//   * amds_bag_plan           an epoch's bag indices (the idx the gather takes) in one launch: randperm(rows)[:bag_size] per patient as a keyed bijection
 // One wave per output row (a row of the store is one contiguous run: 2 KiB at 1 024 fp16 features), lanes over 8-element chunks: 16-byte loads and
 // stores when the pitches allow it, element-wise otherwise.  Every offset is 64-bit: the store is meant to exceed 4 GiB.  No atomics; a pure function
 // of its arguments.
@@ -88,6 +89,58 @@ __global__ void __launch_bounds__(256) bag_batch_shifts_kernel(uint8_t* __restri
     for (; i < n; i += stride) shifts[i] = (uint8_t)(k ? vp_shift(seed, stream, i, k) : 0u);
 }
 
+// ---- amds_bag_plan: randperm(rows)[:bag_size] per patient as a keyed bijection of [0, rows) -------------------------------------------------------------
+// A balanced Feistel network on 2 * half bits (half = ceil(bits / 2), bits = max(2, ceil(log2 rows))), cycle-walked into [0, rows).  Round keys: murmur
+// finalisers of the patient key drop_rowkey(seed, epoch, p) and the round number; round function: fmix32(half ^ round key) & mask.  12 rounds: the few-round
+// networks are visibly unfair on domains of 4 .. 64 values (DESIGN.md section 4.31 has the table); the cost is bag_size hash chains per patient and epoch.
+constexpr int PLAN_ROUNDS = 12;
+
+__device__ __forceinline__ uint32_t plan_feistel(uint32_t x, const uint32_t (&rk)[PLAN_ROUNDS], int half, uint32_t mask) {
+    uint32_t L = x >> half, R = x & mask;
+#pragma unroll
+    for (int r = 0; r < PLAN_ROUNDS; ++r) {
+        const uint32_t t = L ^ (fmix32(R ^ rk[r]) & mask);
+        L = R;
+        R = t;
+    }
+    return (L << half) | R;
+}
+
+// One thread per entry (b, j) of idx.  The walk starts at j < rows and the network is a bijection of [0, domain): the orbit of j returns to [0, rows) after at
+// most domain - rows + 1 applications (the values it visits outside are distinct), which is the loop's trip limit.
+__global__ void __launch_bounds__(256) bag_plan_kernel(const int* __restrict__ offsets, const long* __restrict__ patients, long* __restrict__ idx,
+                                                       long* __restrict__ sizes, long n_entries, int bag_size, uint64_t seed, uint32_t epoch) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (; i < n_entries; i += stride) {
+        const long b = i / bag_size;
+        const int j = (int)(i - b * bag_size);
+        const long p = patients[b];
+        const int o = offsets[p];
+        const int rows = offsets[p + 1] - o;
+        const int m = rows < bag_size ? rows : bag_size;
+        if (j == 0) sizes[b] = m > 0 ? m : 0;
+        long v = -1;
+        if (j < m) {
+            const int bits = rows <= 4 ? 2 : 32 - __builtin_clz((uint32_t)(rows - 1));
+            const int half = (bits + 1) >> 1;
+            const uint32_t mask = (1u << half) - 1u;
+            const uint64_t limit = (1ull << (2 * half)) - (uint64_t)rows + 1ull;
+            const uint32_t key = drop_rowkey(seed, epoch, (uint64_t)p);
+            uint32_t rk[PLAN_ROUNDS];
+#pragma unroll
+            for (int r = 0; r < PLAN_ROUNDS; ++r) rk[r] = fmix32(key ^ ((uint32_t)(r + 1) * 0x9E3779B1u));
+            uint32_t x = (uint32_t)j;
+            for (uint64_t s = 0; s < limit; ++s) {
+                x = plan_feistel(x, rk, half, mask);
+                if (x < (uint32_t)rows) break;
+            }
+            if (x < (uint32_t)rows) v = (long)o + (long)x;
+        }
+        idx[i] = v;
+    }
+}
+
 template <typename TI, typename TO>
 static void launch_gather(bool vec, dim3 grid, hipStream_t st, const void* store, long store_ld, const float* store_coords, const long* idx, void* out, long out_ld,
                           float* coords_out, long n_rows, int cols, uint32_t k, uint64_t seed, uint32_t stream_id) {
@@ -147,5 +200,17 @@ extern "C" int amds_bag_batch_shifts(uint8_t* shifts, int n_bags, int bag_size, 
     const uint32_t k = vp_min_fraction_bits ? (uint32_t)(23 - vp_min_fraction_bits) : 0u;
     hipLaunchKernelGGL(bag_batch_shifts_kernel, dim3((unsigned)min((long)4096, (n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, shifts, n, k, seed, stream_id);
     AMDS_LAUNCH_CHECK("bag_batch_shifts_kernel");
+    return AMDS_OK;
+}
+
+extern "C" int amds_bag_plan(const int* offsets, const long* patients, long* idx, long* sizes, int n, int bag_size, uint64_t seed, uint32_t epoch, void* stream) {
+    AMDS_REQUIRE(offsets && patients && idx && sizes, "amds_bag_plan: null pointer");
+    AMDS_REQUIRE(n >= 0, "amds_bag_plan: n=%d must be >= 0", n);
+    AMDS_REQUIRE(bag_size >= 1, "amds_bag_plan: bag_size=%d must be >= 1", bag_size);
+    if (n == 0) return AMDS_OK;
+    const long n_entries = (long)n * bag_size;
+    hipLaunchKernelGGL(bag_plan_kernel, dim3((unsigned)min((long)4096, (n_entries + 255) / 256)), dim3(256), 0, (hipStream_t)stream, offsets, patients, idx, sizes,
+                       n_entries, bag_size, seed, epoch);
+    AMDS_LAUNCH_CHECK("bag_plan_kernel");
     return AMDS_OK;
 }

@@ -555,6 +555,23 @@ def bag_batch_shifts(n_bags: int, bag_size: int, cols: int, vary_precision_bits:
     return s
 
 
+def bag_plan(offsets: torch.Tensor, patients: torch.Tensor, bag_size: int, seed: int = 0, epoch: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    """An epoch's bag indices in one launch (amds_bag_plan): offsets int32 [P + 1] and patients int64 [n] on the device -> (idx int64 [n, bag_size] of
+    absolute store rows, -1 = padding; sizes int64 [n]): `randperm(rows)[:bag_size]` per patient as a bijection keyed on (seed, epoch, patient)."""
+    _dev(offsets, patients)
+    assert offsets.dim() == 1 and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() >= 1
+    assert patients.dim() == 1 and patients.dtype == torch.int64 and patients.is_contiguous()
+    if bag_size < 1:
+        raise ValueError("bag_size must be >= 1")
+    n = patients.numel()
+    idx = torch.empty(n, int(bag_size), dtype=torch.int64, device=patients.device)
+    sizes = torch.empty(n, dtype=torch.int64, device=patients.device)
+    if n:           # (an empty epoch has no storage to point at, and the call would launch nothing)
+        _lib.check(_lib.lib().amds_bag_plan(_p(offsets), _p(patients), _p(idx), _p(sizes), n, int(bag_size), int(seed) & (2 ** 64 - 1),
+                                            int(epoch) & (2 ** 32 - 1), _stream()), "bag_plan")
+    return idx, sizes
+
+
 def mean_pool(x: torch.Tensor) -> torch.Tensor:
     _dev(x)
     assert x.dim() == 3 and x.is_contiguous()

@@ -2,7 +2,8 @@
 """How far below the MIL `vit` trainer do its feeds sit?  One process, one GPU, a synthetic cohort of feature files:
 
     leg "dataloader0" / "dataloaderN"   bags.tile_bag_dataloader (the reference's feed) with 0 / N workers
-    leg "resident"                      cohort.ResidentCohort.train_batches (features in HBM, one gather launch per batch)
+    leg "resident"                      cohort.ResidentCohort.train_batches (features in HBM, one gather launch per batch); `--sampler device` draws the
+                                        epoch's bags with one amds_bag_plan launch instead of the host's per-patient torch.randperm
     leg "ceiling"                       the trainer alone: the same number of steps on ONE pre-built device batch
 
 Every leg runs `fit`'s training loop (HipMilVitTrainer.step per batch, the loss read on the host after every step) for one epoch and reports epoch bags/s;
@@ -59,6 +60,7 @@ def main() -> int:
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--precision", default="high")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--sampler", choices=("torch", "device"), default="torch", help="who draws the resident leg's bags: the host generator or amds_bag_plan")
     ap.add_argument("--dir", default=None, help="where the synthetic files go (default: a temporary directory, removed afterwards)")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "cohort_feed_bench.json"))
     a = ap.parse_args()
@@ -94,7 +96,7 @@ def main() -> int:
         model = VisionTransformer(dim_output=2, dim_input=a.feats, dim_model=512, n_layers=2, n_heads=8, dim_feedforward=512, dropout=0.25, use_alibi=False)
         trainer = HipMilVitTrainer(model, device=dev, total_steps=100000, sched_interval="step", precision=a.precision)
         cohort = ResidentCohort(pdata, task="classification", categories=cats, device=dev)
-        resident = cohort.train_batches(a.batch, a.bag, shuffle=True)
+        resident = cohort.train_batches(a.batch, a.bag, shuffle=True, sampler=a.sampler, seed=a.seed)
         fixed = next(iter(resident()))
         steps = math.ceil(a.patients / a.batch)
         feeds = {f"dataloader{a.workers}": lambda: loaders[a.workers], "dataloader0": lambda: loaders[0], "resident": resident,
@@ -133,6 +135,15 @@ def main() -> int:
             e.record()
         torch.cuda.synchronize()
         gather_us = statistics.median(s.elapsed_time(e) for s, e in ev) * 1e3
+        # one epoch's index plan on the device: the upload of the patient order + the amds_bag_plan launch, host time until the plan is there
+        plan_dev = []
+        for _ in range(20):
+            order = torch.randperm(len(cohort))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ops.bag_plan(cohort._offsets_dev, order.to(dev), a.bag, a.seed, 0)
+            torch.cuda.synchronize()
+            plan_dev.append((time.perf_counter() - t0) * 1e3)
         item = cohort.feats.element_size()
         gather_bytes = idx.numel() * (a.feats * (item + 4) + 8 + 16)          # a feature row read and written as fp32, its index, its coordinates in and out
         pairs = list(zip(rates["resident"], rates[f"dataloader{a.workers}"]))
@@ -144,7 +155,10 @@ def main() -> int:
             "median_bags_per_s": {k: statistics.median(v) for k, v in rates.items()},
             "resident_load": {"seconds": round(cohort.load_seconds, 3), "GB_per_s": round(cohort.nbytes / cohort.load_seconds / 1e9, 3), "hbm_bytes": cohort.nbytes,
                               "store_dtype": str(cohort.dtype)},
+            "sampler": a.sampler,
+            "epoch_ms": {k: round(1e3 * a.patients / statistics.median(v), 3) for k, v in rates.items()},
             "epoch_plan_host_ms": round(plan_ms, 2),
+            "epoch_plan_device_ms": round(statistics.median(plan_dev), 3),
             "gather": {"us_per_batch_median": round(gather_us, 2), "bytes_per_batch": gather_bytes, "GB_per_s": round(gather_bytes / gather_us / 1e3, 1),
                        "copy_rate_GB_per_s_design_4_17": 6290},
             "condition_resident_ge_dataloader_workers_every_pair": all(x >= y for x, y in pairs),

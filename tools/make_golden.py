@@ -576,6 +576,46 @@ def golden_deploy_tables() -> None:
     print("wrote deploy_tables.json")
 
 
+def golden_crossval_splits() -> None:
+    """The folds of `stamp crossval`: the reference's own `_get_splits` (src/stamp/modeling/crossval.py:373-426, with its `_Split` / `_Splits` models; the
+    module imports lightning through train.py: only these definitions are executed) with the splitter `categorical_crossval_` picks (:92-96), for 23
+    patients and n_splits 3 and 5: classification with 3 unbalanced classes, survival with missing statuses, regression.  Stored: the ground truths and,
+    per case, the folds as sorted lists of patient ids (the `splits.json` schema)."""
+    import json
+    from collections.abc import Mapping, Sequence
+    from dataclasses import dataclass
+    from typing import Any, cast
+
+    from pydantic import BaseModel
+    from sklearn.model_selection import KFold, StratifiedKFold
+
+    mod = types.ModuleType("_ref_crossval_defs")
+    sys.modules[mod.__name__] = mod
+    mod.__dict__.update(np=np, BaseModel=BaseModel, Mapping=Mapping, Sequence=Sequence, Any=Any, cast=cast, PatientId=str, PatientData=typing.Generic)
+    exec_defs(REF / "modeling" / "crossval.py", {"_Split", "_Splits", "_get_splits"}, mod.__dict__)
+
+    @dataclass
+    class PD:
+        ground_truth: Any
+
+    ids = [f"pat-{i:02d}" for i in range(23)]
+    labels = ["wt"] * 13 + ["mut"] * 6 + ["amp"] * 4
+    order = np.random.default_rng(3).permutation(23)
+    gts = {"classification": [labels[i] for i in order],
+           "survival": [(float(30 + 17 * i % 400), None if i % 7 == 3 else int(i % 3 != 0)) for i in range(23)],
+           "regression": [round(0.5 * i - 3.0, 2) for i in range(23)]}
+    out: dict = {"patients": ids, "ground_truths": {k: [list(g) if isinstance(g, tuple) else g for g in v] for k, v in gts.items()}, "cases": []}
+    for task, v in gts.items():
+        for n_splits in (3, 5):
+            res = mod._get_splits(patient_to_data={p: PD(g) for p, g in zip(ids, v)}, n_splits=n_splits, spliter=KFold if task == "regression" else StratifiedKFold,
+                                  task=task)
+            out["cases"].append({"task": task, "n_splits": n_splits,
+                                 "splits": [{"train_patients": sorted(str(p) for p in s.train_patients), "test_patients": sorted(str(p) for p in s.test_patients)}
+                                            for s in res.splits]})
+    (OUT / "crossval_splits.json").write_text(json.dumps(out, indent=1) + "\n")
+    print("wrote crossval_splits.json:", len(out["cases"]), "cases")
+
+
 def golden_get_coords() -> None:
     """The reference's own feature-file coordinate loader `get_coords` / `get_stride` / `CoordsInfo` (src/stamp/modeling/data.py:726-808, 1150-1161; the module
     imports h5py: a stand-in with just `Dataset` / `File`-like objects is handed to the functions), on the formats it distinguishes: STAMP v2, the current
@@ -1380,6 +1420,7 @@ def main() -> None:
     golden_plip()
     golden_dinov2_hf()
     golden_deploy_tables()
+    golden_crossval_splits()
     golden_get_coords()
     golden_mil_vit()
     golden_mil_vit_train()
