@@ -1688,6 +1688,47 @@ int amds_abmil_heatmap(const amds_abmil_cfg* cfg_host, const amds_abmil_weights*
 /* ws: contents on entry are ignored (the call initialises every byte it reads);
  *     nothing outside [ws, ws + amds_abmil_heatmap_workspace_bytes) is written. */
 
+/* ------------------------------------------------------------------------------------------------
+ * MLP / Linear heads on slide- and patient-level feature vectors (reference src/stamp/modeling/models/mlp.py:6-44 `MLP`, :47-62 `Linear`; trained by the
+ * `LitSlide*` / `LitPatient*` wrappers, src/stamp/modeling/models/__init__.py:316-385, 516-588, 803-855): eval forward, training forward and backward, ONE call
+ * each (csrc/mlp.hip).  The chain is (Linear -> ReLU -> Dropout(p)) x (num_layers - 1) -> Linear (mlp.py:24-32); num_layers = 1 is the `Linear` head.
+ *   a_0 = x      a_i = m_i o relu(w[i-1] a_(i-1) + b[i-1])   (hidden layer i - 1, keep mask m scaled by amds_dropout_keep_scale(p))      logits = w[L-1] a_(L-1) + b[L-1]
+ * x [rows][dim_input], AMDS_F32 or AMDS_F16 (converted exactly, as `feats.float()`), row pitch ld_x >= dim_input elements.  Weights fp32 in torch's [out][in]
+ * layout, read in place; no alignment beyond 4 bytes is asked of a weight or gradient tensor (views of one flat buffer are fine).
+ * Precision: every product is exact fp32 on v_mfma_f32_16x16x4_f32 at every amds_set_matmul_precision setting, forward and backward.  No floating-point atomics:
+ * the forward cuts K into slices of 256 columns (a rule of K alone) and adds the slices in order, whether they ran as separate workgroups (rows <= 64) or in one
+ * wave; every other sum is an in-order loop over four interleaved accumulators.  A call is reproducible bit for bit, and a logits row depends on that row's
+ * features and the weights only -- not on `rows`, the row's position or the other rows (eval forward, and training forward with p = 0).
+ * Dropout: the counter-based masks of amds_dropout_mask with the keying of the module path: stream id = index of the hidden layer (0, 1, ...), flat element
+ * index row * dim_hidden + col over the call's rows, i.e. amds_dropout_mask(rows * dim_hidden, p, seed, layer) reshaped [rows][dim_hidden].  The backward draws
+ * the masks again; the saved block holds the hidden activations a_i only (dim_hidden * 4 bytes per row and hidden layer, each region rounded up to 256 bytes).
+ * Limits (AMDS_ERR_INVALID before any launch, and 0 from the *_bytes entries): 1 <= num_layers <= amds_mlp_max_layers() = 8; every width in [1, 65536];
+ * 0 <= rows <= 2^22; ld_x >= dim_input.  rows == 0 succeeds without a launch (the backward then zeroes the gradients).  Saved block and workspaces 256-byte
+ * aligned; too small is AMDS_ERR_WORKSPACE before anything is launched.  Launches only, on `stream`. */
+typedef struct { int dim_input, dim_hidden, dim_output, num_layers; } amds_mlp_cfg;
+typedef struct { const float* w[8]; const float* b[8]; } amds_mlp_weights;      /* layer i: w[i] [out_i][in_i], b[i] [out_i]; entries >= num_layers ignored */
+typedef struct { float* w[8]; float* b[8]; } amds_mlp_grads;                    /* shaped like the weights; overwritten */
+int amds_mlp_max_layers(void);
+size_t amds_mlp_workspace_bytes(const amds_mlp_cfg* cfg_host, long rows);
+size_t amds_mlp_train_saved_bytes(const amds_mlp_cfg* cfg_host, long rows);
+size_t amds_mlp_train_workspace_bytes(const amds_mlp_cfg* cfg_host, long rows);      /* serves the training forward and the backward */
+/* logits fp32 [rows][dim_output] (mlp.py:34-44 in eval mode) */
+int amds_mlp_forward(const amds_mlp_cfg* cfg_host, const amds_mlp_weights* w_host, const void* x, int x_dtype, long ld_x, long rows, float* logits, void* ws,
+                     size_t ws_bytes, void* stream);
+/* ws: contents on entry are ignored (the call initialises every byte it reads);
+ *     nothing outside [ws, ws + amds_mlp_workspace_bytes) is written. */
+/* The same with dropout live (mlp.py:24-32 in train mode) and the hidden activations kept in `saved` */
+int amds_mlp_train_forward(const amds_mlp_cfg* cfg_host, const amds_mlp_weights* w_host, const void* x, int x_dtype, long ld_x, long rows, float p, uint64_t seed,
+                           float* logits, void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, void* stream);
+/* The backward of that forward (what autograd derives in `LitSlideClassifier._step`, src/stamp/modeling/models/__init__.py:324-351): the same x, p and seed;
+ * dlogits fp32 [rows][dim_output].  grads_host: every weight and bias gradient is written (NULL: the input gradient only).  need_dx != 0: dx fp32
+ * [rows][dim_input], the gradient w.r.t. x, is written too; otherwise that product is not launched and dx may be NULL.  One of the two must be asked for. */
+int amds_mlp_train_backward(const amds_mlp_cfg* cfg_host, const amds_mlp_weights* w_host, const void* x, int x_dtype, long ld_x, long rows, float p, uint64_t seed,
+                            const float* dlogits, const void* saved, size_t saved_bytes, const amds_mlp_grads* grads_host, int need_dx, float* dx, void* ws,
+                            size_t ws_bytes, void* stream);
+/* saved, ws: contents on entry are ignored (the calls initialise every byte they read);
+ *     nothing outside [saved, saved + amds_mlp_train_saved_bytes) and [ws, ws + amds_mlp_train_workspace_bytes) is written. */
+
 /* Backward pieces of the TransMIL head (training: the reference differentiates trans_mil.py with autograd inside
  * LitTileClassifier._step, src/stamp/modeling/models/__init__.py:239-279); fp32 like the forward.  The matrix products of the
  * backward are amds_bgemm_f32 calls.

@@ -209,6 +209,21 @@ class AbmilGrads(C.Structure):
     _fields_ = AbmilWeights._fields_
 
 
+MLP_MAX_LAYERS = 8          # include/amdstamp.h: amds_mlp_max_layers()
+
+
+class MlpCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("dim_input", "dim_hidden", "dim_output", "num_layers")]
+
+
+class MlpWeights(C.Structure):
+    _fields_ = [("w", C.c_void_p * MLP_MAX_LAYERS), ("b", C.c_void_p * MLP_MAX_LAYERS)]
+
+
+class MlpGrads(C.Structure):
+    _fields_ = MlpWeights._fields_
+
+
 class AbmilDropout(C.Structure):
     _fields_ = [("p_fc", C.c_float), ("p_gate", C.c_float), ("seed", C.c_uint64)]
 
@@ -467,6 +482,13 @@ PROTOTYPES = {
     "amds_abmil_heatmap": (_i, [_vp, _vp, _vp, _i, _vp, _i, _l, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "amds_abmil_train_forward": (_i, [_vp, _vp, _vp, _i, _vp, _i, _l, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "amds_abmil_train_backward": (_i, [_vp, _vp, _vp, _i, _vp, _i, _l, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
+    "amds_mlp_max_layers": (_i, []),
+    "amds_mlp_workspace_bytes": (_sz, [_vp, _l]),
+    "amds_mlp_train_saved_bytes": (_sz, [_vp, _l]),
+    "amds_mlp_train_workspace_bytes": (_sz, [_vp, _l]),
+    "amds_mlp_forward": (_i, [_vp, _vp, _vp, _i, _l, _l, _vp, _vp, _sz, _vp]),
+    "amds_mlp_train_forward": (_i, [_vp, _vp, _vp, _i, _l, _l, _f, _u64, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "amds_mlp_train_backward": (_i, [_vp, _vp, _vp, _i, _l, _l, _f, _u64, _vp, _vp, _sz, _vp, _i, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

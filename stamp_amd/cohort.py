@@ -128,7 +128,8 @@ class ResidentCohort:
             for f in fs:
                 d, a = h5io.read_file(f)
                 if h5io.feature_type(a) in ("slide", "patient"):
-                    raise ValueError(f"{f}: {h5io.feature_type(a)}-level features; a resident cohort (and crossval on it) takes tile-level feature files")
+                    raise ValueError(f"{f}: {h5io.feature_type(a)}-level features; a resident cohort takes tile-level feature files "
+                                     "(one vector per slide or patient goes into cohort.ResidentFeatureTable, which crossval builds for such files)")
                 x = np.asarray(d["feats"] if "feats" in d else d["patch_embeddings"])
                 c = np.asarray(h5io.get_coords(d, a).coords_um)
                 if o + x.shape[0] > n or x.shape[1] != Fd or c.shape != (x.shape[0], 2):
@@ -298,4 +299,185 @@ class CohortView:
         return self.cohort.ragged_group(p0, p0 + e - a)
 
 
-__all__ = ["ResidentCohort", "CohortView", "plan_indices", "MAX_ROWS", "SAMPLERS"]
+# ---- slide- / patient-level feature vectors: one row per entry ---------------------------------------------------------------------------------------
+def parse_survival_status(value) -> int:
+    """The reference's `_parse_survival_status` (data.py:1164-1201): known spellings first, then any number (> 0 is an event; "nan" compares false: 0)."""
+    s = str(value).strip().lower()
+    if s in {"1", "event", "dead", "deceased", "yes", "y", "true"}:
+        return 1
+    if s in {"0", "alive", "censored", "no", "false"}:
+        return 0
+    try:
+        return 1 if float(s) > 0 else 0
+    except ValueError:
+        raise ValueError(f"Unrecognized survival status: {value!r} (expected dead / alive, event / censored, yes / no, true / false or a number)") from None
+
+
+def feature_table_labels(patient_data: Sequence[PatientData], task: str, categories: Sequence[str] | None = None) -> tuple[torch.Tensor, list]:
+    """-> (labels, categories) exactly as the slide / patient branch of the reference's `create_dataloader` builds them (data.py:359-406): classification a float
+    one-hot [N, C] in the order of `categories` (default: the sorted unique labels); regression float [N, 1]; survival float [N, 2] = (time, event), the time
+    NaN when missing or unparsable, the event through `parse_survival_status` (a ground truth that is no (time, event) pair is a time with an unknown status,
+    which parses as 0).  Multi-target (dict) ground truths are refused like there."""
+    gts = [p.ground_truth for p in patient_data]
+    if any(isinstance(g, dict) for g in gts):
+        raise ValueError("multi-target ground truths are not supported on slide- / patient-level features; provide a single target per entry")
+    if task == "classification":
+        raw = np.array(gts)
+        cats = list(categories) if categories else [c.item() for c in np.unique(raw)]
+        return torch.tensor(raw.reshape(-1, 1) == np.array(cats, dtype=object).reshape(1, -1), dtype=torch.float32).reshape(len(gts), len(cats)), cats
+    if task == "regression":
+        if any(g is None for g in gts):
+            raise ValueError("regression on a feature table needs a numeric target for every entry")
+        return torch.tensor([float(g) for g in gts], dtype=torch.float32).reshape(-1, 1), []
+    if task == "survival":
+        times, events = [], []
+        for g in gts:
+            if isinstance(g, (tuple, list)) and len(g) == 2:
+                t, e = g
+            elif g is None:
+                t, e = None, None
+            else:
+                t, e = str(g), "nan"
+            if t is None:
+                times.append(np.nan)
+            elif isinstance(t, str):
+                try:
+                    times.append(np.nan if t.lower() == "nan" else float(t))
+                except ValueError:
+                    times.append(np.nan)
+            else:
+                times.append(float(t))
+            events.append(parse_survival_status(e))
+        return torch.tensor(np.column_stack([times, events]).reshape(-1, 2), dtype=torch.float32), []
+    raise ValueError(f"Unsupported task: {task}")
+
+
+def read_feature_vector(path) -> np.ndarray:
+    """One slide- / patient-level file -> its vector [F], by the rule of the reference's `PatientFeatureDataset.__getitem__` (data.py:690-723): `feats` of shape
+    [F] or [1, F]; a tile-level file (`h5io.feature_type`) is refused."""
+    d, a = h5io.read_file(path)
+    if h5io.feature_type(a) == "tile":
+        raise ValueError(f"{path}: tile-level features; a feature table takes slide- or patient-level files (tile bags go into a ResidentCohort)")
+    if "feats" not in d:
+        raise RuntimeError(f"{path}: no 'feats' dataset")
+    x = np.asarray(d["feats"])
+    if x.ndim == 2 and x.shape[0] == 1:
+        x = x[0]
+    elif x.ndim != 1:
+        raise RuntimeError(f"Expected single feature vector (shape [F] or [1, F]), got {tuple(x.shape)} in {path}. Check that the features are patient-level.")
+    return x
+
+
+class ResidentFeatureTable:
+    """One feature vector per entry (a slide or a patient), resident in device memory: the feed of `mlp_train.HipMlpTrainer` under `mil_train.fit` and
+    `crossval.crossval`.  The reference's loader (data.py:355-419) opens every entry's file again for every item of every epoch; the whole table of a cohort
+    is a few megabytes (1 000 entries x 2 560 fp16 features = 5 MB), so every file is read ONCE through `h5io.read_file`.
+
+        feats [N, F]   fp16 when every file is fp16, else fp32        targets [N, C] / [N, 1] / [N, 2]  (`feature_table_labels`)
+
+    An entry's file is the FIRST of its `feature_files` (`next(iter(p.feature_files))`, data.py:357).  Batches follow `ResidentCohort`'s protocol; `view(entries)`
+    is a `FeatureTableView` over the same tensors.  No spilling: the size is checked before any allocation.  One device."""
+
+    def __init__(self, patient_data: Sequence[PatientData], *, task: str, categories: Sequence[str] | None = None, device="cuda", max_bytes: int | None = None) -> None:
+        self.files = [next(iter(p.feature_files)) for p in patient_data]
+        self.targets, self.categories = feature_table_labels(patient_data, task, categories)
+        self.task = task
+        self.device = torch.device(device)
+        rows = [read_feature_vector(f) for f in self.files]
+        widths = {int(r.shape[0]) for r in rows}
+        if len(widths) > 1:
+            raise ValueError(f"the table's files must share one feature width, got {sorted(widths)}")
+        self.n_feats = widths.pop() if widths else 0
+        self.dtype = torch.float16 if rows and all(r.dtype == np.float16 for r in rows) else torch.float32
+        self.nbytes = len(rows) * self.n_feats * (2 if self.dtype == torch.float16 else 4)
+        if self.device.type == "cuda":
+            _check_size(self.nbytes, max_bytes, self.device)
+        elif max_bytes is not None and self.nbytes > max_bytes:
+            raise ValueError(f"the table needs {self.nbytes} bytes, max_bytes allows {int(max_bytes)} (there is no spilling)")
+        host = torch.empty(len(rows), self.n_feats, dtype=self.dtype)
+        for i, r in enumerate(rows):
+            host[i].copy_(torch.from_numpy(np.ascontiguousarray(r)))          # (the `.float()` of the reference's step when the store is fp32)
+        self.feats = host.to(self.device)
+        self._targets_dev = self.targets.to(self.device)
+
+    def __len__(self) -> int:
+        return len(self.files)
+
+    def view(self, entries: Iterable[int]) -> "FeatureTableView":
+        """The entries `entries` (store indices, in that order) as a `FeatureTableView`: the folds of a cross-validation are views of ONE table."""
+        return FeatureTableView(self, entries)
+
+    def _all(self) -> "FeatureTableView":
+        return FeatureTableView(self, range(len(self)))
+
+    def train_batches(self, batch_size: int, shuffle: bool = True, generator: torch.Generator | None = None, drop_last: bool = False):
+        """`FeatureTableView.train_batches` of all entries."""
+        return self._all().train_batches(batch_size, shuffle, generator, drop_last)
+
+    def valid_batches(self):
+        """`FeatureTableView.valid_batches` of all entries."""
+        return self._all().valid_batches()
+
+
+class FeatureTableView:
+    """A list of store entries over a `ResidentFeatureTable`'s own tensors: nothing is copied."""
+
+    def __init__(self, table: ResidentFeatureTable, entries: Iterable[int]) -> None:
+        self.table = table
+        self.entries = [int(e) for e in entries]
+        bad = [e for e in self.entries if not 0 <= e < len(table)]
+        if bad:
+            raise ValueError(f"entries {bad[:8]} outside 0..{len(table)}")
+        self._entries_t = torch.tensor(self.entries, dtype=torch.int64)
+
+    def __len__(self) -> int:
+        return len(self.entries)
+
+    def epoch_plan(self, batch_size: int, shuffle: bool = True, generator: torch.Generator | None = None, drop_last: bool = False) -> list[torch.Tensor]:
+        """The batches of one epoch as int64 tensors of STORE rows (host): ONE `torch.randperm(len(view))` from `generator` when shuffling (the cohort's rule 1),
+        then consecutive groups of `batch_size`; the shorter tail batch is kept unless `drop_last`."""
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        N = len(self)
+        order = torch.randperm(N, generator=generator) if shuffle else torch.arange(N)
+        if drop_last:
+            order = order[:N - N % batch_size]
+        rows = self._entries_t[order]
+        return [rows[a:a + batch_size] for a in range(0, rows.numel(), batch_size)]
+
+    def _epoch(self, batch_size, shuffle, generator, drop_last):
+        from . import ops
+        t = self.table
+        if t.device.type != "cuda":
+            raise RuntimeError("a feature table's batches are gathered on the GPU (no CPU fallback)")
+        plan = self.epoch_plan(batch_size, shuffle, generator, drop_last)
+        if not plan:
+            return
+        rows = torch.cat(plan).to(t.device)          # the epoch's plan: uploaded once
+        a = 0
+        for b in plan:
+            idx = rows[a:a + b.numel()]
+            a += b.numel()
+            # amds_gather_rows: the bits of `feats[idx].float()`
+            yield ops.gather_rows(t.feats, idx, idx.numel(), torch.float32), None, None, t._targets_dev[idx]
+
+    def train_batches(self, batch_size: int, shuffle: bool = True, generator: torch.Generator | None = None, drop_last: bool = False):
+        """-> the callable `mil_train.fit` takes: per epoch an iterable of (feats fp32 [B, F], None, None, targets [B, D]) on the device, one amds_gather_rows
+        launch per batch."""
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        return lambda: self._epoch(batch_size, shuffle, generator, drop_last)
+
+    def _valid(self):
+        t = self.table
+        for e in self.entries:
+            yield t.feats[e:e + 1], None, None, t._targets_dev[e:e + 1]
+
+    def valid_batches(self):
+        """-> the callable `fit` takes for validation: one entry per batch in the view's order ([1, F] views of the store in its own precision, no copy): the
+        reference's batch-1 validation loader (src/stamp/modeling/train.py:467-477)."""
+        return lambda: self._valid()
+
+
+__all__ = ["ResidentCohort", "CohortView", "plan_indices", "MAX_ROWS", "SAMPLERS", "ResidentFeatureTable", "FeatureTableView", "feature_table_labels",
+           "parse_survival_status", "read_feature_vector"]

@@ -16,7 +16,11 @@ the folds are `CohortView`s of it: nothing is copied or read again.  With `sampl
 `amds_bag_plan` launch; `sampler="torch"` keeps the host draws, and then a fold's batches are bit-identical to those of a separate cohort of its patients.
 `split-{i}/model.pt` is a plain `torch.save` file (`load_fold_model` reads it), NOT a Lightning checkpoint: `deploy.model_from_checkpoint` does not take it.
 
-Out of scope, each refused with a ValueError: multi-target ground truths and the barspoon trainer (it has its own `fit`), slide- / patient-level feature files,
+Slide- / patient-level feature files (one vector per entry; the whole cohort must be of ONE feature type) take the same flow on a
+`cohort.ResidentFeatureTable` ordered by test fold, with `mlp_train.HipMlpTrainer` over `mil.MLP` / `mil.Linear`: the reference's `feature_type in {"slide",
+"patient"}` feed (src/stamp/modeling/data.py:355-419).  `bag_size` and `sampler` do not apply there; `vary_precision_bits` is refused.
+
+Out of scope, each refused with a ValueError: multi-target ground truths and the barspoon trainer (it has its own `fit`), cohorts of mixed feature types,
 and the CLI / config layer.  `sklearn` is needed by `get_splits` alone: `crossval(splits=...)` runs without it."""
 from __future__ import annotations
 
@@ -31,7 +35,8 @@ import torch
 
 from . import bags as B
 from . import deploy, losses
-from .cohort import ResidentCohort
+from . import h5io
+from .cohort import ResidentCohort, ResidentFeatureTable
 
 _log = logging.getLogger("stamp_amd")
 TASKS = ("classification", "regression", "survival")
@@ -99,8 +104,14 @@ def check_splits(splits: Sequence[Split], patient_ids) -> set:
 # ---- per-fold files ----------------------------------------------------------------------------------------------------------------------------------
 def head_constructor_args(model: torch.nn.Module) -> dict:
     """The keyword arguments that rebuild a MIL head `fit` can train."""
+    from . import mlp_core
     from .abmil import GatedAttentionMIL
-    from .mil import TransMIL, VisionTransformer
+    from .mil import MLP, Linear, TransMIL, VisionTransformer
+    if isinstance(model, MLP):
+        fi, hid, out, layers = mlp_core.model_dims(model)
+        return dict(dim_input=fi, dim_hidden=hid, dim_output=out, num_layers=layers, dropout=model.dropout_p)
+    if isinstance(model, Linear):
+        return dict(dim_input=model.fc.in_features, dim_output=model.fc.out_features)
     if isinstance(model, VisionTransformer):
         d = model.dims
         return dict(dim_output=d.C, dim_input=d.F, dim_model=d.D, n_layers=d.L, n_heads=d.H, dim_feedforward=d.FF, dropout=model.dropout, use_alibi=model.use_alibi)
@@ -109,7 +120,7 @@ def head_constructor_args(model: torch.nn.Module) -> dict:
     if isinstance(model, GatedAttentionMIL):
         fi, hid, att, out = model.dims
         return dict(dim_input=fi, dim_hidden=hid, dim_attention=att, dim_output=out, dropout=model.dropout)
-    raise ValueError(f"{type(model).__name__} is not a head `mil_train.fit` trains (VisionTransformer, TransMIL, GatedAttentionMIL)")
+    raise ValueError(f"{type(model).__name__} is not a head `mil_train.fit` trains (VisionTransformer, TransMIL, GatedAttentionMIL, MLP, Linear)")
 
 
 def save_fold_model(path, trainer, *, task: str, categories: Sequence) -> None:
@@ -123,9 +134,9 @@ def save_fold_model(path, trainer, *, task: str, categories: Sequence) -> None:
 def load_fold_model(path) -> tuple[torch.nn.Module, dict]:
     """-> (the head of a `split-{i}/model.pt` in eval mode, the file's dict)."""
     from .abmil import GatedAttentionMIL
-    from .mil import TransMIL, VisionTransformer
+    from .mil import MLP, Linear, TransMIL, VisionTransformer
     doc = torch.load(path, map_location="cpu", weights_only=True)
-    heads = {c.__name__: c for c in (VisionTransformer, TransMIL, GatedAttentionMIL)}
+    heads = {c.__name__: c for c in (VisionTransformer, TransMIL, GatedAttentionMIL, MLP, Linear)}
     if doc.get("format") != "stamp_amd.crossval/1" or doc.get("head") not in heads:
         raise ValueError(f"{path}: not a model file of stamp_amd.crossval")
     model = heads[doc["head"]](**doc["head_kwargs"])
@@ -137,7 +148,7 @@ def load_fold_model(path) -> tuple[torch.nn.Module, dict]:
 @dataclass
 class CrossvalResult:
     splits: list          # the folds used, `splits.json`'s content
-    cohort: Any           # the ONE ResidentCohort (None when every fold was already done)
+    cohort: Any           # the ONE ResidentCohort / ResidentFeatureTable (None when every fold was already done)
     histories: list       # per fold: `fit`'s history (a skipped fold: its history.json, or None)
     predictions: list     # per fold: patient id -> prediction on the CPU (a skipped fold: None)
     frames: list          # per fold: the `patient-preds.csv` table
@@ -153,6 +164,19 @@ def _frame(task, predictions, gts, categories, patient_label, ground_truth_label
     return deploy.to_survival_prediction_df(patient_to_ground_truth=gts, predictions=predictions, patient_label=patient_label, cut_off=cut_off)
 
 
+def cohort_feature_type(patient_data) -> str:
+    """"tile", "slide" or "patient": the feature type of every file of the cohort (`h5io.feature_type`); a cohort of mixed types is a ValueError."""
+    kinds: dict = {}
+    for p in patient_data:
+        for f in p.feature_files:
+            kinds.setdefault(h5io.file_feature_type(f), f)
+    if not kinds:
+        return "tile"
+    if len(kinds) != 1:
+        raise ValueError("the cohort's feature files must be of one feature type, got " + ", ".join(f"{k} ({v})" for k, v in sorted(kinds.items(), key=lambda kv: str(kv[0]))))
+    return next(iter(kinds))
+
+
 def crossval(patient_to_data: Mapping[str, B.PatientData], *, task: str, make_trainer: Callable, n_splits: int = 5, splits: Sequence[Split] | None = None,
              output_dir=None, categories: Sequence[str] | None = None, bag_size: int = 512, batch_size: int = 64, max_epochs: int = 64, patience: int = 16,
              sampler: str = "device", seed: int = 0, generator: torch.Generator | None = None, vary_precision_bits: int | None = None,
@@ -162,7 +186,9 @@ def crossval(patient_to_data: Mapping[str, B.PatientData], *, task: str, make_tr
     class_weights=) -> any trainer `mil_train.fit` drives (HipMilVitTrainer, HipTransMilTrainer, HipAbmilTrainer).  splits: the folds to use (else
     `output_dir/splits.json` if it exists, else `get_splits`).  fit_kwargs go to `fit`: survival runs pass monitor="val_cindex"; `loss_fn` defaults to the
     task's (cross-entropy / `losses.l1_loss` / `losses.cox_survival_loss`).  The device sampler of fold i is keyed with `seed + i`, so a patient does not
-    meet the same bags in two folds.  Module docstring for the flow and what it writes under `output_dir`."""
+    meet the same bags in two folds.  Slide- / patient-level files (one feature type for the whole cohort, else ValueError): ONE `ResidentFeatureTable`
+    instead, `make_trainer` returning a `HipMlpTrainer`; `bag_size`, `sampler`, `seed` and `out_dtype` do not apply, `vary_precision_bits` is refused.  Module
+    docstring for the flow and what it writes under `output_dir`."""
     from .mil_train import fit
     if task not in TASKS:
         raise ValueError(f"task must be one of {TASKS}, got {task!r}")
@@ -182,7 +208,11 @@ def crossval(patient_to_data: Mapping[str, B.PatientData], *, task: str, make_tr
         splits = read_splits(out / "splits.json")
     else:
         splits = get_splits(ids, [gts[p] for p in ids], n_splits=n_splits, task=task)
-    check_splits(splits, ids)
+    left_out = check_splits(splits, ids)
+    feature_type = cohort_feature_type(d for p, d in data.items() if p not in left_out)          # (file attributes only: no dataset is read)
+    vectors = feature_type in ("slide", "patient")
+    if vectors and vary_precision_bits is not None:
+        raise ValueError(f"vary_precision_bits does not apply to {feature_type}-level features (the reference's transform is part of the tile feed)")
     if out is not None and not (out / "splits.json").exists():
         write_splits(out / "splits.json", splits)
     if task == "classification":
@@ -219,9 +249,12 @@ def crossval(patient_to_data: Mapping[str, B.PatientData], *, task: str, make_tr
             if p in members and p not in position:
                 position[p] = len(position)
     store_ids = sorted(position, key=position.__getitem__)
-    cohort = ResidentCohort([data[p] for p in store_ids], task=task, categories=categories or None, device=device)
-    if cohort.multi_target:
-        raise ValueError("multi-target ground truths are out of scope")
+    if vectors:
+        cohort = ResidentFeatureTable([data[p] for p in store_ids], task=task, categories=categories or None, device=device)
+    else:
+        cohort = ResidentCohort([data[p] for p in store_ids], task=task, categories=categories or None, device=device)
+        if cohort.multi_target:
+            raise ValueError("multi-target ground truths are out of scope")
     res.cohort = cohort
     default_loss = {"classification": None, "regression": losses.l1_loss, "survival": losses.cox_survival_loss}[task]
     fit_kwargs.setdefault("loss_fn", default_loss)
@@ -231,12 +264,15 @@ def crossval(patient_to_data: Mapping[str, B.PatientData], *, task: str, make_tr
         train_set, test_set = set(s["train_patients"]), set(s["test_patients"])
         train_ids, test_ids = [p for p in ids if p in train_set], [p for p in ids if p in test_set]
         train_view, test_view = cohort.view([position[p] for p in train_ids]), cohort.view([position[p] for p in test_ids])
-        weights = B.class_weights(cohort.targets[train_view.patients], categories) if task == "classification" else None
+        weights = B.class_weights(cohort.targets[train_view.entries if vectors else train_view.patients], categories) if task == "classification" else None
         trainer = make_trainer(fold=i, dim_feats=cohort.n_feats, categories=list(categories), class_weights=weights)
         if type(trainer).__name__ == "HipBarspoonTrainer" or not all(hasattr(trainer, a) for a in ("step", "predict", "epoch_end", "P", "model")):
             raise ValueError(f"make_trainer returned {type(trainer).__name__}: crossval drives the trainers of `mil_train.fit` (the barspoon trainer has its own fit)")
-        feed = train_view.train_batches(batch_size, bag_size, shuffle=True, generator=generator, out_dtype=out_dtype, vary_precision_bits=vary_precision_bits,
-                                        sampler=sampler, seed=int(seed) + i)
+        if vectors:
+            feed = train_view.train_batches(batch_size, shuffle=True, generator=generator)
+        else:
+            feed = train_view.train_batches(batch_size, bag_size, shuffle=True, generator=generator, out_dtype=out_dtype, vary_precision_bits=vary_precision_bits,
+                                            sampler=sampler, seed=int(seed) + i)
         hist = fit(trainer, feed, test_view.valid_batches(), max_epochs=max_epochs, patience=patience, class_weights=weights,
                    valid_bags_per_call=valid_bags_per_call, **fit_kwargs)
         preds = deploy.predict_(trainer.model, test_view.valid_batches()(), test_ids, task=task, device=device, bags_per_call=predict_bags_per_call)
@@ -251,5 +287,5 @@ def crossval(patient_to_data: Mapping[str, B.PatientData], *, task: str, make_tr
     return res
 
 
-__all__ = ["get_splits", "write_splits", "read_splits", "check_splits", "crossval", "CrossvalResult", "save_fold_model", "load_fold_model", "head_constructor_args",
+__all__ = ["cohort_feature_type", "get_splits", "write_splits", "read_splits", "check_splits", "crossval", "CrossvalResult", "save_fold_model", "load_fold_model", "head_constructor_args",
            "TASKS"]

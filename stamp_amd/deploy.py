@@ -99,6 +99,33 @@ def _ragged_outputs(model, batches, device, bags_per_call: int, max_rows_per_cal
     return outs
 
 
+def _stacked_outputs(model, batches, device, rows_per_call: int) -> list[torch.Tensor]:
+    """The per-batch outputs of the loop in `predict_` for an `MLP` / `Linear` head on slide- / patient-level vectors: consecutive [1, F] batches of one
+    dtype are stacked, `rows_per_call` at a time, into ONE forward.  A row of these heads' forward is a sum over that row's own features in an order the
+    feature width alone fixes, so each row is the one-row forward's, bit for bit.  Any other batch ([B, T, F] bags, several rows) keeps its own forward."""
+    outs: list = []
+    pend: list = []
+
+    def flush():
+        if pend:
+            out = model(torch.cat(pend, dim=0), coords=None, mask=None)
+            outs.extend(out.float().cpu().split(1, dim=0))
+            pend.clear()
+
+    for bags, *_ in batches:
+        if bags.dim() == 2 and bags.shape[0] == 1:
+            if pend and pend[0].dtype != bags.dtype:
+                flush()
+            pend.append(bags.to(device))
+            if len(pend) >= rows_per_call:
+                flush()
+            continue
+        flush()
+        outs.append(model(bags.to(device), coords=None, mask=None).float().cpu())
+    flush()
+    return outs
+
+
 def _barspoon_outputs(model, batches, device, bags_per_call: int, max_rows_per_call: int) -> list[dict]:
     """The `{target: logits}` of the barspoon loop in `predict_`, in batch order, with consecutive one-bag batches grouped into ragged calls
     (`EncDecTransformer.forward_ragged`, which sends a bag too long to share alone): one dict of [n, n_out] rows per group, each row the one its own
@@ -137,7 +164,8 @@ def predict_(model: torch.nn.Module, batches: Iterable, patient_ids: Sequence[st
     bags_per_call > 1 (`vit`, TransMIL and barspoon heads; any other module ignores it): consecutive bags share ONE ragged forward, at most
     `bags_per_call` bags and `max_rows_per_call` token rows per call (TransMIL: padded token rows; barspoon: tile rows), a bag too long to share runs alone;
     every prediction is the one of the one-bag loop (`vit` and barspoon: bit for bit; TransMIL: to fp32 rounding, every bag with its own grid, padding and
-    pseudo-inverse scale as at batch 1)."""
+    pseudo-inverse scale as at batch 1).  An `MLP` / `Linear` head on slide- / patient-level vectors: `bags_per_call` consecutive [1, F] batches are stacked
+    into one forward, every prediction the one-row loop's bit for bit."""
     if bags_per_call < 1 or max_rows_per_call < 1:
         raise ValueError("bags_per_call and max_rows_per_call must be >= 1")
     if task not in ("classification", "regression", "survival"):
@@ -164,10 +192,12 @@ def predict_(model: torch.nn.Module, batches: Iterable, patient_ids: Sequence[st
         n = next(iter(cat.values())).shape[0]
         return {pid: {t: cat[t][i] for t in cat} for i, pid in enumerate(list(patient_ids)[:n])}
     from .abmil import GatedAttentionMIL
-    from .mil import TransMIL, VisionTransformer
+    from .mil import MLP, Linear, TransMIL, VisionTransformer
 
     if bags_per_call > 1 and isinstance(model, (VisionTransformer, TransMIL, GatedAttentionMIL)):
         outs = _ragged_outputs(model, batches, device, bags_per_call, max_rows_per_call)
+    elif bags_per_call > 1 and isinstance(model, (MLP, Linear)):
+        outs = _stacked_outputs(model, batches, device, min(bags_per_call, max_rows_per_call))
     else:
         outs = []
         for bags, coords, *_ in batches:

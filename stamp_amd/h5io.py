@@ -192,12 +192,12 @@ class _CWriter:
         _chk(self.lib.H5Fclose(self.f), "H5Fclose")
 
 
-def _c_read(path: str) -> tuple[dict[str, np.ndarray], dict]:
+def _c_read(path: str, want=("feats", "coords", "patch_embeddings")) -> tuple[dict[str, np.ndarray], dict]:
     lib = _lib()
     f = _chk(lib.H5Fopen(str(path).encode(), _F_RDONLY, 0), f"H5Fopen({path})")
     try:
         dsets = {}
-        for name in ("feats", "coords", "patch_embeddings"):
+        for name in want:
             if lib.H5Lexists(f, name.encode(), 0) <= 0:
                 continue
             d = _chk(lib.H5Dopen2(f, name.encode(), 0), f"H5Dopen2({name})")
@@ -418,6 +418,17 @@ def feature_type(attrs: dict) -> str:
     """`detect_feature_type`'s per-file rule (data.py:438-446)."""
     ft, enc = attrs.get("feat_type"), attrs.get("encoder")
     return str(ft) if (ft is not None or enc is not None) else "tile"
+
+
+def file_feature_type(path) -> str:
+    """`feature_type` of a file on disk: the root attributes alone, no dataset is read."""
+    be = backend()
+    if be == "h5py":
+        with _h5py.File(path, "r") as f:
+            return feature_type({k: (v.decode() if isinstance(v, bytes) else v) for k, v in f.attrs.items()})
+    if be == "min":
+        return feature_type(h5min.read(path, want=())[1])
+    return feature_type(_c_read(str(path), want=())[1])
 
 
 @dataclass

@@ -1403,6 +1403,57 @@ def golden_reference_facts() -> None:
     print("wrote reference_facts.json:", len(lines), "files")
 
 
+def golden_feature_table_labels() -> None:
+    """The labels of the reference's slide / patient-level feed, executed as it stands: the `feature_type in {"slide", "patient"}` branch of `create_dataloader`
+    (src/stamp/modeling/data.py:355-419) with `_parse_survival_status` (:1164-1201).  `PatientFeatureDataset` and `DataLoader` are stand-ins that keep what they
+    are handed (the files picked -- a patient's FIRST, :357 -- and the label tensor).  The fixture holds the calls' arguments and what the reference built;
+    tests/test_cpu_feature_table.py replays them through `stamp_amd.cohort.feature_table_labels`."""
+    import json
+    from collections.abc import Callable, Mapping, Sequence
+    from dataclasses import KW_ONLY, dataclass
+    from typing import Any, Generic, TypeVar
+
+    class DatasetStub:
+        def __init__(self, feature_files, ground_truths, transform=None):
+            self.feature_files, self.ground_truths = list(feature_files), ground_truths
+
+    class LoaderStub:
+        def __init__(self, ds, **kw):
+            self.dataset = ds
+
+    seed_stub = types.SimpleNamespace(_is_set=lambda: False, get_loader_worker_init=lambda: None)
+    glb = {"np": np, "torch": torch, "dataclass": dataclass, "KW_ONLY": KW_ONLY, "Sequence": Sequence, "Mapping": Mapping, "Callable": Callable, "Any": Any,
+           "Generic": Generic, "Tensor": torch.Tensor, "Task": str, "Category": str, "GroundTruth": str, "GroundTruthType": TypeVar("G"), "FeaturePath": Path,
+           "_BinaryIOLike": Any, "DataLoader": LoaderStub, "PatientFeatureDataset": DatasetStub, "Seed": seed_stub, "Iterable": __import__("collections.abc").abc.Iterable}
+    exec_defs(REF / "modeling" / "data.py", {"PatientData", "create_dataloader", "_parse_survival_status"}, glb, inherit_future=False)
+    PD, make = glb["PatientData"], glb["create_dataloader"]
+
+    def run(task, gts, files, categories=None, feature_type="slide"):
+        pdata = [PD(ground_truth=g, feature_files=[Path(f"/feat/{n}.h5") for n in fs]) for g, fs in zip(gts, files)]
+        dl, cats = make(feature_type=feature_type, task=task, patient_data=pdata, batch_size=4, shuffle=False, num_workers=0, transform=None, categories=categories)
+        lab = dl.dataset.ground_truths
+        return {"task": task, "feature_type": feature_type, "gts": [list(g) if isinstance(g, tuple) else g for g in gts], "files": files, "categories_in": categories,
+                "picked": [Path(f).stem for f in dl.dataset.feature_files], "labels": [[None if (isinstance(v, float) and np.isnan(v)) else v for v in r] for r in lab.tolist()],
+                "labels_dtype": str(lab.dtype), "categories": [str(c) for c in cats]}
+
+    files = [["a1", "a2"], ["b1"], ["c1", "c2", "c3"], ["d1"], ["e1"], ["f1"]]
+    out = {"cases": {}}
+    gts_cls = ["lum", "basal", "lum", "her2", "basal", "her2"]
+    out["cases"]["classification_inferred"] = run("classification", gts_cls, files)
+    out["cases"]["classification_given"] = run("classification", gts_cls, files, categories=["her2", "lum", "basal"], feature_type="patient")
+    out["cases"]["regression"] = run("regression", [1.5, -2.0, 0.25, 7.0, 0.0, 3.0], files)
+    statuses = ["dead", "alive", "1", "0", "event", "censored", "deceased", "yes", "y", "no", "true", "True", "false", "2.0", "-1", " Dead ", "nan"]
+    gts_surv = [(float(i + 1), s) for i, s in enumerate(statuses)] + [("nan", "dead"), (None, "alive"), ("12.5", 1), (3, 0), "17.25"]
+    out["cases"]["survival"] = run("survival", gts_surv, [[f"s{i}"] for i in range(len(gts_surv))], feature_type="patient")
+    try:
+        glb["_parse_survival_status"]("unknown")
+        out["unknown_status_raises"] = None
+    except ValueError:
+        out["unknown_status_raises"] = "ValueError"
+    (OUT / "feature_table_labels.json").write_text(json.dumps(out, indent=1) + "\n")
+    print(f"wrote feature_table_labels.json ({(OUT / 'feature_table_labels.json').stat().st_size} bytes)")
+
+
 def main() -> None:
     install_shims()
     if len(sys.argv) > 1:          # python tools/make_golden.py golden_abmil ...: only the named fixtures
@@ -1430,6 +1481,7 @@ def main() -> None:
     golden_mlp_cox_transforms()
     golden_bag()
     golden_bag_dataset()
+    golden_feature_table_labels()
     golden_ctranspath()
     golden_texture_gray()
     golden_tiling()
