@@ -20,13 +20,10 @@ import ctypes as C
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from . import _lib, mil_core, ops
 from . import train_ops as T
-from .distributed import average_gradients
-from .mil_train import OneCycleClock
-from .transmil_train import flat_layout
+from .flat_trainer import FlatTrainer
 
 CHIEF_SIZES = {"xs": (384, 256, 256), "small": (768, 512, 256), "big": (1024, 512, 384), "large": (2048, 1024, 512)}      # chief.py:38-43
 # amds_abmil_weights field -> state-dict key
@@ -349,60 +346,25 @@ def group_bags(lengths, bags_per_call: int, max_rows_per_call: int = MAX_ROWS_PE
     return mil_core.group_bags(lengths, bags_per_call, min(int(max_rows_per_call), MAX_ROWS_PER_CALL), mil_core.MAX_SOLO_TILES, 0)
 
 
-class HipAbmilTrainer:
-    """Training of `GatedAttentionMIL` without autograd through the network: the `HipTransMilTrainer` of this head.  One `step` = the reference's
-    `LitTileClassifier._step` (src/stamp/modeling/models/__init__.py:239-279) around amds_abmil_train_forward / _backward, then AdamW under OneCycleLR
-    (:133-141) as ONE fused launch (`amds_adamw`) with torch's own schedule (`mil_train.OneCycleClock`).  `P`, `G`, `m`, `v`: one flat fp32 buffer each, the
-    module's tensors back to back in `state_dict` order; amds_abmil_weights / amds_abmil_grads are built ONCE over their views (the library asks for no alignment
-    of a weight or gradient tensor), so there is nothing to refresh after a step.
-    fp32's range throughout: no loss scale (`skipped_steps` 0, `current_loss_scale` 1.0).  `mil_train.fit` is the epoch loop."""
+class HipAbmilTrainer(FlatTrainer):
+    """Training of `GatedAttentionMIL` without autograd through the network: the `flat_trainer.FlatTrainer` of this head (the flat `P` / `G` / `m` / `v`
+    buffers, their views, the step protocol and the schedule are described there).  One `step` runs around amds_abmil_train_forward / _backward;
+    amds_abmil_weights / amds_abmil_grads are built ONCE over the views (the library asks for no alignment of a weight or gradient tensor), so there is nothing
+    to refresh after a step.  fp32's range throughout: no loss scale.  `mil_train.fit` is the epoch loop."""
 
     valid_max_rows_per_call = 262144
-    skipped_steps = 0
-    current_loss_scale = 1.0
 
     def __init__(self, model: GatedAttentionMIL, *, device="cuda", max_lr: float = 1e-4, div_factor: float = 25.0, total_steps: int = 1000,
                  weight_decay: float = 0.01, dropout: bool | None = None, sched_interval: str = "epoch") -> None:
         """dropout: None = the module's rate at all three sites (train mode); False = off (deterministic steps)."""
-        self.model = model
-        self.dev = torch.device(device)
+        super().__init__(model, device, max_lr=max_lr, div_factor=div_factor, total_steps=total_steps, weight_decay=weight_decay, sched_interval=sched_interval)
         self.dims = tuple(model.dims)
         self.p_drop = model.dropout if (dropout is None or dropout) else 0.0
-        sd = model.state_dict()
-        self.names = list(sd.keys())
-        self.shapes = {k: tuple(v.shape) for k, v in sd.items()}
-        self.offs, n = flat_layout(self.shapes)
-        self.P = torch.cat([sd[k].detach().float().reshape(-1) for k in self.names]).to(self.dev).contiguous()
-        self.G = torch.zeros(n, device=self.dev)
-        self.m = torch.zeros(n, device=self.dev)
-        self.v = torch.zeros(n, device=self.dev)
-        self._pv = {k: self.P[o:o + c].view(self.shapes[k]) for k, (o, c) in self.offs.items()}
-        self._gv = {k: self.G[o:o + c].view(self.shapes[k]) for k, (o, c) in self.offs.items()}
-        self.step_count = 0
-        self.wd = weight_decay
-        self.clock = OneCycleClock(total_steps, max_lr, div_factor, sched_interval)
-        self.train_pred_median = None
         if self.dev.type == "cuda":
             self._w, self._w_keep = _weights_struct(self.p)
             self._gc = _lib.AbmilGrads()
             for field, key in KEYS.items():
                 setattr(self._gc, field, self.g(key).data_ptr())
-
-    def p(self, name: str) -> torch.Tensor:
-        return self._pv[name]
-
-    def g(self, name: str) -> torch.Tensor:
-        return self._gv[name]
-
-    def sync_to_model(self) -> None:
-        self.model.load_state_dict({k: self.p(k).detach().clone() for k in self.names})
-
-    def load_from_model(self) -> None:
-        sd = self.model.state_dict()
-        self.P.copy_(torch.cat([sd[k].detach().float().reshape(-1) for k in self.names]).to(self.dev))
-
-    def _refresh(self) -> None:
-        """`fit` calls this after it restored `P`: the library reads `P` itself, there is no derived copy to rebuild."""
 
     def _check(self, bags: torch.Tensor) -> None:
         if not bags.is_cuda:
@@ -410,43 +372,22 @@ class HipAbmilTrainer:
         if bags.shape[-1] != self.dims[0]:
             raise ValueError(f"bags must be [..., {self.dims[0]}], got {tuple(bags.shape)}")
 
-    def step(self, bags: torch.Tensor, targets: torch.Tensor, class_weights: torch.Tensor | None = None, *, update: bool = True, data_parallel: bool = False,
-             coords: torch.Tensor | None = None, loss_fn=None, seed: int | None = None):
-        """bags [Bb, T, F] fp16 / bf16 / fp32 on the GPU (taken as stored: the library converts while it stages), targets as `loss_fn` wants them (default:
-        float one-hot [Bb, C], the classifier's weighted cross-entropy; `losses.l1_loss`, `losses.cox_survival_loss` for regression / survival).
-        -> (loss, logits).  A batch whose loss has no gradient (a Cox batch without events) takes no step.  seed: this step's dropout seed (default: drawn
-        from torch's CPU generator when dropout is live).  coords: accepted and ignored.  update=False computes loss, logits and gradients only."""
+    @property
+    def dropout_live(self) -> bool:
+        return self.p_drop > 0
+
+    def _check_bags(self, bags: torch.Tensor) -> None:
+        """bags [Bb, T, F] fp16 / bf16 / fp32 on the GPU (taken as stored: the library converts while it stages)."""
         if bags.dim() != 3:
             raise ValueError(f"bags must be [batch, tile, {self.dims[0]}], got {tuple(bags.shape)}")
         self._check(bags)
-        dev = self.dev
-        Bb, Tn, Fd = bags.shape
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.p_drop > 0 else 0
-        logits, saved = forward_train(self._w, self.dims, bags.reshape(Bb * Tn, Fd), _offsets([Tn] * Bb, dev), Bb, p_fc=self.p_drop, p_gate=self.p_drop, seed=seed)
-        with torch.enable_grad():
-            lg = logits.detach().clone().requires_grad_(True)
-            if loss_fn is None:
-                loss = F.cross_entropy(lg, targets.to(dev, torch.float32), weight=None if class_weights is None else class_weights.to(dev, torch.float32))
-            else:
-                loss = loss_fn(lg, targets.to(dev))
-            if not update and not loss.requires_grad:
-                return loss.detach(), logits
-            dlogits = torch.autograd.grad(loss, lg, allow_unused=True)[0] if loss.requires_grad else None
-        if dlogits is None:
-            return loss.detach(), logits
-        backward(saved, dlogits, grads=self._gc)
-        if data_parallel:
-            average_gradients(self.G)
-        if update:
-            self.step_count += 1
-            lr, b1 = self.clock.current()
-            T.adamw(self.P, self.G, self.m, self.v, lr, self.step_count, betas=(b1, 0.999), weight_decay=self.wd)
-            self.clock.after_step()
-        return loss.detach(), logits
 
-    def epoch_end(self) -> None:
-        self.clock.epoch_end()
+    def _forward_train(self, bags, coords, seed):
+        Bb, Tn, Fd = bags.shape
+        return forward_train(self._w, self.dims, bags.reshape(Bb * Tn, Fd), _offsets([Tn] * Bb, self.dev), Bb, p_fc=self.p_drop, p_gate=self.p_drop, seed=seed)
+
+    def _backward(self, saved, dlogits) -> None:
+        backward(saved, dlogits, grads=self._gc)
 
     @torch.no_grad()
     def predict(self, bags: torch.Tensor, coords: torch.Tensor | None = None) -> torch.Tensor:

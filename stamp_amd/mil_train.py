@@ -1,9 +1,10 @@
 """Training of the MIL `vit` head on the HIP path: one optimisation step (forward + backward + AdamW, no autograd through the
-network) and the epoch loop around it.
+network) and the epoch loop around it.  The flat `P` / `G` / `m` / `v` buffers, their views, the step protocol and the schedule's clock are
+`flat_trainer.FlatTrainer`'s (described there, once); this head adds its 16-bit operands and loss scale, the ALiBi buffers and the packed operand copy.
 
 Mirrors what `stamp train` does for tile-level models:
 * per batch -- reference src/stamp/modeling/models/__init__.py:239-279 (`LitTileClassifier._step`: ``logits = self.model(bags,
-  coords=coords, mask=None)``, ``F.cross_entropy(logits, float one-hot targets, weight=class_weights)``), :444-483 (L1), :751-776
+  coords=coords, mask=None)``, the cross-entropy of the logits against float one-hot targets under `class_weights`: `flat_trainer.task_loss`), :444-483 (L1), :751-776
   (Cox); train mode, i.e. WITH the reference's dropout sites (`dropout` on project_features and inside nn.MultiheadAttention, the
   hard-coded 0.5 on both feed-forward Dropouts, vision_tranformer.py:157-169 / 268-271) and with every ALiBi `_RunningMeanScaler`
   updated before use (:24-29);
@@ -43,11 +44,11 @@ import math
 from typing import TYPE_CHECKING
 
 import torch
-import torch.nn.functional as F
 
 from . import losses, metrics, mil_core
 from . import train_ops as T
-from .distributed import average_buffers, average_gradients
+from .distributed import average_buffers
+from .flat_trainer import FlatTrainer, OneCycleClock, onecycle_schedule, task_loss  # noqa: F401  (the schedule names stay importable from here)
 from .mil import VisionTransformer
 from .mil_core import PackedVit
 
@@ -57,46 +58,7 @@ if TYPE_CHECKING:
 BF = torch.bfloat16
 
 
-def onecycle_schedule(total_steps: int, max_lr: float, div_factor: float) -> tuple[list[float], list[float]]:
-    """(lr, beta1) per optimiser step exactly as torch's OneCycleLR drives AdamW (reference models/__init__.py:133-141)."""
-    dummy = torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))], lr=1e-3)
-    sched = torch.optim.lr_scheduler.OneCycleLR(dummy, total_steps=total_steps, max_lr=max_lr, div_factor=div_factor)
-    lrs, b1s = [], []
-    for i in range(total_steps):
-        lrs.append(dummy.param_groups[0]["lr"])
-        b1s.append(dummy.param_groups[0]["betas"][0])
-        dummy.step()
-        if i + 1 < total_steps:
-            sched.step()
-    return lrs, b1s
-
-
-class OneCycleClock:
-    """Position of a trainer on torch's OneCycle (lr, beta1) table.  interval "epoch": the position moves in `epoch_end()` only
-    (what Lightning does with the reference's bare scheduler); "step": it moves after every optimiser step.  Past the table's end
-    the last entry is held (torch's scheduler would raise; Lightning never gets there: max_epochs <= total_steps)."""
-
-    def __init__(self, total_steps: int, max_lr: float, div_factor: float, interval: str = "epoch") -> None:
-        if interval not in ("epoch", "step"):
-            raise ValueError(f"sched_interval must be 'epoch' or 'step', got {interval!r}")
-        self.interval = interval
-        self.lrs, self.b1s = onecycle_schedule(total_steps, max_lr, div_factor)
-        self.pos = 0
-
-    def current(self) -> tuple[float, float]:
-        i = min(self.pos, len(self.lrs) - 1)
-        return self.lrs[i], self.b1s[i]
-
-    def after_step(self) -> None:
-        if self.interval == "step":
-            self.pos += 1
-
-    def epoch_end(self) -> None:
-        if self.interval == "epoch":
-            self.pos += 1
-
-
-class HipMilVitTrainer:
+class HipMilVitTrainer(FlatTrainer):
     def __init__(self, model: VisionTransformer, *, device="cuda", max_lr: float = 1e-4, div_factor: float = 25.0,
                  total_steps: int = 1000, weight_decay: float = 0.01, split_k: int = 32, dropout: bool | None = None,
                  sched_interval: str = "epoch", precision: str | None = None, loss_scale: float = 1024.0, dynamic_loss_scale: bool = True,
@@ -116,35 +78,20 @@ class HipMilVitTrainer:
         # fp16 gradients: a static power-of-two scale on dlogits (exact) lifts the 16-bit gradient tensors out of fp16's subnormal range; un-scaled in fp32
         self.loss_scale = 1.0 if self.act == BF else float(loss_scale)
         self._ls = None                  # the device-resident loss-scale state (train_ops.loss_scale_state), fp16 + dynamic only
-        self.model = model
         self.dims = model.dims
         self.alibi = bool(model.use_alibi)
-        self.dev = torch.device(device)
-        if self.dev.type != "cuda":
+        if torch.device(device).type != "cuda":
             raise RuntimeError("HipMilVitTrainer runs on the GPU only")
         self.use_dropout = True if dropout is None else bool(dropout)
         self.split_k = split_k
-        # flat fp32 master parameters + buffers (reference state_dict order), gradients and Adam moments
-        sd = model.state_dict()
-        self.names = list(sd.keys())                                   # the reference's state_dict order (checkpoints, sync_to_model)
-        self.order = mil_core.flat_order(self.dims, self.names)        # order inside the flat buffers (ALiBi: per-head tensors stacked, mil_core.flat_order)
-        self.shapes = {k: tuple(v.shape) for k, v in sd.items()}
-        self.offs, n = {}, 0
-        for k in self.order:
-            self.offs[k] = (n, int(sd[k].numel()))
-            n += self.offs[k][1]
-        self._pv, self._gv = {}, {}                                    # name -> view (P and G are allocated once)
-        self.P = torch.cat([sd[k].detach().float().reshape(-1) for k in self.order]).to(self.dev).contiguous()
-        self.G = torch.zeros(n, device=self.dev)
-        self.m = torch.zeros(n, device=self.dev)
-        self.v = torch.zeros(n, device=self.dev)
-        self.step_count = 0
-        self.wd = weight_decay
+        # order inside the flat buffers: ALiBi's per-head tensors stacked (mil_core.flat_order); `names` stays the reference's state_dict order
+        super().__init__(model, device, max_lr=max_lr, div_factor=div_factor, total_steps=total_steps, weight_decay=weight_decay, sched_interval=sched_interval,
+                         order=mil_core.flat_order(self.dims, list(model.state_dict().keys())))
         # ALiBi: running_mean / items_so_far are BUFFERS of the reference module (no gradient, no optimiser update)
         stat = [k for k in self.names if mil_core.is_buffer(k)]
         self._stat_idx = torch.tensor([self.offs[k][0] for k in stat], dtype=torch.long, device=self.dev)
-        self.clock = OneCycleClock(total_steps, max_lr, div_factor, sched_interval)
-        self._lrs, self._b1s = self.clock.lrs, self.clock.b1s
+        self._dist_on = False
+        self._eval_pk, self._eval_pk_step = None, -1
         self.pk = PackedVit(self.dims, self.p, self.act, train=True)
         if dynamic_loss_scale and self.act != BF:
             self._ls = T.loss_scale_state(self.dev, self.loss_scale, growth_interval=scale_growth_interval, min_scale=min_loss_scale)
@@ -160,41 +107,16 @@ class HipMilVitTrainer:
     def current_loss_scale(self) -> float:
         return self.loss_scale if self._ls is None else float(T.loss_scale_of(self._ls).item())
 
-    # ---- parameter views ------------------------------------------------------------------------------------------------
-    def p(self, name: str) -> torch.Tensor:
-        v = self._pv.get(name)
-        if v is None:
-            o, n = self.offs[name]
-            v = self._pv[name] = self.P[o:o + n].view(self.shapes[name])
-        return v
+    @property
+    def dropout_live(self) -> bool:
+        return self.use_dropout
 
-    def g(self, name: str) -> torch.Tensor:
-        v = self._gv.get(name)
-        if v is None:
-            o, n = self.offs[name]
-            v = self._gv[name] = self.G[o:o + n].view(self.shapes[name])
-        return v
-
-    def sync_to_model(self) -> None:
-        self.model.load_state_dict({k: self.p(k).detach().clone() for k in self.names})
-
-    def load_from_model(self) -> None:
-        sd = self.model.state_dict()
-        self.P.copy_(torch.cat([sd[k].detach().float().reshape(-1) for k in self.order]).to(self.dev))
-        self._refresh()
-
-    # ---- one optimisation step ------------------------------------------------------------------------------------------------
+    # ---- one optimisation step: `FlatTrainer.step` with this head's loss scale and ALiBi buffers -----------------------------------------------
     def step(self, bags: torch.Tensor, targets: torch.Tensor, class_weights: torch.Tensor | None = None, *, update: bool = True,
              data_parallel: bool = False, coords: torch.Tensor | None = None, loss_fn=None, seed: int | None = None):
-        """bags [Bb,T,F] fp16/bf16/fp32 on the GPU, targets float one-hot [Bb,C]. Returns (loss, logits).
-
-        loss_fn(logits, targets) -> scalar selects the task (stamp_amd.losses): default = the classifier's weighted
-        cross-entropy; `losses.l1_loss` = LitTileRegressor (dim_output 1); `losses.cox_survival_loss` = LitTileSurvival
-        (dim_output 1, targets [time, event]).  seed: dropout seed of this step (default: drawn from torch's CPU generator).
-
-        data_parallel=True: every rank of the initialised process group holds a replica and its own bags; the flat
-        fp32 gradient buffer (14.7 MB for the default head) is averaged with ONE RCCL all-reduce before AdamW
-        (the reference itself is single-device, src/stamp/modeling/train.py:541-547).
+        """bags [Bb,T,F] fp16/bf16/fp32 on the GPU, targets float one-hot [Bb,C]. Returns (loss, logits).  The arguments are `FlatTrainer.step`'s; the flat
+        fp32 gradient buffer (14.7 MB for the default head) is averaged with ONE RCCL all-reduce before AdamW (the reference itself is
+        single-device, src/stamp/modeling/train.py:541-547).
 
         update=False computes loss, logits and gradients and leaves EVERY piece of state as it was: no optimiser step, and the ALiBi
         running-mean buffers (which a train-mode forward updates before use, vision_tranformer.py:24-29) are put back afterwards.  (With a
@@ -202,45 +124,34 @@ class HipMilVitTrainer:
 
         A step the dynamic loss scale skips (non-finite gradient) still advances the OneCycle clock (torch's scheduler under GradScaler),
         keeps the forward's ALiBi running-mean update (as the reference module would) and returns its loss and logits."""
+        self._dist_on = data_parallel and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
+        kw = dict(update=update, data_parallel=data_parallel, coords=coords, loss_fn=loss_fn, seed=seed)
         if update or not self.alibi:
-            return self._step(bags, targets, class_weights, update, data_parallel, coords, loss_fn, seed)
+            return super().step(bags, targets, class_weights, **kw)
         stats_before = self.P[self._stat_idx].clone()
         try:
-            return self._step(bags, targets, class_weights, update, data_parallel, coords, loss_fn, seed)
+            return super().step(bags, targets, class_weights, **kw)
         finally:
             self.P[self._stat_idx] = stats_before
             self._refresh()
 
-    def _step(self, bags, targets, class_weights, update, data_parallel, coords, loss_fn, seed):
-        dev = self.dev
-        dist_on = data_parallel and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.use_dropout else 0
+    def _forward_train(self, bags, coords, seed):
         if self.alibi:
             if coords is None:
                 raise ValueError("use_alibi=True needs coords")
-            cc = mil_core._coords_with_cls(coords, bags.shape[0], dev)
+            cc = mil_core._coords_with_cls(coords, bags.shape[0], self.dev)
             mil_core.update_running_means(self.p, self.dims, cc)
-            if dist_on:      # replicas see different bags: keep the scaler buffers identical (mean of the ranks' updates)
+            if self._dist_on:      # replicas see different bags: keep the scaler buffers identical (mean of the ranks' updates)
                 self.P[self._stat_idx] = average_buffers(self.P[self._stat_idx])
             self._refresh()
-        logits, saved = mil_core.forward_train(self.pk, bags, coords, training=self.use_dropout, seed=seed)
-        # ---- loss on [Bb, C]: the reference's weighted CE with float one-hot targets (models/__init__.py:254-258) ---------------------
-        with torch.enable_grad():
-            lg = logits.detach().clone().requires_grad_(True)
-            if loss_fn is None:
-                loss = F.cross_entropy(lg, targets.to(dev, torch.float32), weight=None if class_weights is None else class_weights.to(dev, torch.float32))
-            else:
-                loss = loss_fn(lg, targets.to(dev))
-            if not update and not loss.requires_grad:
-                return loss.detach(), logits
-            dlogits = torch.autograd.grad(loss, lg, allow_unused=True)[0] if loss.requires_grad else None
-        if dlogits is None:      # e.g. a Cox batch without events (cox.py:219-224 returns a constant 0): nothing to learn from, no step
-            return loss.detach(), logits
+        return mil_core.forward_train(self.pk, bags, coords, training=self.use_dropout, seed=seed)
+
+    def _scale_dlogits(self, dlogits):
         if self._ls is not None:
-            dlogits = dlogits * self._ls_scale          # 0-d device tensor: no synchronisation
-        elif self.loss_scale != 1.0:
-            dlogits = dlogits * self.loss_scale
+            return dlogits * self._ls_scale          # 0-d device tensor: no synchronisation
+        return dlogits * self.loss_scale if self.loss_scale != 1.0 else dlogits
+
+    def _backward(self, saved, dlogits) -> None:
         G, _ = mil_core.backward(self.pk, saved, dlogits, need_params=True, need_bags=False, split_k=self.split_k, grad_views=self.g)
         grouped = self._copy_grouped_grads(G) if self.alibi else ()
         for k, gk in G.items():          # (unpadded geometries: the library wrote into the flat buffer's views themselves -- nothing to copy)
@@ -248,27 +159,27 @@ class HipMilVitTrainer:
                 self.g(k).copy_(gk)
         if self._ls is None and self.loss_scale != 1.0:
             self.G.mul_(1.0 / self.loss_scale)
-        # ---- AdamW + OneCycleLR ---------------------------------------------------------------------------------------------------
-        if dist_on:
-            average_gradients(self.G)        # (dynamic scale: before the check, so every rank counts the same values and takes the same decision)
+
+    def _apply(self, update: bool) -> None:
+        """(The gradient was averaged over the ranks before this: with a dynamic scale every rank counts the same values and takes the same decision.)"""
         if self._ls is not None:
             T.grad_unscale_check(self.G, self._ls)
-        if update:
+        if not update:
+            if self._ls is not None:
+                T.loss_scale_update(self._ls, apply=False)
+            return
+        stats = self.P[self._stat_idx].clone() if self.alibi else None      # buffers: not touched by the optimiser (weight decay)
+        if self._ls is None:
+            super()._apply(True)
+        else:
             self.step_count += 1
             lr, b1 = self.clock.current()
-            stats = self.P[self._stat_idx].clone() if self.alibi else None      # buffers: not touched by the optimiser (weight decay)
-            if self._ls is not None:
-                T.adamw_guarded(self.P, self.G, self.m, self.v, lr, self.step_count, self._ls, betas=(b1, 0.999), weight_decay=self.wd)
-                T.loss_scale_update(self._ls, apply=True)
-            else:
-                T.adamw(self.P, self.G, self.m, self.v, lr, self.step_count, betas=(b1, 0.999), weight_decay=self.wd)
+            T.adamw_guarded(self.P, self.G, self.m, self.v, lr, self.step_count, self._ls, betas=(b1, 0.999), weight_decay=self.wd)
+            T.loss_scale_update(self._ls, apply=True)
             self.clock.after_step()
-            if stats is not None:
-                self.P[self._stat_idx] = stats
-            self._refresh()
-        elif self._ls is not None:
-            T.loss_scale_update(self._ls, apply=False)
-        return loss.detach(), logits
+        if stats is not None:
+            self.P[self._stat_idx] = stats
+        self._refresh()
 
     def _copy_grouped_grads(self, G: dict) -> set:
         """ALiBi: the per-head Linears are 3 x H weights + 3 x H biases + H bias scales per layer -- separate tensors in the reference's state_dict, equally
@@ -290,29 +201,22 @@ class HipMilVitTrainer:
                 done.update(n for row in grp for n in row)
         return done
 
-    def epoch_end(self) -> None:
-        """Lightning steps an epoch-interval scheduler once after every training epoch."""
-        self.clock.epoch_end()
-
     def _refresh(self) -> None:
         """The packed operands follow the master parameters; any cached inference pack is stale from here on."""
         self.pk.refresh(self.p)
         self._eval_pk_step = -1
 
     # ---- evaluation (validation / deploy): inference kernels, fp16 operands, any bag length ---------------------------------------------
-    @torch.no_grad()
-    def predict(self, bags: torch.Tensor, coords: torch.Tensor | None = None) -> torch.Tensor:
-        # the fp16 inference pack is rebuilt whenever the master parameters or buffers changed since it was made (`_refresh`)
-        if getattr(self, "_eval_pk_step", -1) != self.step_count or getattr(self, "_eval_pk", None) is None:
-            self._eval_pk = PackedVit(self.dims, self.p, torch.float16, train=False)
-            self._eval_pk_step = self.step_count
-        return mil_core.forward_infer(self._eval_pk, bags, coords, None)
-
     def _eval_pack(self) -> PackedVit:
-        if getattr(self, "_eval_pk_step", -1) != self.step_count or getattr(self, "_eval_pk", None) is None:
+        # the fp16 inference pack is rebuilt whenever the master parameters or buffers changed since it was made (`_refresh`)
+        if self._eval_pk_step != self.step_count or self._eval_pk is None:
             self._eval_pk = PackedVit(self.dims, self.p, torch.float16, train=False)
             self._eval_pk_step = self.step_count
         return self._eval_pk
+
+    @torch.no_grad()
+    def predict(self, bags: torch.Tensor, coords: torch.Tensor | None = None) -> torch.Tensor:
+        return mil_core.forward_infer(self._eval_pack(), bags, coords, None)
 
     @torch.no_grad()
     def predict_ragged(self, bags, coords=None) -> torch.Tensor:
@@ -325,12 +229,6 @@ class HipMilVitTrainer:
 
     def max_shared_tiles(self) -> int:
         return mil_core.max_shared_tiles(self._eval_pack())
-
-
-def _valid_loss(lg, targets, dev, class_weights, loss_fn):
-    if loss_fn is None:
-        return F.cross_entropy(lg, targets.to(dev, torch.float32), weight=None if class_weights is None else class_weights.to(dev, torch.float32))
-    return loss_fn(lg, targets.to(dev))
 
 
 def _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, per_call: int, keep: list | None = None, with_loss: bool = True) -> tuple[float, int]:
@@ -366,7 +264,7 @@ def _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, per_ca
             if keep is not None:
                 keep.append((lg, targets.to(dev)))
             if with_loss:
-                losses.append(_valid_loss(lg, targets, dev, class_weights, loss_fn).reshape(()))
+                losses.append(task_loss(lg, targets, dev, class_weights, loss_fn).reshape(()))
         for (bags, _c, _t), v in zip(pend, torch.stack(losses).tolist() if losses else ()):
             vtot += float(v) * bags.shape[0]
             vcnt += bags.shape[0]
@@ -467,11 +365,7 @@ def fit(trainer: "HipMilVitTrainer | HipTransMilTrainer", train_batches, valid_b
                 kept.append((lg, targets.to(dev)))
             if cindex:
                 continue
-            if loss_fn is None:
-                vl = F.cross_entropy(lg, targets.to(dev, torch.float32), weight=None if class_weights is None else class_weights.to(dev, torch.float32))
-            else:
-                vl = loss_fn(lg, targets.to(dev))
-            vtot += float(vl) * bags.shape[0]
+            vtot += float(task_loss(lg, targets, dev, class_weights, loss_fn)) * bags.shape[0]
             vcnt += bags.shape[0]
         vloss = vtot / max(vcnt, 1)
         if valid_auroc or valid_auprc:

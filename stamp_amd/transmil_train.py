@@ -1,15 +1,10 @@
-"""Training of the TransMIL head on the HIP path without autograd through the network: `HipTransMilTrainer`, the `HipMilVitTrainer` of `trans_mil`.
+"""Training of the TransMIL head on the HIP path without autograd through the network: `HipTransMilTrainer`, the `flat_trainer.FlatTrainer` of `trans_mil`.
 
-One `step` = the reference's `LitTileClassifier._step` (src/stamp/modeling/models/__init__.py:239-279: ``logits = self.model(bags, coords=coords, mask=None)``,
-the weighted cross-entropy on float one-hot targets; :444-483 L1, :751-776 Cox) around `amds_transmil_train_forward` / `_backward` (ONE library call each,
-csrc/transmil_train.hip), then the optimiser of :133-141 -- ``AdamW(lr=1e-3)`` under ``OneCycleLR`` -- as ONE fused launch (`amds_adamw`) with the
-learning rate and beta1 of torch's own schedule (`mil_train.OneCycleClock`; `sched_interval`: mil_train's module docstring).  `mil_train.fit` is the epoch loop.
-
-What is flat, what is a view:
-* `P`, `G`, `m`, `v` -- one fp32 buffer each, the module's tensors back to back in its `state_dict` order (`flat_layout`); `p(name)` / `g(name)` are views.
-  Every TransMIL tensor holds a multiple of 4 elements except the last one (`_fc2.bias`), so every view starts 16-byte aligned.
+One `step` (`flat_trainer.py`: the flat `P` / `G` / `m` / `v` buffers, their views, the step protocol, the schedule) runs around
+`amds_transmil_train_forward` / `_backward` (ONE library call each, csrc/transmil_train.hip).  What is this head's own:
+* Every TransMIL tensor holds a multiple of 4 elements except the last one (`_fc2.bias`), so every view starts 16-byte aligned.
 * `amds_transmil_weights` is built ONCE over the views of `P`: the training forward, the backward, `amds_transmil_forward` and the ragged forward all read fp32
-  weights, so there is no packed operand copy and nothing to refresh after an optimiser step (`_refresh` is empty).
+  weights, so there is no packed operand copy and nothing to refresh after an optimiser step.
 * `amds_transmil_grads` is built ONCE over the views of `G`: the library writes every gradient where AdamW reads it.  PPEG's six gradients are windows of the
   [50, dim_hidden] tap-correlation table the backward fills (a persistent buffer); `amds_ppeg_grads_unpack` cuts it into `G` in one launch
   (the `nn.Module` path slices it with about ten torch ops, `transmil_core.backward`).
@@ -17,61 +12,34 @@ What is flat, what is a view:
   [Bb, C] logits it returns and the loss's few [Bb, C] tensors; the backward's workspace is `ops.scratch`.
 
 Precision follows `torch.get_float32_matmul_precision()` at every call like the module (exact fp32 MFMA at "highest", bf16 x 3 below;
-`ops.sync_float32_matmul_precision`): fp32's range either way, so there is no operand cast and no loss scale (`skipped_steps` 0, `current_loss_scale` 1.0).
+`ops.sync_float32_matmul_precision`): fp32's range either way, so there is no operand cast and no loss scale.
 Dropout: the reference's one site (`to_out`'s Dropout(0.1), trans_mil.py:63-66) with the module's counter-based masks.  Train-mode `mask` does not exist on
-this path (the reference's Lightning wrappers pass none, models/__init__.py:286-313).  There is no CPU fallback: `step` / `predict*` raise on CPU tensors
-(the constructor itself only lays out buffers, on whatever `device` names).
+this path (the reference's Lightning wrappers pass none, models/__init__.py:286-313).  `coords` are ignored, as the reference's TransMIL ignores them
+(trans_mil.py:299-301).  There is no CPU fallback: `step` / `predict*` raise on CPU tensors (the constructor itself only lays out buffers, on whatever
+`device` names).
 """
 from __future__ import annotations
 
-import math
-
 import torch
-import torch.nn.functional as F
 
 from . import _lib, transmil_core
 from . import train_ops as T
-from .distributed import average_gradients
+from .flat_trainer import FlatTrainer, flat_layout
 from .mil import TransMIL
-from .mil_train import OneCycleClock
 
 _PPEG = ("pos_layer.proj.weight", "pos_layer.proj1.weight", "pos_layer.proj2.weight", "pos_layer.proj.bias", "pos_layer.proj1.bias", "pos_layer.proj2.bias")
 
 
-def flat_layout(shapes: dict) -> tuple[dict, int]:
-    """name -> shape (in `state_dict` order) -> ({name: (offset, numel)}, total): the tensors back to back, in that order, in elements."""
-    offs, n = {}, 0
-    for k, s in shapes.items():
-        offs[k] = (n, math.prod(s))
-        n += offs[k][1]
-    return offs, n
-
-
-class HipTransMilTrainer:
+class HipTransMilTrainer(FlatTrainer):
     valid_max_rows_per_call = 262144          # padded token rows one ragged validation call may hold (`group_valid_bags`; the workspace scales with them)
 
     def __init__(self, model: TransMIL, *, device="cuda", max_lr: float = 1e-4, div_factor: float = 25.0, total_steps: int = 1000,
                  weight_decay: float = 0.01, dropout: bool | None = None, sched_interval: str = "epoch") -> None:
         """dropout: None = the reference's train mode (Dropout(0.1) on both `to_out`s, `transmil_core.P_OUT`); False = off (deterministic steps).
         sched_interval: "epoch" (what Lightning does with the reference's bare scheduler; `fit` calls `epoch_end()`) or "step"."""
-        self.model = model
-        self.dev = torch.device(device)
+        super().__init__(model, device, max_lr=max_lr, div_factor=div_factor, total_steps=total_steps, weight_decay=weight_decay, sched_interval=sched_interval)
         self.dims = (model._fc1[0].in_features, model.dim_hidden, model.n_classes)
         self.use_dropout = True if dropout is None else bool(dropout)
-        sd = model.state_dict()
-        self.names = list(sd.keys())
-        self.shapes = {k: tuple(v.shape) for k, v in sd.items()}
-        self.offs, n = flat_layout(self.shapes)
-        self.P = torch.cat([sd[k].detach().float().reshape(-1) for k in self.names]).to(self.dev).contiguous()
-        self.G = torch.zeros(n, device=self.dev)
-        self.m = torch.zeros(n, device=self.dev)
-        self.v = torch.zeros(n, device=self.dev)
-        self._pv = {k: self.P[o:o + c].view(self.shapes[k]) for k, (o, c) in self.offs.items()}
-        self._gv = {k: self.G[o:o + c].view(self.shapes[k]) for k, (o, c) in self.offs.items()}
-        self.step_count = 0
-        self.wd = weight_decay
-        self.clock = OneCycleClock(total_steps, max_lr, div_factor, sched_interval)
-        self.train_pred_median = None
         Cd = self.dims[1]
         self._corr = torch.zeros(50, Cd, device=self.dev)
         self._w, self._w_keep = transmil_core._c_weights(self.p, Cd)          # (the reshapes inside are views of P: every tensor is contiguous)
@@ -88,77 +56,31 @@ class HipTransMilTrainer:
                                                   g(f"{nm}.attn.to_out.0.bias"), g(f"{nm}.attn.res_conv.weight"))
         return gc
 
-    # ---- the read-outs `fit` asks every trainer for: fp32's range, so no loss scale and no skipped step ---------------------------------------------
-    skipped_steps = 0
-    current_loss_scale = 1.0
-
-    # ---- parameter views -------------------------------------------------------------------------------------------------------------------------------
-    def p(self, name: str) -> torch.Tensor:
-        return self._pv[name]
-
-    def g(self, name: str) -> torch.Tensor:
-        return self._gv[name]
-
-    def sync_to_model(self) -> None:
-        self.model.load_state_dict({k: self.p(k).detach().clone() for k in self.names})
-
-    def load_from_model(self) -> None:
-        sd = self.model.state_dict()
-        self.P.copy_(torch.cat([sd[k].detach().float().reshape(-1) for k in self.names]).to(self.dev))
-
-    def _refresh(self) -> None:
-        """`fit` calls this after it restored `P`: the library reads `P` itself, there is no derived copy to rebuild."""
-
     def _check(self, bags: torch.Tensor) -> None:
         if not bags.is_cuda:
             raise RuntimeError("HipTransMilTrainer needs bags on the GPU (no CPU fallback)")
         if bags.shape[-1] != self.dims[0]:
             raise ValueError(f"bags must be [..., {self.dims[0]}], got {tuple(bags.shape)}")
 
-    # ---- one optimisation step -----------------------------------------------------------------------------------------------------------------------
-    def step(self, bags: torch.Tensor, targets: torch.Tensor, class_weights: torch.Tensor | None = None, *, update: bool = True,
-             data_parallel: bool = False, coords: torch.Tensor | None = None, loss_fn=None, seed: int | None = None):
-        """bags [Bb, T, F] fp16 / bf16 / fp32 on the GPU (taken as they are: the forward converts while it reads), targets float one-hot [Bb, C].
-        -> (loss, logits).  loss_fn(logits, targets) -> scalar selects the task (`losses.l1_loss`, `losses.cox_survival_loss`; default: the classifier's
-        weighted cross-entropy); a batch whose loss has no gradient (a Cox batch without events) takes no step.  seed: this step's dropout seed (default:
-        drawn from torch's CPU generator when dropout is live).  coords: accepted and ignored, as the reference's TransMIL ignores them (trans_mil.py:299-301).
-        data_parallel=True: the flat gradient is averaged over the process group (`distributed.average_gradients`) before AdamW.
-        update=False computes loss, logits and gradients and leaves `P`, `m`, `v`, `step_count` and the schedule's position as they were."""
+    # ---- the head's part of `FlatTrainer.step` -------------------------------------------------------------------------------------------------------
+    @property
+    def dropout_live(self) -> bool:
+        return self.use_dropout
+
+    def _check_bags(self, bags: torch.Tensor) -> None:
+        """bags [Bb, T, F] fp16 / bf16 / fp32 on the GPU (taken as they are: the forward converts while it reads)."""
         if bags.dim() != 3:
             raise ValueError(f"bags must be [batch, tile, {self.dims[0]}], got {tuple(bags.shape)}")
         self._check(bags)
-        dev = self.dev
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.use_dropout else 0
+
+    def _forward_train(self, bags, coords, seed):
         # (the class-row tail is resolved in there, once per step; the backward below reads the same `amds_transmil_cfg` out of `saved`)
-        logits, saved = transmil_core.forward_train(None, bags, self.dims, training=self.use_dropout, seed=seed, weights=(self._w, self._w_keep))
-        # ---- loss on [Bb, C]: the reference's weighted CE with float one-hot targets (models/__init__.py:254-258), as HipMilVitTrainer._step --------------
-        with torch.enable_grad():
-            lg = logits.detach().clone().requires_grad_(True)
-            if loss_fn is None:
-                loss = F.cross_entropy(lg, targets.to(dev, torch.float32), weight=None if class_weights is None else class_weights.to(dev, torch.float32))
-            else:
-                loss = loss_fn(lg, targets.to(dev))
-            if not update and not loss.requires_grad:
-                return loss.detach(), logits
-            dlogits = torch.autograd.grad(loss, lg, allow_unused=True)[0] if loss.requires_grad else None
-        if dlogits is None:      # e.g. a Cox batch without events (cox.py:219-224 returns a constant 0): nothing to learn from, no step
-            return loss.detach(), logits
-        # every parameter gradient of the step into G: the backward writes the views, then PPEG's six leave the correlation table in one launch
+        return transmil_core.forward_train(None, bags, self.dims, training=self.use_dropout, seed=seed, weights=(self._w, self._w_keep))
+
+    def _backward(self, saved, dlogits) -> None:
+        # the backward writes the views of G, then PPEG's six leave the correlation table in one launch
         transmil_core.backward(saved, dlogits, grads=self._gc)
         T.ppeg_grads_unpack(self._corr, *[self.g(k) for k in _PPEG])
-        if data_parallel:
-            average_gradients(self.G)
-        if update:
-            self.step_count += 1
-            lr, b1 = self.clock.current()
-            T.adamw(self.P, self.G, self.m, self.v, lr, self.step_count, betas=(b1, 0.999), weight_decay=self.wd)
-            self.clock.after_step()
-        return loss.detach(), logits
-
-    def epoch_end(self) -> None:
-        """Lightning steps an epoch-interval scheduler once after every training epoch."""
-        self.clock.epoch_end()
 
     # ---- evaluation (validation / deploy): the inference forwards on the master weights themselves ------------------------------------------------------
     @torch.no_grad()

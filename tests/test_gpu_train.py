@@ -209,7 +209,7 @@ def test_mil_vit_training_step_matches_autograd(gpu):
     losses = [tr.step(bags.to(gpu), targets, weights)[0].item() for _ in range(8)]
     assert losses[-1] < losses[0] and torch.isfinite(tr.P).all()
     ref_sched = torch.optim.lr_scheduler.OneCycleLR(torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))], lr=1e-3), total_steps=50, max_lr=1e-3, div_factor=25.0)
-    assert abs(tr._lrs[0] - 1e-3 / 25.0) < 1e-12 and len(tr._lrs) == 50
+    assert abs(tr.clock.lrs[0] - 1e-3 / 25.0) < 1e-12 and len(tr.clock.lrs) == 50
     tr.sync_to_model()
     assert torch.allclose(model.state_dict()["mlp_head.0.bias"].cpu(), tr.p("mlp_head.0.bias").cpu())
 
