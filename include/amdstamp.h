@@ -1967,6 +1967,49 @@ int amds_adamw_guarded(float* p, const float* g, float* m, float* v, long n, flo
  * gradients but applies no update): scale and counters untouched.  Both record the count in last_nonfinite and reset it. */
 int amds_loss_scale_update(amds_loss_scale_state* state, int apply, void* stream);
 
+/* ---- Training objectives on the [batch, outputs] logits (csrc/objective.hip) ---------------------------------------------------------------------------
+ * The loss of the reference's Lightning steps and its gradient with respect to the logits, which stamp_amd/losses.py states in torch:
+ *   AMDS_OBJ_CE           weighted cross-entropy on float (possibly soft) targets y [B][C], class weights w [C] or NULL (reference
+ *                         src/stamp/modeling/models/__init__.py:254-258); with p = softmax(x), computed max-shifted:
+ *                             loss = (1/B) sum_n sum_c -w_c y_nc log p_nc          dlogits_nk = (p_nk sum_c w_c y_nc - w_k y_nk) / B
+ *                         (torch's F.cross_entropy with probability targets and reduction="mean": the divisor is B, not a weight sum).  Any C >= 1.
+ *   AMDS_OBJ_L1           mean |p - t| on [B][1] (models/__init__.py:420-422); dlogits = sign(p - t) / B, sign(0) = 0.
+ *   AMDS_OBJ_COX_EFRON    Cox negative partial log-likelihood, Efron's ties, reduction "mean" (src/stamp/modeling/models/cox.py:107-270, called by
+ *                         models/__init__.py:751-776).  targets [B][2] = (time, event); an event is any value other than 0.  With e_j = exp(lh_j - max lh),
+ *                         and for an event i: R_i = sum(e_j : t_j >= t_i), D_i = sum(e_j : t_j = t_i, j an event), d_i the number of those tied events and
+ *                         r_i = i's place among them (0-based, by item index):
+ *                             loss = -(1/G) sum_{events i} [ (lh_i - max lh) - log(R_i - (r_i / d_i) D_i) ],   G = the number of distinct event times.
+ *                         One formula for the reference's branches: without any tie, censored items included (cox.py:20-34), every group is one event and
+ *                         G is the number of events; with ties (cox.py:37-79) a group's r = 0 .. d-1 terms are its Efron denominator.  The shifted
+ *                         exponential is the reference's function, finite where its unshifted exp overflows fp32.  No event (cox.py:219-224): loss 0,
+ *                         has_grad 0.  A single item that is an event: loss 0, dlogits 0, has_grad 1 (the torch loss is lh - lh there, with a gradient).
+ *   AMDS_OBJ_COX_BRESLOW  the reference's `cox_loss` (models/__init__.py:625-659): risk sets {j : t_j >= t_i} per event i,
+ *                             loss = -(1/E) sum_{events i} [ (lh_i - max lh) - log R_i ],   E = the number of events.
+ *                         No event: loss 0, dlogits 0 and has_grad 0 (the torch expression `scores.sum() * 0.0` keeps a graph whose gradient is zero:
+ *                         a caller that stops on has_grad = 0 skips the weight-decay-only optimiser step torch would take there).
+ * Times and scores must be finite.  Both Cox kinds take C = 1, no weights and B <= amds_objective_max_items() = 4096 (AMDS_ERR_INVALID beyond): the batch
+ * lives in the LDS of one workgroup, 32 bytes per item, ranked by counting.
+ *
+ * amds_objective_step: ONE launch.  logits fp32 [B][C], targets fp32 (CE: [B][C]; L1: [B]; Cox: [B][2]), all contiguous.  Outputs, on the device:
+ *   loss      fp32 scalar;
+ *   dlogits   fp32 [B][C], all zeros when has_grad is 0;
+ *   has_grad  int32: 0 exactly where the loss is a constant of the batch (a Cox batch without an event), 1 otherwise;
+ *   epoch_acc NULL, or fp64 [2] to which one lane of the same launch adds loss * B and B, in stream order: an epoch's `sum(loss_i B_i) / sum(B_i)` needs
+ *             one host read at its end.
+ * dlogits is multiplied by `scale` (host) and then, when scale_dev is not NULL, by *scale_dev (device; the scale of an amds_loss_scale_state) -- the last
+ * two operations, so a power-of-two scale gives scale x the unscaled bits.
+ * amds_objective_rows (CE and L1; a Cox kind returns AMDS_ERR_INVALID: a one-item Cox batch is constant): out[n] = the loss of row n as a batch of its own,
+ * fp32 [N].  Row n's value is a function of row n and the weights alone -- one wave per row, a fixed order over the classes -- so it has the same bits
+ * whether the row is evaluated alone, among N rows, or as the B = 1 case of amds_objective_step.
+ * Everything between the fp32 loads and the one fp32 rounding of a result is fp64.  No atomics, no workspace, nothing written but the outputs; every sum
+ * runs in a fixed order: a call is bitwise reproducible.  Launches only, on `stream`.  NULL pointers, B, C, N < 1, B * C >= 2^31, N >= 2^31 or
+ * N * C >= 2^40 return AMDS_ERR_INVALID before any launch. */
+typedef enum { AMDS_OBJ_CE = 0, AMDS_OBJ_L1 = 1, AMDS_OBJ_COX_EFRON = 2, AMDS_OBJ_COX_BRESLOW = 3 } amds_objective;
+int amds_objective_max_items(void);
+int amds_objective_step(int kind, const float* logits, const float* targets, const float* weight, int B, int C, float scale, const float* scale_dev,
+                        float* loss, float* dlogits, int32_t* has_grad, double* epoch_acc, void* stream);
+int amds_objective_rows(int kind, const float* logits, const float* targets, const float* weight, long N, int C, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -464,6 +464,9 @@ PROTOTYPES = {
     "amds_grad_unscale_check": (_i, [_vp, _l, _vp, _vp]),
     "amds_adamw_guarded": (_i, [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _vp, _vp]),
     "amds_loss_scale_update": (_i, [_vp, _i, _vp]),
+    "amds_objective_max_items": (_i, []),
+    "amds_objective_step": (_i, [_i, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "amds_objective_rows": (_i, [_i, _vp, _vp, _vp, _l, _i, _vp, _vp]),
     "amds_gated_attn_pool_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "amds_gated_attn_pool": (_i, [_vp, C.POINTER(GapWeights), _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "amds_gated_attn_pool_batched_supported": (_i, [_i, _i, _i]),

@@ -475,8 +475,28 @@ class FeatureTableView:
 
     def valid_batches(self):
         """-> the callable `fit` takes for validation: one entry per batch in the view's order ([1, F] views of the store in its own precision, no copy): the
-        reference's batch-1 validation loader (src/stamp/modeling/train.py:467-477)."""
-        return lambda: self._valid()
+        reference's batch-1 validation loader (src/stamp/modeling/train.py:467-477).  The callable also has `block()` -> (feats [N, F], targets [N, D]): the
+        same entries in the same order as ONE gather of the store, for a caller that runs them through one forward (`fit(objective="library")`)."""
+        return _ValidEntries(self)
+
+
+class _ValidEntries:
+    """What `FeatureTableView.valid_batches()` returns: called, it iterates one entry per batch; `block()` hands all of them over as one tensor."""
+
+    def __init__(self, view: FeatureTableView) -> None:
+        self.view = view
+        self._rows = None
+
+    def __call__(self):
+        return self.view._valid()
+
+    def block(self):
+        t = self.view.table
+        if t.device.type != "cuda":
+            raise RuntimeError("a feature table's batches are gathered on the GPU (no CPU fallback)")
+        if self._rows is None:
+            self._rows = self.view._entries_t.to(t.device)          # uploaded once
+        return t.feats.index_select(0, self._rows), t._targets_dev.index_select(0, self._rows)
 
 
 __all__ = ["ResidentCohort", "CohortView", "plan_indices", "MAX_ROWS", "SAMPLERS", "ResidentFeatureTable", "FeatureTableView", "feature_table_labels",

@@ -13,7 +13,8 @@ One `step` = the reference's `_step` (src/stamp/modeling/models/__init__.py:239-
    generator in one order;
 3. `_forward_train(bags, coords, seed) -> (logits, saved)`;
 4. the loss on the [batch, classes] logits, the one tiny piece left to torch (`task_loss`), and `dlogits` by autograd on a detached copy.  A loss without a
-   gradient (a Cox batch without events, cox.py:219-224 returns a constant 0) ends the step here: nothing to learn from, no backward, no optimiser step;
+   gradient (a Cox batch without events, cox.py:219-224 returns a constant 0) ends the step here: nothing to learn from, no backward, no optimiser step.
+   `step(objective="library")` takes both from ONE `amds_objective_step` launch instead, the head's loss scale folded in (`_dlogits_scale`);
 5. `_backward(saved, _scale_dlogits(dlogits))`, which leaves every gradient in `G`;
 6. `distributed.average_gradients(G)` when `data_parallel`;
 7. `_apply(update)`: ONE fused AdamW launch (`amds_adamw`) on the `(lr, beta1)` of torch's own OneCycle schedule (`OneCycleClock`); nothing when `update` is
@@ -89,11 +90,33 @@ def task_loss(logits: torch.Tensor, targets: torch.Tensor, dev, class_weights, l
     return loss_fn(logits, targets.to(dev))
 
 
+OBJECTIVES = ("torch", "library")
+
+
+def objective_kind(loss_fn) -> int:
+    """`loss_fn` -> the library's objective (`train_ops.OBJ_*`): None = the classifier's weighted cross-entropy, `losses.l1_loss`,
+    `losses.cox_survival_loss` (Efron), `losses.cox_slide_survival_loss` (Breslow).  Any other callable has no kernel: ValueError."""
+    from . import losses
+    kinds = {None: T.OBJ_CE, losses.l1_loss: T.OBJ_L1, losses.cox_survival_loss: T.OBJ_COX_EFRON, losses.cox_slide_survival_loss: T.OBJ_COX_BRESLOW}
+    try:
+        return kinds[loss_fn]
+    except (KeyError, TypeError):
+        raise ValueError(f"objective='library' takes loss_fn None (weighted cross-entropy), losses.l1_loss, losses.cox_survival_loss or "
+                         f"losses.cox_slide_survival_loss, got {loss_fn!r}") from None
+
+
+def check_objective(objective: str) -> str:
+    if objective not in OBJECTIVES:
+        raise ValueError(f"objective must be 'torch' or 'library', got {objective!r}")
+    return objective
+
+
 class FlatTrainer:
     # ---- the read-outs `fit` asks every trainer for: fp32's range, so no loss scale and no skipped step ----------------------------------------------
     skipped_steps = 0
     current_loss_scale = 1.0
     dropout_live = False          # a head with dropout sites overrides this: does a step without `seed` draw one?
+    epoch_acc = None              # fp64 [2] on the device once a step ran with objective="library": sum(loss * batch), sum(batch) since `fit` zeroed it
 
     def __init__(self, model, device, *, max_lr: float, div_factor: float, total_steps: int, weight_decay: float, sched_interval: str,
                  order: list | None = None) -> None:
@@ -141,17 +164,37 @@ class FlatTrainer:
 
     # ---- one optimisation step (module docstring) ------------------------------------------------------------------------------------------------------
     def step(self, bags: torch.Tensor, targets: torch.Tensor, class_weights: torch.Tensor | None = None, *, update: bool = True,
-             data_parallel: bool = False, coords: torch.Tensor | None = None, loss_fn=None, seed: int | None = None):
+             data_parallel: bool = False, coords: torch.Tensor | None = None, loss_fn=None, seed: int | None = None, objective: str = "torch"):
         """bags on the GPU as the head takes them, targets as `loss_fn` wants them (default: float one-hot [batch, classes], the classifier's weighted
         cross-entropy; `losses.l1_loss`, `losses.cox_survival_loss` for regression / survival).  -> (loss, logits).  A batch whose loss has no gradient takes
         no step.  seed: this step's dropout seed (default: drawn from torch's CPU generator when dropout is live).  coords: accepted, and ignored by every head
         without a positional term.  data_parallel=True: every rank of the initialised process group holds a replica and its own bags; the flat gradient is
         averaged with ONE all-reduce before AdamW.  update=False computes loss, logits and gradients and leaves `P`, `m`, `v`, `step_count` and the schedule's
-        position as they were."""
+        position as they were.
+        objective="library": loss and dlogits come from ONE `amds_objective_step` launch (`objective_kind(loss_fn)` names the kernel; the head's loss scale is
+        folded into it) instead of torch's loss and autograd.  The loss is a 0-d device tensor and, for cross-entropy and L1, the step reads nothing back;
+        the two Cox kinds read the 4-byte `has_grad` (where the torch path reads `event.sum()`) and a batch without an event takes no step.  The launch also
+        adds loss * batch and batch to `self.epoch_acc` (fp64 [2] on the device), which `fit` reads once per epoch."""
+        check_objective(objective)
+        kind = objective_kind(loss_fn) if objective == "library" else None
         self._check_bags(bags)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.dropout_live else 0
         logits, saved = self._forward_train(bags, coords, seed)
+        if kind is not None:
+            scale, scale_dev = self._dlogits_scale()
+            if self.epoch_acc is None:
+                self.epoch_acc = torch.zeros(2, dtype=torch.float64, device=self.dev)
+            loss, dlogits, has_grad = T.objective_step(kind, logits.detach().float(), targets.to(self.dev, torch.float32),
+                                                       None if class_weights is None or kind != T.OBJ_CE else class_weights.to(self.dev, torch.float32),
+                                                       scale=scale, scale_dev=scale_dev, epoch_acc=self.epoch_acc)
+            if kind in (T.OBJ_COX_EFRON, T.OBJ_COX_BRESLOW) and int(has_grad.item()) == 0:
+                return loss, logits
+            self._backward(saved, dlogits)
+            if data_parallel:
+                average_gradients(self.G)
+            self._apply(update)
+            return loss, logits
         with torch.enable_grad():
             lg = logits.detach().clone().requires_grad_(True)
             loss = task_loss(lg, targets, self.dev, class_weights, loss_fn)
@@ -180,6 +223,10 @@ class FlatTrainer:
     def _scale_dlogits(self, dlogits: torch.Tensor) -> torch.Tensor:
         return dlogits
 
+    def _dlogits_scale(self) -> tuple[float, torch.Tensor | None]:
+        """`_scale_dlogits` as the (host factor, 0-d device factor or None) that `amds_objective_step` multiplies into dlogits itself."""
+        return 1.0, None
+
     def _apply(self, update: bool) -> None:
         if update:
             self.step_count += 1
@@ -192,4 +239,4 @@ class FlatTrainer:
         self.clock.epoch_end()
 
 
-__all__ = ["FlatTrainer", "OneCycleClock", "flat_layout", "onecycle_schedule", "task_loss"]
+__all__ = ["FlatTrainer", "OneCycleClock", "flat_layout", "onecycle_schedule", "task_loss", "objective_kind", "check_objective", "OBJECTIVES"]

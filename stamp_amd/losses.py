@@ -1,7 +1,8 @@
 """Losses of the reference's Lightning steps, evaluated on the [batch, outputs] predictions of the HIP heads.
 
 These tensors hold at most a few hundred scalars: they stay torch ops on purpose -- the trainer feeds the
-HIP logits in, takes d(loss)/d(logits) out of autograd and runs everything with a token dimension in libamdstamp.
+HIP logits in, takes d(loss)/d(logits) out of autograd and runs everything with a token dimension in libamdstamp.  They are also the statement
+`amds_objective_step` / `amds_objective_rows` (csrc/objective.hip, the opt-in `objective="library"` of the trainers and of `fit`) are tested against.
 
 * classification: weighted cross-entropy on float one-hot targets (reference src/stamp/modeling/models/__init__.py:254-258)
 * regression: L1 (`LitBaseRegressor._compute_loss`, :420-422)

@@ -36,7 +36,8 @@ non-finite values (`amds_grad_unscale_check`, replacing the plain multiply); Ada
 halves the scale (floored at `min_loss_scale`) or doubles it after `scale_growth_interval` clean steps, capped at `loss_scale` -- so a
 run that never overflows keeps 2^10 and the static scale's bits exactly.  No host synchronisation inside a step; `skipped_steps` and
 `current_loss_scale` read the state when asked, `fit` records the skipped steps per epoch.  `dynamic_loss_scale=False`: the static scale.
-The loss on the [batch, classes] logits is the one tiny piece left to torch.
+The loss on the [batch, classes] logits is the one tiny piece left to torch by default; `step(objective="library")` / `fit(objective="library")`
+take it from amds_objective_step / amds_objective_rows instead, with this head's loss scale folded into the launch (`_dlogits_scale`).
 """
 from __future__ import annotations
 
@@ -48,7 +49,7 @@ import torch
 from . import losses, metrics, mil_core
 from . import train_ops as T
 from .distributed import average_buffers
-from .flat_trainer import FlatTrainer, OneCycleClock, onecycle_schedule, task_loss  # noqa: F401  (the schedule names stay importable from here)
+from .flat_trainer import FlatTrainer, OneCycleClock, check_objective, objective_kind, onecycle_schedule, task_loss  # noqa: F401  (the schedule names stay importable from here)
 from .mil import VisionTransformer
 from .mil_core import PackedVit
 
@@ -113,7 +114,7 @@ class HipMilVitTrainer(FlatTrainer):
 
     # ---- one optimisation step: `FlatTrainer.step` with this head's loss scale and ALiBi buffers -----------------------------------------------
     def step(self, bags: torch.Tensor, targets: torch.Tensor, class_weights: torch.Tensor | None = None, *, update: bool = True,
-             data_parallel: bool = False, coords: torch.Tensor | None = None, loss_fn=None, seed: int | None = None):
+             data_parallel: bool = False, coords: torch.Tensor | None = None, loss_fn=None, seed: int | None = None, objective: str = "torch"):
         """bags [Bb,T,F] fp16/bf16/fp32 on the GPU, targets float one-hot [Bb,C]. Returns (loss, logits).  The arguments are `FlatTrainer.step`'s; the flat
         fp32 gradient buffer (14.7 MB for the default head) is averaged with ONE RCCL all-reduce before AdamW (the reference itself is
         single-device, src/stamp/modeling/train.py:541-547).
@@ -125,7 +126,7 @@ class HipMilVitTrainer(FlatTrainer):
         A step the dynamic loss scale skips (non-finite gradient) still advances the OneCycle clock (torch's scheduler under GradScaler),
         keeps the forward's ALiBi running-mean update (as the reference module would) and returns its loss and logits."""
         self._dist_on = data_parallel and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
-        kw = dict(update=update, data_parallel=data_parallel, coords=coords, loss_fn=loss_fn, seed=seed)
+        kw = dict(update=update, data_parallel=data_parallel, coords=coords, loss_fn=loss_fn, seed=seed, objective=objective)
         if update or not self.alibi:
             return super().step(bags, targets, class_weights, **kw)
         stats_before = self.P[self._stat_idx].clone()
@@ -150,6 +151,9 @@ class HipMilVitTrainer(FlatTrainer):
         if self._ls is not None:
             return dlogits * self._ls_scale          # 0-d device tensor: no synchronisation
         return dlogits * self.loss_scale if self.loss_scale != 1.0 else dlogits
+
+    def _dlogits_scale(self):
+        return (1.0, self._ls_scale) if self._ls is not None else (self.loss_scale, None)
 
     def _backward(self, saved, dlogits) -> None:
         G, _ = mil_core.backward(self.pk, saved, dlogits, need_params=True, need_bags=False, split_k=self.split_k, grad_views=self.g)
@@ -278,9 +282,33 @@ def _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, per_ca
     return vtot, vcnt
 
 
+def _rows_loss_sum(kept: list, dev, class_weights, loss_fn) -> tuple[float, int]:
+    """The validation sum of `fit(objective="library")`: the kept (logits, targets) of every batch -> one concatenation, ONE `amds_objective_rows` launch,
+    ONE host read of the row losses, added in batch order in Python doubles."""
+    kind = objective_kind(loss_fn)
+    lg = torch.cat([l.float().reshape(l.shape[0], -1) for l, _ in kept])
+    y = torch.cat([t.to(dev, torch.float32).reshape(t.shape[0], -1) for _, t in kept])
+    w = None if class_weights is None or kind != T.OBJ_CE else class_weights.to(dev, torch.float32)
+    vtot = 0.0
+    for v in T.objective_rows(kind, lg, y, w).tolist():
+        vtot += v
+    return vtot, lg.shape[0]
+
+
+def _validate_block(trainer, valid_batches, per_call: int, keep: list) -> None:
+    """Validation entries that are already one tensor (`valid_batches.block()`): `predict` on slices of the trainer's `group_valid_bags` size (or of `per_call`
+    rows), no per-entry view; keep receives each slice's (logits, targets)."""
+    feats, targets = valid_batches.block()
+    N = feats.shape[0]
+    groups = trainer.group_valid_bags([feats.shape[1]] * N, per_call) if hasattr(trainer, "group_valid_bags") else \
+        [(a, min(a + per_call, N)) for a in range(0, N, per_call)]
+    for a, e in groups:
+        keep.append((trainer.predict(feats[a:e]), targets[a:e]))
+
+
 def fit(trainer: "HipMilVitTrainer | HipTransMilTrainer", train_batches, valid_batches, *, max_epochs: int, patience: int = 16, class_weights=None,
         loss_fn=None, log=None, valid_bags_per_call: int = 1, monitor: str = "validation_loss", valid_auroc: bool = False,
-        valid_auprc: bool = False) -> dict:
+        valid_auprc: bool = False, objective: str = "torch") -> dict:
     """The epoch loop of the reference's `train_model_` (src/stamp/modeling/train.py:504-564) around `HipMilVitTrainer.step` or
     `transmil_train.HipTransMilTrainer.step` (any object with their step / predict / predict_ragged / epoch_end / P drives it).
 
@@ -313,7 +341,21 @@ def fit(trainer: "HipMilVitTrainer | HipTransMilTrainer", train_batches, valid_b
     models/__init__.py:217, 270-277); selection is unchanged.
     valid_auprc=True (same conditions): hist["validation_auprc"] holds, per epoch, the mean one-vs-rest average precision
     ``metrics.multiclass_auprc(softmax(logits), argmax(targets))`` over the whole validation set (amds_binary_curves), from the same kept logits as
-    valid_auroc; selection is unchanged, and with the flag off neither the history nor a bit of the run changes."""
+    valid_auroc; selection is unchanged, and with the flag off neither the history nor a bit of the run changes.
+
+    objective="library" (`FlatTrainer` heads; default "torch": today's calls and bits): every training step takes loss and dlogits from ONE
+    `amds_objective_step` launch and `fit` reads no loss per step -- the launches add into `trainer.epoch_acc`, zeroed before an epoch and read once after it:
+    train_loss = acc[0] / acc[1].  Under monitor="validation_loss" every validation batch's logits stay on the device; after the last batch ONE
+    `amds_objective_rows` launch gives the loss of every row as a batch of its own, ONE read brings them to the host, and the host adds them in batch order
+    in Python doubles (a batch of B bags contributes its B rows: its mean times B).  A row's value depends on that row alone, so the history under
+    valid_bags_per_call = k IS the history under 1, float for float, for every trainer.  A `valid_batches` callable with a `block()` method
+    (`FeatureTableView.valid_batches`) is, under valid_bags_per_call > 1, not iterated: `block()` hands over (feats [N, F], targets [N, D]) as one gather and
+    `predict` runs on `group_valid_bags`-sized slices of it.  The Cox kinds have no per-row value (a one-bag Cox batch is a constant): they need
+    monitor="val_cindex", whose whole-set Breslow value stays in torch."""
+    check_objective(objective)
+    library = objective == "library"
+    if library and objective_kind(loss_fn) in (T.OBJ_COX_EFRON, T.OBJ_COX_BRESLOW) and monitor != "val_cindex":
+        raise ValueError("objective='library' with a Cox loss_fn needs monitor='val_cindex' (a one-bag Cox validation batch is a constant)")
     if valid_bags_per_call < 1:
         raise ValueError("valid_bags_per_call must be >= 1")
     if monitor not in ("validation_loss", "val_cindex"):
@@ -334,16 +376,24 @@ def fit(trainer: "HipMilVitTrainer | HipTransMilTrainer", train_batches, valid_b
         hist["validation_auprc"] = []
     wait = 0
     skipped = getattr(trainer, "skipped_steps", 0)          # (any object with the trainer's step / predict / epoch_end drives this loop)
+    step_kw = {"objective": objective} if library else {}
+    rows_loss = library and not cindex                      # validation losses from one amds_objective_rows launch
     for epoch in range(max_epochs):
         tot, cnt, steps = 0.0, 0, 0
         train_scores = []
+        if library and trainer.epoch_acc is not None:
+            trainer.epoch_acc.zero_()
         for bags, coords, _sizes, targets in train_batches():
-            loss, step_logits = trainer.step(bags.to(dev), targets, class_weights, coords=None if coords is None else coords.to(dev), loss_fn=loss_fn)
+            loss, step_logits = trainer.step(bags.to(dev), targets, class_weights, coords=None if coords is None else coords.to(dev), loss_fn=loss_fn,
+                                             **step_kw)
             if cindex:
                 train_scores.append(step_logits.detach().reshape(-1))
-            tot += float(loss) * bags.shape[0]
-            cnt += bags.shape[0]
+            if not library:
+                tot += float(loss) * bags.shape[0]
+                cnt += bags.shape[0]
             steps += 1
+        if library and steps:          # the epoch's one read: what every step's launch added
+            tot, cnt = trainer.epoch_acc.tolist()
         trainer.epoch_end()
         hist["train_loss"].append(tot / max(cnt, 1))
         if cindex and train_scores:
@@ -356,17 +406,21 @@ def fit(trainer: "HipMilVitTrainer | HipTransMilTrainer", train_batches, valid_b
                 f"loss scale now {trainer.current_loss_scale:g}")
         skipped = now
         vtot, vcnt = 0.0, 0
-        kept = [] if cindex or valid_auroc or valid_auprc else None          # every validation batch's (logits, targets), on the device
-        if valid_bags_per_call > 1:
-            vtot, vcnt = _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, valid_bags_per_call, kept, not cindex)
+        kept = [] if cindex or valid_auroc or valid_auprc or rows_loss else None          # every validation batch's (logits, targets), on the device
+        if valid_bags_per_call > 1 and rows_loss and hasattr(valid_batches, "block"):
+            _validate_block(trainer, valid_batches, valid_bags_per_call, kept)
+        elif valid_bags_per_call > 1:
+            vtot, vcnt = _validate_ragged(trainer, valid_batches, dev, class_weights, loss_fn, valid_bags_per_call, kept, not cindex and not rows_loss)
         for bags, coords, _sizes, targets in (valid_batches() if valid_bags_per_call == 1 else ()):
             lg = trainer.predict(bags.to(dev), None if coords is None else coords.to(dev))
             if kept is not None:
                 kept.append((lg, targets.to(dev)))
-            if cindex:
+            if cindex or rows_loss:
                 continue
             vtot += float(task_loss(lg, targets, dev, class_weights, loss_fn)) * bags.shape[0]
             vcnt += bags.shape[0]
+        if rows_loss and kept:
+            vtot, vcnt = _rows_loss_sum(kept, dev, class_weights, loss_fn)
         vloss = vtot / max(vcnt, 1)
         if valid_auroc or valid_auprc:
             lg_all, y_all = torch.cat([lg.float() for lg, _ in kept]), torch.cat([t.float() for _, t in kept])

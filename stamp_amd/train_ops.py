@@ -241,6 +241,57 @@ def loss_scale_update(state: torch.Tensor, apply: bool = True) -> None:
     _lib.check(_lib.lib().amds_loss_scale_update(_p(state), int(bool(apply)), _stream()), "loss_scale_update")
 
 
+# ---- training objectives on the [batch, outputs] logits (amds_objective_step / amds_objective_rows, include/amdstamp.h) ----------------------------------
+OBJ_CE, OBJ_L1, OBJ_COX_EFRON, OBJ_COX_BRESLOW = range(4)
+
+
+def objective_max_items() -> int:
+    """The largest batch a Cox objective takes."""
+    return int(_lib.lib().amds_objective_max_items())
+
+
+def _objective_operands(kind: int, logits: torch.Tensor, targets: torch.Tensor, weight):
+    _dev(logits, targets, weight)
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and targets.dtype == torch.float32
+    logits, targets = logits.contiguous(), targets.contiguous()
+    B, Cc = logits.shape
+    want = B * Cc if kind == OBJ_CE else (B if kind == OBJ_L1 else 2 * B)
+    if targets.numel() != want:
+        raise ValueError(f"targets hold {targets.numel()} values, objective {kind} on logits {tuple(logits.shape)} takes {want}")
+    if weight is not None:
+        assert weight.dtype == torch.float32 and weight.numel() == Cc
+        weight = weight.contiguous()
+    return logits, targets, weight
+
+
+def objective_step(kind: int, logits: torch.Tensor, targets: torch.Tensor, weight: torch.Tensor | None = None, *, scale: float = 1.0,
+                   scale_dev: torch.Tensor | None = None, epoch_acc: torch.Tensor | None = None):
+    """ONE launch: fp32 logits [B, C] and targets (CE: [B, C] float, L1: [B] or [B, 1], Cox: [B, 2] = time, event) -> (loss 0-d fp32, dlogits fp32 [B, C],
+    has_grad 0-d int32), all on the device and nothing read back.  scale / scale_dev (a 0-d fp32 device tensor, `loss_scale_of(state)`): multiplied into
+    dlogits last.  epoch_acc: fp64 [2] on the device, to which the launch adds loss * B and B."""
+    logits, targets, weight = _objective_operands(kind, logits, targets, weight)
+    _dev(scale_dev, epoch_acc)
+    assert scale_dev is None or scale_dev.dtype == torch.float32
+    assert epoch_acc is None or (epoch_acc.dtype == torch.float64 and epoch_acc.numel() == 2 and epoch_acc.is_contiguous())
+    B, Cc = logits.shape
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    has_grad = torch.empty((), dtype=torch.int32, device=logits.device)
+    dlogits = torch.empty_like(logits)
+    _lib.check(_lib.lib().amds_objective_step(int(kind), _p(logits), _p(targets), _p(weight), B, Cc, float(scale), _p(scale_dev), _p(loss), _p(dlogits),
+                                              _p(has_grad), _p(epoch_acc), _stream()), "objective_step")
+    return loss, dlogits, has_grad
+
+
+def objective_rows(kind: int, logits: torch.Tensor, targets: torch.Tensor, weight: torch.Tensor | None = None) -> torch.Tensor:
+    """ONE launch: the loss of every row of fp32 logits [N, C] as a batch of its own -> fp32 [N] on the device; row n has the bits of a one-row call and of
+    `objective_step` on that row alone.  CE and L1."""
+    logits, targets, weight = _objective_operands(kind, logits, targets, weight)
+    N, Cc = logits.shape
+    out = torch.empty(N, dtype=torch.float32, device=logits.device)
+    _lib.check(_lib.lib().amds_objective_rows(int(kind), _p(logits), _p(targets), _p(weight), N, Cc, _p(out), _stream()), "objective_rows")
+    return out
+
+
 def attention_alibi_fwd_train(qkv: torch.Tensor, coords: torch.Tensor, inv_running_mean: torch.Tensor, bias_scale: torch.Tensor,
                               B: int, T: int, H: int):
     """ALiBi attention forward that saves what its backward needs: returns (out, U, Osm: bf16; lse fp32 [B,H,T])."""
